@@ -1,15 +1,20 @@
 #!/usr/bin/env python
 """Headline benchmark: retargeted frames/s of the TS-Net forward at bs=4 per GPU, 256x256, n_source=3.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg1|cfg2|cfg3|cfg4]
+    python bench.py --gpus N --steps K --warmup W [--config cfg1|cfg2|cfg3|cfg4] [--dump-outputs DIR] [--full]
     N>1 either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py
     --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE from the environment) or by itself: without WORLD_SIZE in the environment
     `python bench.py --gpus N` spawns its N ranks (one per GPU, rendezvous on 127.0.0.1) and prints rank 0's line.
 
 A "step" is one forward (tsnet_forward through the C ABI) over one synthetic batch of B=4 (source-set, driving-frame) pairs
 per GPU, inputs resident in HBM, fp32-class arithmetic.  Workload = BASELINE.json configs[1]:
-TSNet(label_nc=2, n_downsampling=3, n_source=3, n_blocks=0), random-init N(0,0.02) weights.  Rank 0 prints ONE JSON line
-(contract in the task statement) with `roofline` and `cpu_baseline` objects.
+TSNet(label_nc=2, n_downsampling=3, n_source=3, n_blocks=0), random-init N(0,0.02) weights.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line (`value`, `ms_per_step`, the
+hipEvent median).  `--full` adds, after the timed region and as before: the per-kernel `roofline` (extra forwards with hipEvents around
+every launch), the `host` enqueue probe, the `cpu_baseline` with its parity figures and gate (N = 1) and, for cfg1, the
+`secondary_bf16_cfg2` figures.  `--dump-outputs DIR` writes what the last timed step returned to its caller (the reconstructed frames,
+DIR/rec_tar_img.npy, float32, rank 0's batch); weights and inputs come from fixed seeds, so two builds compare output for output.
 
 `--config` (default cfg1 = the headline, untouched) runs the other BASELINE.json configs through the SAME rank logic, so that every one
 of them can be measured at N = 1, 2, 4, 8: cfg2 = configs[2] (face-checkpoint shape n_blocks=4, bs=8 per GPU, bf16 operands), cfg3 =
@@ -117,12 +122,30 @@ def _pmc_traffic_bytes(kernel_prefix: str, suffix: str = ""):
     return None, why
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every output of the timed path, float32 (float64 stays float64), whole arrays: the largest configuration's
+    output (cfg2: 8 x 3 x 256 x 256 fp32 = 6.3 MB) is far below DUMP_LIMIT_BYTES."""
+    import numpy as np
+    host = {k: v.detach().cpu() for k, v in arrays.items()}
+    host = {k: (v if v.dtype == torch.float64 else v.float()).numpy() for k, v in host.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def run_rank(*, rank: int, world: int, device, steps: int, warmup: int, lib=None, config: str = "cfg1", batch: int | None = None,
              height: int | None = None, width: int | None = None, model_kw=None, cpu_baseline: bool = True, timing_probe: bool = True,
-             secondary: bool = False) -> dict | None:
+             secondary: bool = False, enqueue_probe: bool = True, dump_dir: str | None = None) -> dict | None:
     """Everything one rank does: replica from rank 0's weights (ONE broadcast), its own batch of independent pairs, W warm-up steps,
     K timed steps between barriers, MAX over ranks.  Returns the result line on rank 0, None elsewhere.  `config` picks the BASELINE.json
-    workload (CONFIGS); batch / height / width / model_kw override it (test hooks: tiny shapes on the emulation build)."""
+    workload (CONFIGS); batch / height / width / model_kw override it (test hooks: tiny shapes on the emulation build).  `dump_dir`:
+    rank 0 writes the last timed step's output there (dump_outputs) before anything else runs on the engine."""
     from wacv23_tsnet_amd import synth
     from wacv23_tsnet_amd.dist import build_replica
     from wacv23_tsnet_amd.engine import TSNetEngine
@@ -180,11 +203,13 @@ def run_rank(*, rank: int, world: int, device, steps: int, warmup: int, lib=None
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, {"rec_tar_img": out})
     # ---- host side of a step (what one thread pays to enqueue a forward -- the scaling question at 8 GPUs is a host question,
     # the ranks exchange nothing per step).  After the timed region, from an idle device: the wall time of `nq` step() calls BEFORE any
     # synchronisation (the HIP queue holds a few thousand packets: five forwards never fill it), beside the time until the device is done.
     host_probe = None
-    if cuda:
+    if cuda and enqueue_probe:
         nq = 5
         sync()
         q0 = time.perf_counter()
@@ -420,8 +445,12 @@ def _rank_main(rank: int, world: int, local_rank: int, args, q=None):
         if CONFIGS[args.config]["model"]["n_blocks"]:
             tk["n_blocks"] = 1
         kw = dict(batch=1, height=32, width=32, model_kw=tk, timing_probe=False)
+    # a plain run times the steps and nothing else; --full adds the probes, the CPU baseline with its parity gate and the secondary figures
+    opts = dict(timing_probe=args.full, enqueue_probe=args.full)
+    opts.update(kw)
     line = run_rank(rank=rank, world=world, device=dev, steps=args.steps, warmup=args.warmup, lib=lib, config=args.config,
-                    cpu_baseline=not args.no_cpu_baseline and world == 1, secondary=not args.no_secondary and world == 1, **kw)
+                    cpu_baseline=args.full and not args.no_cpu_baseline and world == 1,
+                    secondary=args.full and not args.no_secondary and world == 1, dump_dir=args.dump_outputs, **opts)
     if world > 1:
         dist.destroy_process_group()
     if rank == 0:
@@ -446,12 +475,17 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="cfg1", choices=sorted(CONFIGS), help="BASELINE.json workload: cfg1 = configs[1] (the headline, default), cfg2 / cfg3 / cfg4 = configs[2] / [3] / [4]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configs[2] bf16-operand figure")
+    ap.add_argument("--full", action="store_true", help="also the roofline and host probes, the CPU baseline with its parity gate (N = 1) "
+                    "and the secondary configs[2] figures (cfg1, N = 1), after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's output to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity gate")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary configs[2] bf16-operand figure")
     ap.add_argument("--device", default="cuda", help=argparse.SUPPRESS)      # test hooks (CPU tier): "cpu" = gloo + --lib = the emulation build
     ap.add_argument("--lib", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--tiny", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" in os.environ:
         # started by a launcher (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...): one rank per process

@@ -107,3 +107,61 @@ def test_bench_configs_match_baseline_json():
     assert (c["cfg4"]["size"], c["cfg4"]["model"]["n_source"], c["cfg4"]["operands"]) == (512, 5, "bf16") and "512" in base[4] and "n_source=5" in base[4]
     for k, v in c.items():
         assert "BASELINE.json configs[%d]" % v["index"] in v["workload"]
+
+
+def _bench_cpu(bench, emu_path, capsys, *extra):
+    """bench.main at N = 1 with the CPU test hooks (emulation build, tiny shapes); the one line it printed."""
+    bench.main(["--gpus", "1", "--device", "cpu", "--lib", emu_path, "--tiny"] + list(extra))
+    out = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(out) == 1
+    return json.loads(out[0])
+
+
+def test_plain_run_times_the_steps_and_nothing_else(emu_lib, capsys, monkeypatch):
+    """`bench.py --steps K --warmup W` runs exactly W + K forwards, K of them timed, and no other leg: no CPU oracle, no probe, no secondary
+    figure.  The headline keys keep their meaning (value = frames / timed seconds, ms_per_step = timed ms / K)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from conftest import build_emu_lib
+    from oracle import tsnet_oracle as O
+    from wacv23_tsnet_amd.engine import TSNetEngine
+    calls = {"forward": 0, "oracle": 0}
+    fwd, ora = TSNetEngine.forward, O.tsnet_forward
+    monkeypatch.setattr(TSNetEngine, "forward", lambda self, *a, **k: (calls.__setitem__("forward", calls["forward"] + 1), fwd(self, *a, **k))[1])
+    monkeypatch.setattr(O, "tsnet_forward", lambda *a, **k: (calls.__setitem__("oracle", calls["oracle"] + 1), ora(*a, **k))[1])
+    line = _bench_cpu(bench, build_emu_lib(), capsys, "--steps", "3", "--warmup", "2")
+    assert calls == {"forward": 5, "oracle": 0}
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["n_gpus"] == 1 and line["higher_is_better"] is True
+    assert line["metric"] == bench.CONFIGS["cfg1"]["metric"] and line["dtype"] == bench.CONFIGS["cfg1"]["dtype"] and line["unit"] == "frames/s"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 3 / (line["ms_per_step"] * 3 / 1e3)) / line["value"] < 1e-2
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["host"] is None and line["secondary_bf16_cfg2"] is None
+    assert line["max_abs_delta_vs_oracle"] is None
+
+
+def test_full_run_keeps_the_cpu_baseline_and_parity_gate(emu_lib, capsys):
+    """`--full` still runs the CPU oracle beside the timed steps: the baseline figure, the parity figures and their gate."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from conftest import build_emu_lib
+    line = _bench_cpu(bench, build_emu_lib(), capsys, "--steps", "1", "--warmup", "1", "--full")
+    assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["kind"] == "port"
+    assert line["max_abs_delta_vs_oracle"] is not None and line["max_abs_delta_fp64"] is not None and line["parity_gate"] == "ok"
+
+
+def test_dump_outputs_is_the_last_timed_step_and_repeats(emu_lib, capsys, tmp_path, monkeypatch):
+    """`--dump-outputs DIR` writes what the last timed forward returned (rec_tar_img, float32), and two runs with the same arguments
+    write the same bits (seeded weights and inputs)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from conftest import build_emu_lib
+    from wacv23_tsnet_amd.engine import TSNetEngine
+    last = []
+    fwd = TSNetEngine.forward
+    monkeypatch.setattr(TSNetEngine, "forward", lambda self, *a, **k: (lambda r: (last.append(r[0].clone()), r)[1])(fwd(self, *a, **k)))
+    for run in ("a", "b"):
+        _bench_cpu(bench, build_emu_lib(), capsys, "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run))
+    a, b = (np.load(tmp_path / run / "rec_tar_img.npy") for run in ("a", "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["rec_tar_img.npy"]
+    assert a.dtype == np.float32 and a.shape == (1, 3, 32, 32) and np.isfinite(a).all()
+    assert np.array_equal(a, last[2].numpy()) and np.array_equal(a, b)
