@@ -161,13 +161,15 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  *   or 2128 (2 rows x 128: the forward's shape; 12128: its deep schedule, what a launch of at most two workgroups per CU runs); general kernel: 64 or 128 (16-deep steps, conv_h2r.hpp), 3064 / 3128 (64-deep steps,
  *   conv_g64.hpp, 64 / 128 rows: where the layer allows, the forward's choice).
  *   All one-group tiles of one kernel produce identical bits, and so do the two two-group tiles among themselves (tested); the two-group
- *   tiles, and patch vs general kernels, sum K in another association / order: agreement to fp32 rounding.
+ *   tiles, and patch vs general kernels, sum K in another association / order: agreement to fp32 rounding.  Any other kernel or tile value,
+ *   or a code the layer's kernel has no tile for, returns TSNET_ERR_ARG (csrc/conv_plan.hpp decode_tile_code, plan_conv).
  * tsnet_op_conv2d_cat <- the same on torch.cat((x, x2), channel axis) formed on load (dec.map_conv on cat(pg, sg), TSNet.py:163):
  *   x (N,H,W,C1), x2 (x2_nmod,H,W,C2) read at image n % x2_nmod; C1 a multiple of 16.  No input transform.
  * tsnet_op_head <- the decoder's RGB head: ReflectionPad2d(3) + Conv2d(C -> 3, 7x7) + bias + Tanh (TSNet.py:151-152) on relu(alpha*x+beta),
  *   with the pose model's fixed-background composite (TSNet_pose.py:416-417: columns outside [64,192) <- bg) when composite != 0.
  *   x (N,H,W,C) NHWC, w (3,C,7,7), bias (3), bg 3 host floats or NULL; y (N,3,H,W) NCHW.  composite: bit 0 = the composite; bits 8.. = tile
  *   rows of the kernel to force (8, 16, 32; 0 = the launcher's choice by the number of workgroups: every choice gives the same bits).
+ *   Bits 1-7 set, other tile rows, or forced rows with C not a multiple of 16 (the narrow head has no row tiles) return TSNET_ERR_ARG.
  * tsnet_op_instnorm_stats <- nn.InstanceNorm2d statistics (TSNet.py:53; eps 1e-5, biased variance):
  *   alpha = 1/sqrt(var+eps), beta = -mean*alpha, each (N*C).
  * tsnet_op_norm_act   : y = alpha*x+beta (relu optional) ; if resid != NULL y += resid  (ResnetBlock tail, TSNet.py:48)
@@ -271,8 +273,10 @@ int tsnet_resize_pad(const unsigned char* in, int F, int h, int w, const int* yt
                      int pad_top, int pad_left, int OH, int OW, int binarise, float* out, void* stream);
 
 /* Micro-benchmark of one convolution shape on synthetic (non-zero) data: average milliseconds per launch over `iters` back-to-back
- * launches, hipEvent-timed on `stream`.  variant: -1 = the layer's own kernel and tile; else bits 0-11 tile code (tsnet_op_conv2d),
- * bit 12 general kernel, bit 13 bf16 operands, bits 16-23 / 24-31 ablation / experiment masks (tools build).  Diagnostic only. */
+ * launches, hipEvent-timed on `stream`.  variant: -1 = the layer's own kernel and tile; else bits 0-11 tile code (tsnet_op_conv2d; with
+ * bit 15 tiles per workgroup), bit 12 general kernel, bit 13 bf16 operands, bit 14 patch kernel, bit 15 Winograd form, bits 16-20 ablation
+ * mask, bit 21 cold weights, bits 22-27 experiment mask (tools build), bits 28-30 XCD grid (0 the launcher's, 1 linear, 2..5 grids of
+ * 1, 2, 4, 8 columns) -- csrc/conv_plan.hpp decode_bench_variant.  Diagnostic only. */
 int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int pad_mode, int norm,
                      int variant, int iters, float* ms_out, void* stream);
 

@@ -16,9 +16,10 @@
 // Which kernel a layer runs on (the Winograd-along-x kernel of conv_w1.hpp for the ResnetBlock / FuseNet layers and the first two
 // up-convolutions, the patch kernels of conv_h2.hpp where the output splits into 4 x 32 rectangles, the general implicit GEMM of
 // conv_g64.hpp / conv_h2r.hpp elsewhere) and which tile it takes depend on the layer and the frame size only -- never on the batch, never
-// on the environment.  Two launch parameters DO follow the batch -- conv_w1's tiles per workgroup and nothing else -- and are bit-neutral by
-// construction (the same chains per output element in every chunk size): a frame's result is the same bits alone (B = 1) and in any batch
-// (tests/test_gpu_forward.py::test_single_frame_forward).
+// on the environment.  Three launch parameters DO follow the batch -- conv_w1's tiles per workgroup, the stride-2 tile's deep schedule and the
+// RGB head's tile rows -- and are bit-neutral by construction (the same chains per output element in every form): a frame's result is the
+// same bits alone (B = 1) and in any batch
+// (tests/test_gpu_forward.py::test_single_frame_forward).  conv_plan.hpp holds these choices.
 // InstanceNorm statistics: fp64 partial sums in the producing conv's epilogue, finalised there by the last-arriving workgroup
 // (or by in_finalize2 when an image has many tiles).
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include <vector>
 
 #include "../../include/tsnet_abi.h"
+#include "conv_plan.hpp"
 #include "kernels.hpp"
 #include "lmfit.hpp"
 #include "flow_warp.hpp"
@@ -71,16 +73,13 @@ struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; 
 struct WeightError : std::runtime_error { using std::runtime_error::runtime_error; };
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+static_assert(kPlanTileRows == kPatchRows && kPlanTileCols == kPatchCols, "conv_plan.hpp's patch tile is conv_common.hpp's");
 // CUs of the current device (MI355X: 256 in 8 XCDs -- the XCD count is part of the kernels' block -> tile maps, conv_common.hpp; the CU count
-// only enters launch heuristics: how many tiles fill the chip in whole rounds).  Asked once; a device that reports nothing counts as 256.
-inline int device_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 8) v = 256;
-        cus = v;
-    }
-    return cus;
+// only enters launch heuristics: how many tiles fill the chip in whole rounds).  A device that reports nothing counts as 256.
+inline int current_device_cus() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 8) v = 256;
+    return v;
 }
 inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 inline int next_pow2(int x) { int p = 4; while (p < x) p <<= 1; return p; }
@@ -120,9 +119,29 @@ struct Timing {
 };
 
 struct Ctx {            // what a launch helper needs
-    hipStream_t stream = nullptr;
+    hipStream_t stream;
+    int cus;            // CUs of the device the launches go to (launch heuristics only: conv_plan.hpp)
     Timing* timing = nullptr;
     int lane = 0;       // 0 = the caller's stream; 1 = the engine's side stream (own statistics scratch, see tsnet_forward)
+    Ctx(hipStream_t s, int cus_, Timing* t = nullptr, int lane_ = 0) : stream(s), cus(cus_), timing(t), lane(lane_) {}
+};
+
+// a pair of timing events, destroyed on every exit path
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() {
+        HIP_TRY(hipEventCreate(&a));
+        try { HIP_TRY(hipEventCreate(&b)); } catch (...) { (void)hipEventDestroy(a); throw; }
+    }
+    ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    float ms() {            // between the two records, once b has completed
+        HIP_TRY(hipEventSynchronize(b));
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, a, b));
+        return t;
+    }
 };
 
 // Scope guard of a fork onto the engine's side stream: if the scope is left before the explicit join (an exception between fork
@@ -184,8 +203,6 @@ struct DevBufs {
     DevBufs& operator=(const DevBufs&) = delete;
 };
 
-constexpr size_t kFinCounterInts = 65536;   // size of the arrival-counter arrays of the in-kernel statistics finalize
-constexpr int kFinGroup = 32;               // most tiles per image the last-arriving workgroup folds itself (conv_epilogue); above: in_finalize2
 // doubles a convolution's statistics scratch must hold: (sum, sum of squares) per (tile, channel)
 inline size_t stat_part_doubles(size_t N, size_t tpi, size_t Cout) { return N * tpi * Cout * 2; }
 constexpr int KPAD_ALIGN = 32;   // packed weights are K-padded to an even number of 16-deep chunks (fragment prefetch runs up to two past the end)
@@ -209,11 +226,6 @@ struct ConvCall {
     unsigned* amax_out = nullptr;   // publish max |y| per image (operand scale of a consumer without an a-priori bound)
     int x_bf16 = 0, y_bf16 = 0; // bf16 storage mode (bf16-operand kernels only): the input / output tensor holds bf16
     int nprod = 3;              // products per k-group: 3 (4 adds lo*lo), or 1 = bf16 operands
-    int kernel = 0;             // 0 = the layer's own kernel class, 1 = force the general kernel, 2 = require a patch kernel (op tests)
-    int tile = 0;               // 0 = heuristic; else rows * 1000 + width of the patch tile (32, 64, 128 = 4 rows; 2128 = 2 x 128; + 20000 = its
-                                // two-K-group form, 4 x 32 and 4 x 64 only), or 64 / 128 for the others
-    int abl = 0, opt = 0;       // tools build: ablation / experiment masks of h2_tile
-    int xcd_gn = -1;            // -1 = the launcher's choice; 0 = consecutive tiles per XCD; 1, 2, 4, 8 = XCD grid columns over the N tiles (tile_of_block)
     int tclass = TSNET_T_CONV;
 };
 
@@ -228,42 +240,7 @@ inline int h2_scale_log2(float bound) {
     return sa;
 }
 
-// Kernel class of a layer at a frame size.  The patch kernels sum K slab-major, the general one tap-major: the class must depend on the
-// layer and the geometry alone, never on the batch (a sample's result is the same bits in any batch, B = 1 included).
-enum { K_GENERAL = 0, K_H2 = 1, K_H2S = 2, K_H2D = 3, K_W1 = 4, K_H2S32 = 5 };
-// a layer packed in the Winograd-along-x form runs conv_w1 and nothing else: 3 x 3 / stride 1 / pad 1 on frames of whole 4 x 32 tiles
-inline size_t w1_lds_bytes_host(int Cin, int tables) {       // conv_w1.hpp w1_lds_bytes for the two-plane stages
-    return 3 * (size_t)(2 * (4 * 2 * 2 * (96 * 16 + 64) + 32)) + (size_t)tables * 2 * ((Cin + 31) / 32 * 32) * 4;
-}
-inline bool w1_eligible(const ConvLayer& L, int H, int W) {
-    // (the three V stages + the transform table of 2 Cin floats must fit the CU's 160 KiB beside the epilogue's 64 B of static LDS)
-    return L.ks == 3 && L.stride == 1 && L.pad == 1 && L.cin_pad >= 16 && (L.cin_pad & 15) == 0 && H >= 4 && W >= 32 && H % kPatchRows == 0 && W % kPatchCols == 0 &&
-           w1_lds_bytes_host(L.cin_pad, 1) + 256 <= 160 * 1024;
-}
-// eligible_only: what the layer CAN run on (an explicit request, op tests / tools); otherwise what the forward runs it on
-inline int conv_class(const ConvLayer& L, int H, int W, bool two_sources, bool transform, int rows = kPatchRows, bool eligible_only = false, bool bf16 = false) {
-    const int Ho = (H + 2 * L.pad - L.ks) / L.stride + 1, Wo = (W + 2 * L.pad - L.ks) / L.stride + 1;
-    const bool s1 = L.ks == 3 && L.stride == 1 && L.pad == 1 && L.cin_pad >= 16 && (L.cin_pad & 15) == 0 && H >= 2 && W >= 2;
-    if (two_sources || Ho <= 0 || Wo <= 0 || Wo % kPatchCols) return K_GENERAL;
-    const bool s2 = L.ks == 3 && L.stride == 2 && L.pad == 1 && !L.reflect && L.cin_pad >= (eligible_only ? 16 : 128) && (L.cin_pad & 15) == 0 && H == 2 * Ho && W == 2 * Wo;
-    if (rows == 2 && Ho % 2 == 0) {                              // a 2-row tile (requested explicitly, or the stride-2 layers' own choice)
-        if (s1) return K_H2;
-        if (s2) return K_H2D;
-    }
-    if (Ho % kPatchRows) return K_GENERAL;
-    if (s1) return K_H2;
-    if (L.ks == 7 && L.stride == 1 && L.pad == 3 && L.reflect && L.cin_pad == 8 && !transform && H >= 4 && W >= 4) return K_H2S;
-    // the pose model's stems (31 / 28 channels padded to 32): their own patch kernel since round 6 (653 + 231 us on the general kernel at configs[3])
-    if (L.ks == 7 && L.stride == 1 && L.pad == 3 && L.reflect && L.cin_pad == 32 && !transform && H >= 4 && W >= 4) return K_H2S32;
-    // stride 2: the patch kernel from 128 input channels on (117 / 125 us on the 128 -> 256 / 256 -> 512 layers against 132 / 142 us for the
-    // general kernel); with 64 channels the K loop is four slabs long and the general kernel's smaller per-tile prologue wins (147 vs 157 us)
-    // bf16 operands: a third of the MFMA work per staged byte -- the patch tiles' five-round staging binds (459 / 378 us on 128 -> 256 /
-    // 256 -> 512 at 24 images against 180 us for the general kernel's 128-wide tile: profiles/round4_bf16_layers.txt)
-    if (s2 && (eligible_only || !bf16)) return K_H2D;
-    return K_GENERAL;
-}
-
-void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c) {
+void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req = {}) {
     const bool bf16 = c.nprod == 1;
     if (!L.wq) throw ArgError("conv: layer has no packed weights");
     if (L.ks != 1 && L.ks != 3 && L.ks != 7) throw ArgError("conv: kernel size must be 1, 3 or 7");
@@ -291,174 +268,38 @@ void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c) {
         (double)g.M * L.cout >= 2147483647.0 || (double)L.kpad * L.npad * 2 >= 2147483648.0)
         throw ArgError("conv: tensor too large for 32-bit buffer offsets");
     if ((size_t)2 * g.Cin * 4 > 32 * 1024) throw ArgError("conv: too many input channels for the transform table");
-    const int hw = g.Ho * g.Wo;
-    if (L.form == 1 && (c.x2 || !w1_eligible(L, c.H, c.W))) throw ArgError("conv(w1): the layer is packed in the Winograd form, which needs a single source and whole 4 x 32 tiles");
-    if (L.form == 1 && c.nprod == 4) throw ArgError("conv(w1): 1 or 3 products");
-    const int cls = L.form == 1 ? K_W1 : c.kernel == 1 ? K_GENERAL : conv_class(L, c.H, c.W, c.x2 != nullptr, c.alpha != nullptr, c.tile % 10000 >= 1000 ? c.tile % 10000 / 1000 : kPatchRows, c.kernel == 2, bf16);
-    if (c.kernel == 2 && cls == K_GENERAL) throw ArgError("conv: this layer / frame size has no patch kernel");
-    g.fin_alpha = c.fin_alpha; g.fin_beta = c.fin_beta; g.fin_eps = 1e-5f;
-    TimeScope ts(ctx, c.tclass);
-    auto set_tiles = [&](int rows_per_tile_m, int bn) {     // rows_per_tile_m: output positions of an M tile (patch: PR * 32; general: 128)
-        g.tpi = (hw + rows_per_tile_m - 1) / rows_per_tile_m;
-        g.tiles_m = c.N * g.tpi; g.tiles_n = (g.Cout + bn - 1) / bn;
-        g.fin_S = g.tpi;
-        // few tiles per image: the last workgroup of each (image, channel tile) finalises the statistics (conv_epilogue).  Many tiles per
-        // image (the 64^2 .. 256^2 layers): the in_finalize2 launch spreads the fold over C / 16 x N workgroups.  Round 6 measured the
-        // alternative -- a two-level in-kernel finalize, groups of 32 tiles then groups -- against it in one process: 5.062 vs 5.035 ms
-        // per forward for the launch (profiles/round6_ab_twolevel.txt): the last group's serial tail (6 memory round trips + 2 hand-offs
-        // on the stem) costs more than a kernel boundary + a 4 us kernel, once that kernel's loads are batched.
-        g.fin_counter = (c.stat_part && c.fin_counter && g.tpi <= kFinGroup && (size_t)g.N * ((g.Npad + 31) / 32) <= kFinCounterInts) ? c.fin_counter : nullptr;
-    };
-    // 256 CUs each run ceil(tiles / 256) tiles (co-resident workgroups share the MFMA pipe): minimise that count x tile area / efficiency
-    auto wide_pays = [&](long tm, double gain) {
-        const double c64 = (double)((tm * ((g.Cout + 63) / 64) + 255) / 256) * 64.0;
-        const double c128 = (double)((tm * ((g.Cout + 127) / 128) + 255) / 256) * 128.0 / gain;
-        return g.Npad % 128 == 0 && g.Cout > 64 && c128 < c64;
-    };
-    try {
-        if (cls == K_W1) {
-            if (c.opt) throw ArgError("conv(w1): no experiment variants");
-            set_tiles(kPatchRows * kPatchCols, 64);
-            // weight planes far beyond an XCD's L2 (FuseNet's 1024 -> 1024: 50 MB): a 2 x 4 XCD grid streams a quarter of them per XCD (603 -> 565 us)
-            int gn = c.xcd_gn < 0 ? (((double)L.kpad * L.npad * 4 > 16e6) ? 4 : 0) : c.xcd_gn;
-            if (gn && ((gn != 1 && gn != 2 && gn != 4 && gn != 8) || g.tiles_n % gn || g.tiles_m % (8 / gn))) {
-                if (c.xcd_gn >= 0) throw ArgError("conv(w1): the XCD grid does not divide the tile matrix");
-                gn = 0;
-            }
-            g.xcd_gn = gn;
-            // Tiles per workgroup (conv_w1.hpp): chunks of 3 or 2 consecutive spatial tiles of one channel tile -- the prologue of every tile
-            // but a chunk's first disappears under its predecessor's last two periods.  Every XCD owns whole rows of the tile matrix (or its
-            // cell of the XCD grid) and the chunk size must divide their count.  A chunk that crosses into the next image needs the second
-            // transform table in LDS (it fits up to 512 input channels; a raw input has no table); without it chunks stay inside an image.
-            // Chosen where the chunks fill the CUs in whole rounds -- so the chunk size DOES depend on the batch; what keeps a frame's bits
-            // independent of its batch is that every chunk size runs the same chains per output element (bit-identical, tested at the
-            // forward's shapes and under random ones).  c.tile = 1, 2, 3 forces a size (op tests, tools).
-            {
-                const int n = g.tiles_m * g.tiles_n, npp = ((g.Cin >> 4) + 1) / 2;
-                const int rows = gn ? g.tiles_m / (8 / gn) : (g.tiles_m % 8 ? 0 : g.tiles_m / 8);
-                const bool tab2 = !c.alpha || w1_lds_bytes_host(g.Cin, 2) + 256 <= 160 * 1024;
-                // (four periods at least: the fetch stream reads the next tile's periods 0..2 without the last period's tail mask -- with three
-                // periods and an odd slab count, period 2 would stage another pixel's channels past Cin)
-                auto fits = [&](int cc) { return cc == 1 || (c.nprod != 1 && npp >= 4 && rows > 0 && rows % cc == 0 && (tab2 || g.tpi % cc == 0)); };
-                int cc = 1;
-                if (c.tile >= 1 && c.tile <= 3) {
-                    if (!fits(c.tile)) throw ArgError("conv(w1): this chunk size does not fit the layer");
-                    cc = c.tile;
-                } else {
-                    for (int t : {3, 2}) if (fits(t) && n % (device_cus() * t) == 0) { cc = t; break; }
-                }
 #ifdef TSNET_TOOLS
-                if (!c.tile && cc > g_tools_knob[0]) cc = 1;          // tools/forward_ab.py: the same forward with and without chunks, one process
+    req.chunk_cap = g_tools_knob[0];          // tools/forward_ab.py: the same forward with and without chunks, one process
 #endif
-                g.w1_chunk = cc; g.w1_tab2 = (c.alpha && tab2 && cc > 1) ? 1 : 0;
-            }
-            launch_conv_w1(g, c.nprod, c.abl, ctx.stream);
+    ConvShape sh;
+    sh.ks = L.ks; sh.stride = L.stride; sh.pad = L.pad; sh.reflect = L.reflect; sh.cin = L.cin_pad; sh.cout = L.cout; sh.npad = L.npad; sh.kpad = L.kpad;
+    sh.form = L.form; sh.N = c.N; sh.H = c.H; sh.W = c.W; sh.csplit = c.x2 ? c.csplit : 0; sh.transform = c.alpha != nullptr; sh.nprod = c.nprod;
+    sh.fin_counter = c.stat_part && c.fin_counter;
+    TimeScope ts(ctx, c.tclass);
+    try {
+        const ConvPlan p = plan_conv(sh, req, ctx.cus);
+        g.tpi = p.tpi; g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n; g.fin_S = p.tpi; g.xcd_gn = p.xcd_gn;
+        g.fin_alpha = c.fin_alpha; g.fin_beta = c.fin_beta; g.fin_eps = 1e-5f; g.fin_counter = p.fin ? c.fin_counter : nullptr;
+        g.w1_chunk = p.w1_chunk; g.w1_tab2 = p.w1_tab2;
+        const bool res = c.tclass == TSNET_T_CONV_RES;
+        switch (p.family) {
+        case ConvFamily::W1:
+            launch_conv_w1(g, c.nprod, req.abl, ctx.stream);
             ++g_launch_counters[0];
-            if (c.tclass == TSNET_T_CONV_RES) g_launch_counters[3] = 4064 + 30000;      // 4 x 32 pixels x 64 channels, Winograd form
-        } else if (cls == K_H2) {
-            int pr = 4, bn = 0, opt = c.opt;
-            if (c.tile) {
-                const int tc = c.tile % 10000, mode = c.tile / 10000;          // mode 2: deep prefetch + two K groups; 1 / 3: one of the two (tools build)
-                pr = tc >= 1000 ? tc / 1000 : 4; bn = tc % 1000;
-                opt |= mode == 1 ? 8 : (mode == 2 ? 24 : (mode == 3 ? 16 : 0));
-            }
-            if (bn == 0) {
-                // 128-wide tiles (wave tile 64 x 64) move half the LDS / L1 bytes per MFMA: measured 1.07-1.15x per unit area without the
-                // fused transform, 1.03x with it; the 384-tile ResnetBlock layers at batch 4 are the case where 768 64-wide tiles = exactly
-                // three per CU win.  Small M (one driving frame: the decoder's ResnetBlocks are 64 tiles of 128 x 64 on 256 CUs): 32-wide
-                // tiles double the number of workgroups; each stages the same patch but runs half the MFMA chain.
-                const long tm = (long)c.N * (hw / 128);
-                bn = wide_pays(tm, c.alpha ? 1.03 : 1.10) ? 128 : 64;
-                // bf16 operands: one product per step -- the 64-wide tile is latency-bound (mfma_util 0.19, 81 % of the wave cycles
-                // waiting at configs[4]); the 128-wide one runs three workgroups per CU as well (no second accumulator level) and wins
-                // whenever it still fills the chip
-                if (bf16 && g.Npad % 128 == 0 && g.Cout > 64 && tm * ((g.Cout + 127) / 128) >= 256) bn = 128;
-                // (Round 3 gave a forward of ONE frame two-K-group tiles here -- eight waves, total = P0 + P1: another association of the same
-                // chains, so a frame run alone differed from its copy inside a batch in the last bits.  Since round 5 every layer that form
-                // paid on runs conv_w1 in every batch (the decoder's second up-convolution included: 29.7 against 34.0 us for one frame, equal
-                // at B = 4), and the forward no longer takes it: a frame's bits do not depend on its batch, B = 1 included.  The tile codes
-                // 20032 / 20064 stay available to tsnet_op_conv2d.)
-            }
-            // bf16 operands, the 4 x 128 tile: the four waves SIDE BY SIDE (1 x 4, wave tile 128 x 32) instead of 2 x 2 (64 x 64) -- every weight
-            // fragment is loaded once per workgroup instead of twice (the tile was bound by its weight loads: 72 of 80 vector loads per slab),
-            // the A rows double-buffered by tap column: 120.5 -> 107.0 us on the 512 -> 512 layer, 96.1 -> 86.3 us on the decoder's first
-            // up-convolution (profiles/round6_h2_1x4.txt).  Same K order and chains: the same bits as the 2 x 2 form (tests).  Tile code 3128
-            // forces it, 128 (or 4128) the 2 x 2 form.
-            const bool side_by_side = pr == 3 || (!c.tile && bf16 && pr == 4 && bn == 128);
-            if (pr == 3) pr = 4;
-            if (side_by_side && (!bf16 || bn != 128)) throw ArgError("conv(h2): the 1 x 4 wave grid is the bf16 4 x 128 tile's");
-            if ((pr != 2 && pr != 4) || g.Ho % pr) throw ArgError("conv(h2): the output height must be a multiple of the tile's rows (2 or 4)");
-            if (g.Npad % bn) throw ArgError("conv(h2): the tile width must divide the padded output width");
-            set_tiles(pr * kPatchCols, bn);
-            {
-                // weight planes far beyond the 4 MiB of an XCD's L2 (FuseNet: 37.7 MB): a 2 x 4 XCD grid streams a quarter of them per XCD
-                // (-2..3 % on the 1024 -> 1024 layer, nothing on the 512 -> 512 ones: profiles/round3_conv_variants.txt)
-                int gn = c.xcd_gn < 0 ? (((double)L.kpad * L.npad * 4 > 16e6) ? 4 : 0) : c.xcd_gn;
-                if (gn && ((gn != 1 && gn != 2 && gn != 4 && gn != 8) || g.tiles_n % gn || g.tiles_m % (8 / gn))) {
-                    if (c.xcd_gn >= 0) throw ArgError("conv(h2): the XCD grid does not divide the tile matrix");
-                    gn = 0;
-                }
-                g.xcd_gn = gn;
-            }
-            launch_conv_h2(g, side_by_side ? 5 : pr, bn, c.nprod, c.abl, opt, ctx.stream);
+            if (res) g_launch_counters[3] = 4064 + 30000;      // 4 x 32 pixels x 64 channels, Winograd form
+            break;
+        case ConvFamily::H2: {
+            const int opt = req.opt | (p.sched == ConvSched::TwoGroups ? 24 : (p.sched == ConvSched::Deep ? 8 : 0));   // deep prefetch (+ two K groups)
+            launch_conv_h2(g, p.side_by_side ? 5 : p.rows, p.width, c.nprod, req.abl, opt, ctx.stream);
             ++g_launch_counters[0];
-            if (c.tclass == TSNET_T_CONV_RES) g_launch_counters[3] = (side_by_side ? 3 : pr) * 1000 + bn + ((opt & 16) ? 20000 : 0);
-        } else if (cls == K_H2S) {
-            set_tiles(128, 64);
-            launch_conv_h2s(g, c.nprod, ctx.stream);
-            ++g_launch_counters[0];
-        } else if (cls == K_H2S32) {
-            set_tiles(128, 64);
-            launch_conv_h2s32(g, c.nprod, ctx.stream);
-            ++g_launch_counters[0];
-        } else if (cls == K_H2D) {
-            // two rows x 128 columns (four waves, 44 KiB of LDS: three workgroups per CU) wherever the layer is 128 channels wide: 125 -> 99 us
-            // on 256 -> 512, 117 -> 109 us on 128 -> 256 at batch 4, equal or better down to one frame (profiles/round3_conv_variants.txt);
-            // the four-row shapes hold 80 KiB and run one workgroup per CU
-            if (c.tile / 10000 > 1) throw ArgError("conv(h2d): the stride-2 tiles have no two-K-group form (1xxxx: the deep schedule of the 2 x 128 tile)");
-            const int tc = c.tile % 10000;
-            int pr = tc >= 1000 ? tc / 1000 : 4, bn = tc % 1000;          // a code without a width (0, 2000, 4000) leaves the width to the heuristic
-            if (bn == 0) {
-                bn = 64;
-                if (tc < 1000 && g.Npad % 128 == 0 && g.Cout > 64 && g.Ho % 2 == 0) { pr = 2; bn = 128; }
-            }
-            if (pr != 2 && pr != 4) throw ArgError("conv(h2d): tiles have two or four output rows");
-            if (g.Npad % bn) throw ArgError("conv(h2d): the tile width must divide the padded output width");
-            if (g.Ho % pr) throw ArgError("conv(h2d): the output height must be a multiple of the tile's rows");
-            set_tiles(pr * kPatchCols, bn);
-            // A launch of at most two workgroups per CU (a single frame's: 64 .. 384 tiles) runs the deep schedule -- nothing else hides a lone
-            // workgroup's memory round trips (72 -> us on the 64-tile launch).  Same bits: the choice may follow the batch.  Tile code 12128 forces
-            // it, 2128 the plain schedule.
-            const bool deep = c.tile ? c.tile / 10000 == 1 : (pr == 2 && bn == 128 && c.nprod == 3 && (long)g.tiles_m * g.tiles_n <= 2L * device_cus());
-            launch_conv_h2d(g, pr, bn, c.nprod, deep, ctx.stream);
-            ++g_launch_counters[0];
-        } else {
-            if (c.abl || c.opt) throw ArgError("conv: experiment variants exist for the 3x3 / stride-1 patch kernel only");
-            const long tm = (long)c.N * ((hw + 127) / 128);
-            // 64-deep K steps (conv_g64.hpp: the same bits, a quarter of the barriers and address computations, whole cache lines per
-            // load) wherever the layer allows: 1 x 1 / 3 x 3, input channels (and the concat split) multiples of 64, 128-wide output.  In the
-            // forward: the two 1 x 1 convolutions, the 64 -> 128 stride-2 layer and, with bf16 operands, every stride-2 layer.  Tile codes
-            // 3064 / 3128 (with kernel = general) request it with 64 / 128 rows; 64 / 128 request conv_h2r with that width.
-            const bool g64_ok = (L.ks == 1 || L.ks == 3) && (g.Cin & 63) == 0 && (!c.x2 || (g.Csplit & 63) == 0) && g.Npad % 128 == 0 && g.Cout > 64 &&
-                                (c.nprod == 1 || c.nprod == 3);
-            if (c.tile == 3064 || c.tile == 3128 || (!c.tile && g64_ok)) {
-                if (!g64_ok) throw ArgError("conv(g64): needs a 1 x 1 / 3 x 3 layer, input channels in multiples of 64 and more than 64 output channels");
-                // rows per tile: 64 in every batch (with statistics the tile decides the partial sums' grouping, so it may never depend on the
-                // batch: a frame's bits do not)
-                // (measured, tools/g64_variants.py: the 128-row tile -- eight waves at 140 VGPRs: one workgroup per CU -- loses everywhere with
-                // fp16 x 2 operands, 208 vs 156 us on the 64 -> 128 stride-2 layer, and ties with bf16 operands)
-                const int bm = c.tile ? c.tile - 3000 : 64;
-                set_tiles(bm, 128);
-                launch_conv_g64(g, L.ks, bm, c.nprod, ctx.stream);
-                ++g_launch_counters[1];
-            } else {
-            int bn = c.tile ? c.tile : ((L.ks == 3 && L.cin_pad >= 16 && wide_pays(tm, 1.15)) ? 128 : 64);
-            if (bn != 64 && bn != 128) throw ArgError("conv(h2r): the tile width must be 64 or 128");
-            if (g.Npad % bn) throw ArgError("conv(h2r): the tile width must divide the padded output width");
-            set_tiles(128, bn);
-            launch_conv_h2r(g, L.ks, bn, c.nprod, ctx.stream);
-            ++g_launch_counters[1];
-            }
+            if (res) g_launch_counters[3] = (p.side_by_side ? 3 : p.rows) * 1000 + p.width + ((opt & 16) ? 20000 : 0);
+            break;
+        }
+        case ConvFamily::H2S: launch_conv_h2s(g, c.nprod, ctx.stream); ++g_launch_counters[0]; break;
+        case ConvFamily::H2S32: launch_conv_h2s32(g, c.nprod, ctx.stream); ++g_launch_counters[0]; break;
+        case ConvFamily::H2D: launch_conv_h2d(g, p.rows, p.width, c.nprod, p.sched == ConvSched::Deep, ctx.stream); ++g_launch_counters[0]; break;
+        case ConvFamily::G64: launch_conv_g64(g, L.ks, p.rows, c.nprod, ctx.stream); ++g_launch_counters[1]; break;
+        case ConvFamily::H2R: launch_conv_h2r(g, L.ks, p.width, c.nprod, ctx.stream); ++g_launch_counters[1]; break;
         }
     } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     check_launch("conv");
@@ -534,14 +375,14 @@ void run_upsample(Ctx& ctx, const float* x, const float* alpha, const float* bet
 }
 
 // RGB head (head_conv.hpp): head_conv3_kernel for widths that are multiples of 16 (every reference caller: ngf = 64), the
-// one-pixel-per-thread form for narrower nets.  The choice depends on the width alone.
-void launch_head(const HeadArgs& ha, int hh, int ww, int B, hipStream_t s, int force_rows = 0) {
+// one-pixel-per-thread form for narrower nets.  The choice depends on the width alone; head_conv3's tile rows follow conv_plan.hpp head_rows
+// unless force_rows (8, 16, 32: operator tests) says otherwise.
+void launch_head(const HeadArgs& ha, int hh, int ww, int B, hipStream_t s, int cus, int force_rows = 0) {
     if (ha.C % (2 * kHead3Ch) != 0) {
+        if (force_rows) throw ArgError("head: the narrow head (C not a multiple of 16) has no tile rows to force");
         const int tiles = ((ww + kHeadT - 1) / kHeadT) * ((hh + kHeadT - 1) / kHeadT);
         hipLaunchKernelGGL(head_conv_kernel, dim3(tiles, B), dim3(256), 0, s, ha);
     } else {
-        // Tile rows by the number of workgroups (head_conv.hpp): the tallest tile that still gives every CU one -- 32 rows from B = 4 on
-        // at 256^2, 16 at B = 2, 8 for one frame (84 -> 3x us there: eight waves on 64 CUs queue at the LDS pipe).  Same bits for every choice.
         const int tiles_x = (ww + kHead3T - 1) / kHead3T;
         auto go = [&](auto tr) {
             constexpr int TR = decltype(tr)::value;
@@ -549,9 +390,7 @@ void launch_head(const HeadArgs& ha, int hh, int ww, int B, hipStream_t s, int f
             ensure_dynamic_lds(reinterpret_cast<const void*>(head_conv3_kernel<TR>), lds);
             hipLaunchKernelGGL(head_conv3_kernel<TR>, dim3(tiles_x * ((hh + TR - 1) / TR), B), dim3(TR * 16), lds, s, ha);
         };
-        const long cus = device_cus();
-        if (force_rows && force_rows != 8 && force_rows != 16 && force_rows != 32) throw ArgError("head: tile rows 8, 16 or 32");
-        const int rows = force_rows ? force_rows : ((long)B * tiles_x * ((hh + 31) / 32) >= cus ? 32 : ((long)B * tiles_x * ((hh + 15) / 16) >= cus ? 16 : 8));
+        const int rows = force_rows ? force_rows : head_rows(B, tiles_x, hh, cus);
         if (rows == 32) go(std::integral_constant<int, 32>{});
         else if (rows == 16) go(std::integral_constant<int, 16>{});
         else go(std::integral_constant<int, 8>{});
@@ -660,6 +499,7 @@ struct tsnet_engine {
     tsnet_cfg cfg{};
     std::string err;
     bool finalized = false;
+    int cus = 256;                        // CUs of the engine's device, read at tsnet_finalize (launch heuristics only: conv_plan.hpp)
     int C = 0, h = 0, w = 0, P = 0, K = 0, Bmax = 0;
     int cp_img = 0, cp_lbl = 0;
     int np = 3;                           // MFMA products per k-group: 3 (fp16 x 2 operands), or 1 = bf16-operand mode (cfg.operand_mode)
@@ -820,7 +660,7 @@ void tsnet_engine::build_layers() {
     // up-convolutions (128^2: equal; 256^2: 120 against 111 us) and the bf16-operand mode keep the direct kernel.  A layer has ONE packed
     // form and therefore one kernel in every batch.
     auto to_w1 = [&](ConvLayer& L, int hh, int ww) {
-        if (np == 1 || !w1_eligible(L, hh, ww)) return;
+        if (np == 1 || !w1_eligible(L.ks, L.stride, L.pad, L.cin_pad, hh, ww)) return;
         L.form = 1; L.kpad = conv_kpad_w1(L.cin_pad);
     };
     for (size_t i = 1 + c.n_downsampling; i < img_enc.size(); ++i) to_w1(img_enc[i], h, w);
@@ -967,7 +807,7 @@ void tsnet_engine::alloc_all(hipStream_t s) {
     HIP_TRY(hipMalloc((void**)&amax, (size_t)(K + 3) * Bmax * sizeof(unsigned)));
     HIP_TRY(hipMemsetAsync(amax, 0, (size_t)(K + 3) * Bmax * sizeof(unsigned), s));
     // arrival counters: one per (image, 32-channel group) of a launch; launches with more (image, group) pairs than kFinCounterInts
-    // fall back to the in_finalize2 kernel (run_conv checks the index range against this size)
+    // fall back to the in_finalize2 kernel (plan_conv checks the index range against this size)
     HIP_TRY(hipMalloc((void**)&fin_counter, (2 * kFinCounterInts + 256) * sizeof(int)));
     HIP_TRY(hipMemsetAsync(fin_counter, 0, (2 * kFinCounterInts + 256) * sizeof(int), s));
     fin_counter_side = fin_counter + kFinCounterInts;
@@ -1080,7 +920,7 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
     // ---- transformation branch.  Its result (pg) is first needed by the decoder, and its kernels are latency-bound (384 workgroups):
     // with the side stream available it runs there, concurrently with the MFMA-bound synthesis branch below, and joins before dec_map.
     const bool fork = side_stream && !ctx.timing && ctx.lane == 0;
-    Ctx cside; cside.stream = side_stream; cside.lane = 1;
+    Ctx cside(side_stream, cus, nullptr, 1);
     Ctx& cx = fork ? cside : ctx;
     SideJoin join2{fork ? side_stream : nullptr, ctx.stream, ev_join2};
     if (fork) {
@@ -1160,7 +1000,7 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
         ha.N = B; ha.H = hh; ha.W = ww; ha.C = cc; ha.x_bf16 = st16 && cfg.n_downsampling > 0;
         ha.composite = cfg.pose_composite; ha.fore_x0 = 64; ha.fore_x1 = 192;          // TSNet_pose.py:279
         for (int c = 0; c < 3; ++c) ha.bg[c] = (-cfg.pose_mean[c]) / 255.0f;             // TSNet_pose.py:276
-        launch_head(ha, hh, ww, B, ctx.stream);
+        launch_head(ha, hh, ww, B, ctx.stream, ctx.cus);
     }
     last_B = B;
     HIP_TRY(hipEventRecord(ev_done, ctx.stream));       // what tsnet_stage_ptr orders its widening pass behind
@@ -1257,6 +1097,7 @@ int tsnet_finalize(tsnet_handle h, void* stream) {
     for (auto& p : h->params)
         if (!p.loaded) throw WeightError("parameter '" + p.name + "' was never loaded");
     h->alloc_all((hipStream_t)stream);
+    h->cus = current_device_cus();                  // the engine's device: its allocations live there
     h->finalized = true;
     API_END(h)
 }
@@ -1306,7 +1147,7 @@ int tsnet_set_sources(tsnet_handle h, const float* const* src_img, const float* 
     if (!src_img || !src_lbl || !src_bbox) throw ArgError("null source list");
     for (int s = 0; s < h->K; ++s)
         if (!src_img[s] || !src_lbl[s] || !src_bbox[s]) throw ArgError("null source tensor (need n_source entries)");
-    Ctx ctx; ctx.stream = (hipStream_t)stream; ctx.timing = h->timing.on ? &h->timing : nullptr;
+    Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
     h->set_sources(ctx, src_img, src_lbl, src_bbox, B);
     API_END(h)
 }
@@ -1317,7 +1158,7 @@ int tsnet_forward_target(tsnet_handle h, const float* tar_lbl, const float* tar_
     check_forward_args(h, B);
     if (!tar_lbl || !tar_bbox || !out_rgb) throw ArgError("null target/output tensor");
     if (h->cached_B != B) throw ArgError("forward_target: batch differs from the cached sources (call tsnet_set_sources first)");
-    Ctx ctx; ctx.stream = (hipStream_t)stream; ctx.timing = h->timing.on ? &h->timing : nullptr;
+    Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
     h->forward_target(ctx, tar_lbl, tar_bbox, out_rgb, out_flow, B);
     API_END(h)
 }
@@ -1334,7 +1175,7 @@ int tsnet_forward(tsnet_handle h, const float* const* src_img, const float* cons
         hipStream_t main = (hipStream_t)stream;
         HIP_TRY(hipEventRecord(h->ev_fork, main));
         HIP_TRY(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-        Ctx cs; cs.stream = h->side_stream; cs.lane = 1;
+        Ctx cs(h->side_stream, h->cus, nullptr, 1);
         // from here on the side lane has work in flight: whatever happens below (an exception included), the caller's stream waits
         // for it before this call returns -- the side lane must not outlive the call
         SideJoin join{h->side_stream, main, h->ev_join};
@@ -1342,12 +1183,12 @@ int tsnet_forward(tsnet_handle h, const float* const* src_img, const float* cons
         for (int s = 0; s < h->K; ++s)
             if (!src_img[s] || !src_lbl[s] || !src_bbox[s]) throw ArgError("null source tensor (need n_source entries)");
         h->target_chain(cs, tar_lbl, B);
-        Ctx cm; cm.stream = main;
+        Ctx cm(main, h->cus);
         h->set_sources(cm, src_img, src_lbl, src_bbox, B, h->side_stream);      // (the bounding-box copies ride the side lane, ahead of the flow kernel)
         HIP_TRY(hipEventRecord(h->ev_join, h->side_stream));
         HIP_TRY(hipStreamWaitEvent(main, h->ev_join, 0));
         join.done = true;
-        Ctx ctx; ctx.stream = main;
+        Ctx ctx(main, h->cus);
         h->forward_rest(ctx, tar_bbox, out_rgb, out_flow, B);
         API_END(h)
     }
@@ -1527,11 +1368,12 @@ int tsnet_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w
     if (!x || !w_oihw || !y) throw ArgError("null tensor");
     if (nprod != 1 && nprod != 3 && nprod != 4) throw ArgError("conv2d op: 1 (bf16 operands), 3 or 4 products");
     hipStream_t s = (hipStream_t)stream;
-    Ctx ctx; ctx.stream = s;
+    Ctx ctx(s, current_device_cus());
+    ConvRequest req;
+    try { req = decode_tile_code(kernel, tile); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     OpLayer op(w_oihw, bias, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, kernel == 3 ? 1 : 0);     // kernel 3: Winograd-along-x form (conv_w1.hpp)
-    ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y;
-    c.nprod = nprod; c.kernel = kernel == 3 ? 0 : kernel; c.tile = tile;       // kernel 3: tile = tiles per workgroup (0 = the launcher's choice)
-    run_conv(ctx, op.L, c);
+    ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
+    run_conv(ctx, op.L, c, req);
     HIP_TRY(hipStreamSynchronize(s));
     OP_END
 }
@@ -1541,7 +1383,7 @@ int tsnet_op_conv2d_cat(const float* x, const float* x2, int N, int H, int W, in
     OP_BEGIN
     if (!x || !x2 || !w_oihw || !y) throw ArgError("null tensor");
     hipStream_t s = (hipStream_t)stream;
-    Ctx ctx; ctx.stream = s;
+    Ctx ctx(s, current_device_cus());
     OpLayer op(w_oihw, bias, C1 + C2, Cout, ksize, stride, pad, pad_mode, nprod, s);
     ConvCall c; c.x = x; c.x2 = x2; c.csplit = C1; c.x2_nmod = x2_nmod; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
     run_conv(ctx, op.L, c);
@@ -1555,6 +1397,8 @@ int tsnet_op_head(const float* x, int N, int H, int W, int C, const float* in_al
     if (!x || !w_oihw || !bias || !y) throw ArgError("null tensor");
     if (C < 4 || (C & 3)) throw ArgError("head op: C must be a multiple of 4");
     if (in_alpha && !in_beta) throw ArgError("head op: alpha without beta");
+    HeadRequest hr;
+    try { hr = decode_head_code(composite); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     hipStream_t s = (hipStream_t)stream;
     const size_t wn = (size_t)3 * C * 49;
     DevBufs mem;
@@ -1569,9 +1413,9 @@ int tsnet_op_head(const float* x, int N, int H, int W, int C, const float* in_al
     HeadArgs ha{};
     ha.x = x; ha.alpha = in_alpha; ha.beta = in_alpha ? in_beta : nullptr; ha.w = tab; ha.bias = bd; ha.y = y;
     ha.N = N; ha.H = H; ha.W = W; ha.C = C;
-    ha.composite = composite & 1; ha.fore_x0 = 64; ha.fore_x1 = 192;
+    ha.composite = hr.composite; ha.fore_x0 = 64; ha.fore_x1 = 192;
     for (int c = 0; c < 3; ++c) ha.bg[c] = bg ? bg[c] : 0.f;
-    launch_head(ha, H, W, N, s, composite >> 8);               // (bits 8..: tile rows to force -- operator tests; the forward passes 0 / 1)
+    launch_head(ha, H, W, N, s, current_device_cus(), hr.rows);
     HIP_TRY(hipStreamSynchronize(s));
     OP_END
 }
@@ -1579,7 +1423,7 @@ int tsnet_op_head(const float* x, int N, int H, int W, int C, const float* in_al
 int tsnet_op_instnorm_stats(const float* x, int N, int HW, int C, float* alpha, float* beta, void* stream) {
     OP_BEGIN
     if (!x || !alpha || !beta) throw ArgError("null tensor");
-    Ctx ctx; ctx.stream = (hipStream_t)stream;
+    Ctx ctx((hipStream_t)stream, current_device_cus());
     DevBufs mem;
     double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
     run_stats(ctx, x, N, HW, C, part, alpha, beta);
@@ -1591,7 +1435,7 @@ int tsnet_op_norm_act(const float* x, const float* alpha, const float* beta, int
                       int N, int HW, int C, float* y, void* stream) {
     OP_BEGIN
     if (!x || !y) throw ArgError("null tensor");
-    Ctx ctx; ctx.stream = (hipStream_t)stream;
+    Ctx ctx((hipStream_t)stream, current_device_cus());
     run_norm_act(ctx, x, alpha, beta, relu, resid, N, HW, C, y);
     OP_END
 }
@@ -1599,7 +1443,7 @@ int tsnet_op_norm_act(const float* x, const float* alpha, const float* beta, int
 int tsnet_op_upsample2x(const float* x, const float* alpha, const float* beta, int relu, int N, int H, int W, int C, float* y, void* stream) {
     OP_BEGIN
     if (!x || !y) throw ArgError("null tensor");
-    Ctx ctx; ctx.stream = (hipStream_t)stream;
+    Ctx ctx((hipStream_t)stream, current_device_cus());
     run_upsample(ctx, x, alpha, beta, relu, N, H, W, C, y);
     OP_END
 }
@@ -1610,7 +1454,7 @@ static void op_flow_impl(const float* tar_fea, const float* src_fea, const float
     if (!tar_fea || !src_fea || !tar_bbox || !src_bbox || !flow) throw ArgError("null tensor");
     if (B < 1 || K < 1 || K > 8) throw ArgError("flow op: 1 <= K <= 8 sources, B >= 1");
     if (H % h || W % w) throw ArgError("flow op: bbox size must be a multiple of the feature size");
-    Ctx ctx; ctx.stream = stream;
+    Ctx ctx(stream, current_device_cus());
     const int P = h * w, NB = K * B;
     DevBufs bufs;
     auto* that = bufs.alloc<unsigned short>(flow_plane_halves(B, P, C) * 2);
@@ -1633,19 +1477,13 @@ static void op_flow_impl(const float* tar_fea, const float* src_fea, const float
     fa.tq = that; fa.sq = shat; fa.tar_bbox = tar_bbox; fa.gx = gx; fa.gy = gy; fa.flow = flow;
     for (int k = 0; k < K; ++k) fa.src_bbox[k] = src_bbox + (size_t)k * B * H * W;
     fa.B = B; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ms_out) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
+    std::unique_ptr<EventPair> ev(ms_out ? new EventPair : nullptr);
     run_flow(ctx, fa, NB, variant);
-    if (ms_out) HIP_TRY(hipEventRecord(e0, ctx.stream));
+    if (ev) HIP_TRY(hipEventRecord(ev->a, ctx.stream));
     for (int r = 1; r < repeat; ++r) run_flow(ctx, fa, NB, variant);
-    if (ms_out) HIP_TRY(hipEventRecord(e1, ctx.stream));
+    if (ev) HIP_TRY(hipEventRecord(ev->b, ctx.stream));
     HIP_TRY(hipStreamSynchronize(ctx.stream));
-    if (ms_out) {
-        float ms = 0.f;
-        if (repeat > 1) { HIP_TRY(hipEventElapsedTime(&ms, e0, e1)); ms /= (float)(repeat - 1); }
-        *ms_out = ms;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    }
+    if (ms_out) *ms_out = repeat > 1 ? ev->ms() / (float)(repeat - 1) : 0.f;
 }
 
 int tsnet_op_flow(const float* tar_fea, const float* src_fea, const float* tar_bbox, const float* src_bbox,
@@ -1668,7 +1506,7 @@ int tsnet_op_warp(const float* src_fea, const float* flow, int B, int h, int w, 
     OP_BEGIN
     if (!src_fea || !flow || !out) throw ArgError("null tensor");
     if (C & 3) throw ArgError("warp op: C must be a multiple of 4");
-    Ctx ctx; ctx.stream = (hipStream_t)stream;
+    Ctx ctx((hipStream_t)stream, current_device_cus());
     run_warp(ctx, src_fea, flow, out, B, 1, h, w, C);
     OP_END
 }
@@ -1678,19 +1516,15 @@ int tsnet_op_warp_k(const float* src_fea, const float* flow, int B, int K, int h
     if (!src_fea || !flow || !out) throw ArgError("null tensor");
     if (C & 3) throw ArgError("warp op: C must be a multiple of 4");
     if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape");
-    Ctx ctx; ctx.stream = (hipStream_t)stream;
+    Ctx ctx((hipStream_t)stream, current_device_cus());
     if (ms_out) *ms_out = 0.f;
     run_warp(ctx, src_fea, flow, out, B, K, h, w, C);
     if (repeat > 1) {                    // launches 2 .. repeat between two events: the kernel ALONE (tools/warp_bench.py)
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, ctx.stream));
+        EventPair ev;
+        HIP_TRY(hipEventRecord(ev.a, ctx.stream));
         for (int i = 1; i < repeat; ++i) run_warp(ctx, src_fea, flow, out, B, K, h, w, C);
-        HIP_TRY(hipEventRecord(e1, ctx.stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        HIP_TRY(hipEventRecord(ev.b, ctx.stream));
+        const float t = ev.ms();
         if (ms_out) *ms_out = t / (float)(repeat - 1);
     }
     OP_END
@@ -1860,11 +1694,11 @@ int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stri
     OP_BEGIN
     if (iters < 1 || !ms_out) throw ArgError("bench_conv: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    Ctx ctx; ctx.stream = s;
-    // variant (-1 = the layer's own kernel and tile): bits 0-11 tile code (ConvCall::tile), bit 12 general kernel, bit 13 bf16 operands, bit 14 patch kernel,
-    // bits 16-20 ablation mask, bit 21 cold weights (a fresh copy of the planes per launch), bit 22 weights five steps ahead, bit 23 two K groups, bits 24-27 experiment mask (8 = deep prefetch; the rest tools build), bits 28-30 XCD grid
-    const int v = variant < 0 ? 0 : variant;
-    const int nprod = (v & 8192) ? 1 : 3;
+    Ctx ctx(s, current_device_cus());
+    // variant (-1 = the layer's own kernel and tile): conv_plan.hpp decode_bench_variant
+    BenchVariant bv;
+    try { bv = decode_bench_variant(variant); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    const int nprod = bv.nprod;
     const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
     const size_t xn = (size_t)N * H * W * Cin, yn = (size_t)N * Ho * Wo * Cout, wn = (size_t)Cout * Cin * ksize * ksize;
     DevBufs mem;
@@ -1880,15 +1714,13 @@ int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stri
     fill(x, xn, 2.f, 0.f); fill(al, (size_t)N * Cin, 1.f, 1.f); fill(be, (size_t)N * Cin, 0.5f, 0.f);
     fill(nullptr, wn, 0.1f, 0.f);
     {
-        const int form = (v & 32768) ? 1 : 0;                       // bit 15: Winograd-along-x form
+        const int form = bv.form;
         OpLayer op(hbuf.data(), nullptr, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, form);
-        // bit 21: COLD weights -- every launch reads another copy of the packed planes (24 copies: beyond the 256 MiB Infinity Cache for the
+        // COLD weights -- every launch reads another copy of the packed planes (24 copies: beyond the 256 MiB Infinity Cache for the
         // big layers), as consecutive layers of a forward do; the default re-launches one layer, whose planes stay cache-resident
         std::vector<std::unique_ptr<OpLayer>> cold;
-        if (v & (1 << 21)) for (int i = 0; i < 24; ++i) cold.emplace_back(new OpLayer(hbuf.data(), nullptr, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, form));
+        if (bv.cold) for (int i = 0; i < 24; ++i) cold.emplace_back(new OpLayer(hbuf.data(), nullptr, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, form));
         ConvCall c; c.x = x; c.N = N; c.H = H; c.W = W; c.y = y; c.bound = (norm & 1) ? 64.f : 1.f; c.nprod = nprod;
-        c.tile = v & 4095;          /* Winograd form: tiles per workgroup (0 = the launcher's choice) */ c.kernel = (v & 4096) ? 1 : ((v & 16384) ? 2 : 0); c.abl = (v >> 16) & 31; c.opt = ((v >> 24) & 15) | ((v & (1 << 23)) ? 16 : 0) | ((v & (1 << 22)) ? 32 : 0);
-        { const int gx = (v >> 28) & 7; c.xcd_gn = gx == 0 ? -1 : (gx == 1 ? 0 : 1 << (gx - 2)); }          // bits 28-30: 0 default, 1 linear, 2..5 grid with 1, 2, 4, 8 columns
         if (norm & 1) { c.alpha = al; c.beta = be; c.relu = 1; }
         if (norm & 2) {                                              // with the InstanceNorm statistics of the output, as the forward's layers run
             const size_t tpi = ((size_t)Ho * Wo + 63) / 64;
@@ -1897,17 +1729,12 @@ int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stri
             c.fin_counter = mem.alloc<int>(kFinCounterInts * sizeof(int));
             HIP_TRY(hipMemset(c.fin_counter, 0, kFinCounterInts * sizeof(int)));
         }
-        for (int i = 0; i < 2; ++i) run_conv(ctx, op.L, c);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) run_conv(ctx, cold.empty() ? op.L : cold[(size_t)i % cold.size()]->L, c);
-        HIP_TRY(hipEventRecord(e1, s));
-        HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        *ms_out = ms / iters;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        for (int i = 0; i < 2; ++i) run_conv(ctx, op.L, c, bv.req);
+        EventPair ev;
+        HIP_TRY(hipEventRecord(ev.a, s));
+        for (int i = 0; i < iters; ++i) run_conv(ctx, cold.empty() ? op.L : cold[(size_t)i % cold.size()]->L, c, bv.req);
+        HIP_TRY(hipEventRecord(ev.b, s));
+        *ms_out = ev.ms() / iters;
     }
     OP_END
 }
