@@ -87,22 +87,21 @@ def conv_h2r_case(lib, dev, N, H, W, Cin, Cout, ksize, norm=False, bias=True, se
     return conv_case(lib, dev, N, H, W, Cin, Cout, 3, 2, 1, False, norm=norm, bias=bias, seed=seed, kernel=kernel, tile=tile, return_output=return_output)
 
 
-def conv_cat_case(lib, dev, N, H, W, C1, C2, Cout, k=1, seed=0, shared=False):
+def conv_cat_case(lib, dev, N, H, W, C1, C2, Cout, k=1, seed=0, shared=False, nprod=3, ref="fp64"):
     """convolution of torch.cat((x, x2), dim=1) with the concat formed on load (dec.map_conv on cat(pg, sg), TSNet.py:163); `shared`: x2 has
-    one image that every image of x is concatenated with (image index n % x2_nmod)."""
+    one image that every image of x is concatenated with (image index n % x2_nmod).  nprod as conv_case's (the forward's bf16 modes run
+    this layer with 1); ref: "fp64" (the unrounded convolution) or "bf16" (the operand-exact reference, bf16_conv_ref)."""
     x = _rand(seed, "x", (N, C1, H, W))
     x2 = _rand(seed, "x2", (1 if shared else N, C2, H, W)) * 3.0
     w = _rand(seed, "w", (Cout, C1 + C2, k, k)) * (2.0 / ((C1 + C2) * k * k) ** 0.5)
     b = _rand(seed, "b", (Cout,))
     xin = torch.cat([x, x2.expand(N, -1, -1, -1)], dim=1)
-    ref = F.conv2d(xin.double(), w.double(), b.double(), padding=k // 2)
-    y = torch.full((N, H, W, Cout), float("nan"), device=dev)
-    xd, x2d, wd, bd = nhwc(x).to(dev), nhwc(x2).to(dev), w.to(dev), b.to(dev)
-    rc = lib.tsnet_op_conv2d_cat(xd.data_ptr(), x2d.data_ptr(), N, H, W, C1, C2, x2.shape[0], wd.data_ptr(), bd.data_ptr(), Cout, k, 1, k // 2, 0,
-                                 float(xin.abs().max()) * 1.0001, 3, y.data_ptr(), None)
-    assert rc == 0, lib.tsnet_op_last_error().decode()
-    _sync(dev)
-    return ((nchw(y.cpu()).double() - ref).abs().max() / ref.abs().max()).item()
+    if ref == "bf16":
+        r = bf16_conv_ref(xin, w, b, None, None, False, 1, k // 2, False)
+    else:
+        r = F.conv2d(xin.double(), w.double(), b.double(), padding=k // 2)
+    y = run_cat_op(lib, dev, x, x2, w, b, k, nprod, float(xin.abs().max()) * 1.0001)
+    return ((y.double() - r).abs().max() / r.abs().max()).item()
 
 
 def head_case(lib, dev, N, H, W, C, norm=True, composite=False, seed=0, rows=0, return_output=False):
@@ -453,3 +452,310 @@ def conv_h2s32_cases(lib, dev, big=False):
         if nprod == 3:
             worst = max(worst, conv_case(lib, dev, N, H, W, 32, Cout, 7, 1, 3, True, nprod=nprod, bias=bias, seed=seed, kernel=2))
     return worst
+
+
+# ---- bf16 operands (nprod = 1, tsnet_cfg.operand_mode 1 / 2) against an OPERAND-EXACT reference ------------------------------------------
+# A bf16 conversion is exactly specified: with both operands rounded to nearest even, every product is exact in fp32 and the only error left
+# is the fp32 accumulation.  The reference therefore rounds where the kernels round -- t = fp32(x*alpha + beta) (one rounding: the staging's
+# fmaf), ReLU, padding of t, bf16(t) and bf16(w) -- and sums in fp64.  A model that rounds anywhere else differs by ~2^-9 relative.
+REL_BF16 = 1e-5
+
+
+def bf16_round(t):
+    """round to nearest even to bf16, widened back to the input's dtype"""
+    return t.float().to(torch.bfloat16).to(t.dtype)
+
+
+def bf16_operand(x, al=None, be=None, relu=False):
+    """the operand the kernels stage, NCHW fp32, before padding: fp32(x*alpha + beta) rounded once from fp64, ReLU"""
+    t = x
+    if al is not None:
+        t = (x.double() * al.double()[:, :, None, None] + be.double()[:, :, None, None]).float()
+    if relu:
+        t = F.relu(t)
+    return t
+
+
+def bf16_conv_ref(x, w, b, al, be, relu, stride, pad, reflect):
+    """operand-exact reference of a bf16-operand convolution (fp64 NCHW): transform, ReLU, pad t, round t and w to bf16, fp64 conv + bias"""
+    t = bf16_operand(x, al, be, relu)
+    if pad:
+        t = F.pad(t, (pad,) * 4, mode="reflect" if reflect else "constant")
+    b64 = None if b is None else b.double()
+    return F.conv2d(bf16_round(t).double(), bf16_round(w).double(), b64, stride=stride)
+
+
+def w1_bf16_model(x, w, b, al, be, relu, reflect):
+    """conv_w1 (the Winograd F(2,3)-along-x form, 3 x 3 / stride 1 / pad 1) with bf16 operands, as its header specifies it: d = the padded
+    fp32 t; V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3 formed in fp32 and rounded to bf16; U = the filter transform in fp64,
+    rounded once to fp32, then to bf16; M_p = fp64 sums over (c, ky); out[2j] = M0 + M1 + M2, out[2j+1] = M1 - M2 - M3 (+ bias).  fp64 NCHW."""
+    d = F.pad(bf16_operand(x, al, be, relu), (1,) * 4, mode="reflect" if reflect else "constant")      # (N, C, H+2, W+2) fp32
+    d0, d1, d2, d3 = (d[..., i:i + d.shape[-1] - 3:2] for i in range(4))                               # d[2j-1+i] in unpadded columns
+    V = [bf16_round(v).double() for v in (d0 - d2, d1 + d2, d2 - d1, d1 - d3)]                          # (N, C, H+2, W/2)
+    g = w.double()
+    U = [g[..., 0], 0.5 * (g[..., 0] + g[..., 1] + g[..., 2]), 0.5 * (g[..., 0] - g[..., 1] + g[..., 2]), g[..., 2]]
+    M = [F.conv2d(v, bf16_round(u.float()).double().unsqueeze(-1)) for v, u in zip(V, U)]               # (N, O, H, W/2)
+    out = torch.stack((M[0] + M[1] + M[2], M[1] - M[2] - M[3]), dim=-1).flatten(-2)
+    return out if b is None else out + b.double()[None, :, None, None]
+
+
+def run_conv_op(lib, dev, x, w, b, al, be, relu, k, stride, pad, reflect, bound, nprod, kernel, tile):
+    """tsnet_op_conv2d on NCHW CPU tensors; returns the NCHW fp32 output on the CPU"""
+    N, Cin, H, W = x.shape
+    Cout = w.shape[0]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    xd, wd = nhwc(x).to(dev), w.contiguous().to(dev)
+    bd = None if b is None else b.to(dev)
+    ald = None if al is None else al.contiguous().to(dev)
+    bed = None if be is None else be.contiguous().to(dev)
+    y = torch.full((N, Ho, Wo, Cout), float("nan"), device=dev)
+    rc = lib.tsnet_op_conv2d(xd.data_ptr(), N, H, W, Cin, wd.data_ptr(), _p(bd), Cout, k, stride, pad, int(reflect),
+                             _p(ald), _p(bed), int(relu), bound, nprod, kernel, tile, y.data_ptr(), None)
+    assert rc == 0, lib.tsnet_op_last_error().decode()
+    _sync(dev)
+    return nchw(y.cpu())
+
+
+def _rel(y, ref):
+    return ((y.double() - ref).abs().max() / ref.abs().max()).item()
+
+
+def conv_bf16_case(lib, dev, N, H, W, Cin, Cout, k, stride, pad, reflect, norm=False, relu=None, bias=True, seed=0, kernel=0, tile=0,
+                   scale=1.0, ref="bf16"):
+    """tsnet_op_conv2d with bf16 operands (nprod = 1) against the operand-exact reference (ref = "bf16", every direct kernel) or the
+    Winograd-domain model (ref = "w1", kernel = 3).  Inputs as conv_case's; with `norm` the per-image alpha / beta differ per image.
+    Returns max|d| relative to max|reference|."""
+    x = _rand(seed, "x", (N, Cin, H, W)) * scale
+    w = _rand(seed, "w", (Cout, Cin, k, k)) * (2.0 / (Cin * k * k) ** 0.5)
+    b = _rand(seed, "b", (Cout,)) if bias else None
+    relu = norm if relu is None else relu
+    al = _rand(seed, "al", (N, Cin), 0.5, 1.5) if norm else None
+    be = _rand(seed, "be", (N, Cin), -0.3, 0.3) if norm else None
+    if ref == "w1":
+        r = w1_bf16_model(x, w, b, al, be, relu, reflect)
+    else:
+        r = bf16_conv_ref(x, w, b, al, be, relu, stride, pad, reflect)
+    y = run_conv_op(lib, dev, x, w, b, al, be, relu, k, stride, pad, reflect, 1.0, 1, kernel, tile)
+    return _rel(y, r)
+
+
+def run_cat_op(lib, dev, x, x2, w, b, k, nprod, bound=1.0):
+    """tsnet_op_conv2d_cat on NCHW CPU tensors (x2: x2_nmod images); returns the NCHW fp32 output on the CPU"""
+    N, C1, H, W = x.shape
+    C2, Cout = x2.shape[1], w.shape[0]
+    y = torch.full((N, H, W, Cout), float("nan"), device=dev)
+    xd, x2d, wd = nhwc(x).to(dev), nhwc(x2).to(dev), w.contiguous().to(dev)
+    bd = None if b is None else b.to(dev)
+    rc = lib.tsnet_op_conv2d_cat(xd.data_ptr(), x2d.data_ptr(), N, H, W, C1, C2, x2.shape[0], wd.data_ptr(), _p(bd), Cout, k, 1, k // 2, 0,
+                                 bound, nprod, y.data_ptr(), None)
+    assert rc == 0, lib.tsnet_op_last_error().decode()
+    _sync(dev)
+    return nchw(y.cpu())
+
+
+def bf16_tie_values(seed, name, shape, emin=-100, emax=100):
+    """fp32 values where a bf16 conversion is decided: exact ties (low 16 bits 0x8000) with an even and with an odd kept LSB, their
+    neighbours one fp32 ulp either side (0x7fff, 0x8001), 0xffff (the carry into the exponent) and random low bits, both signs, binades
+    2^emin .. 2^emax (normal fp32, far from bf16's overflow)"""
+    n = 1
+    for s in shape:
+        n *= s
+    u = lambda tag: prng.uniform01(seed, name + tag, (n,)).double()
+    exp = (u("_e") * (emax - emin + 1)).floor().long().clamp(max=emax - emin) + emin + 127
+    hi7 = (u("_m") * 128).floor().long().clamp(max=127)                          # the 7 kept mantissa bits: their LSB is the tie's parity
+    low = torch.tensor([0x8000, 0x8000, 0x7FFF, 0x8001, 0xFFFF, 0x0000, 0x8000, 0x7FFF])[(u("_k") * 8).floor().long().clamp(max=7)]
+    rnd = (u("_r") * 65536).floor().long().clamp(max=65535)
+    low = torch.where(u("_x") < 0.125, rnd, low)
+    sgn = (u("_s") < 0.5).long() << 31
+    bits = sgn | (exp << 23) | (hi7 << 16) | low
+    bits = torch.where(bits >= 2 ** 31, bits - 2 ** 32, bits).to(torch.int32)
+    return bits.view(torch.float32).view(shape).clone()
+
+
+def _delta_weights(Cout, Cin, k):
+    """channel c -> output c through the centre tap (1.0), all other taps zero: each output is one staged operand, in any summation order"""
+    w = torch.zeros(Cout, Cin, k, k)
+    for c in range(min(Cin, Cout)):
+        w[c, c, k // 2, k // 2] = 1.0
+    return w
+
+
+def conv_bf16_delta_case(lib, dev, N, H, W, Cin, Cout, k, stride, pad, reflect, transform="pow2", relu=False, seed=0, kernel=0, tile=0):
+    """BIT-EXACT activation rounding: a delta filter (centre tap 1.0 from channel c to output c; 1 x 1: the identity) on inputs full of bf16
+    ties, no bias.  Every output is bf16(t) of one pixel, so the kernel must return the reference's bits -- a ties-away, truncating or
+    misplaced rounding cannot hide in the accumulation.  transform: None (t = x), "pow2" (alpha = 2^j per (image, channel), beta = 0: the
+    tie survives the fmaf), "rand" (random alpha / beta: the rounding point of the fmaf).  Returns (y, reference) as fp32 NCHW."""
+    emin, emax = (-100, 100) if transform != "rand" else (-4, 4)
+    x = bf16_tie_values(seed, "xt", (N, Cin, H, W), emin, emax)
+    al = be = None
+    if transform == "pow2":
+        al = torch.exp2((prng.uniform01(seed, "alj", (N, Cin)) * 7).floor() - 3)
+        be = torch.zeros(N, Cin)
+    elif transform == "rand":
+        al = _rand(seed, "al", (N, Cin), 0.5, 1.5)
+        be = _rand(seed, "be", (N, Cin), -0.3, 0.3)
+    w = _delta_weights(Cout, Cin, k)
+    ref = bf16_conv_ref(x, w, None, al, be, relu, stride, pad, reflect).float()
+    y = run_conv_op(lib, dev, x, w, None, al, be, relu, k, stride, pad, reflect, 1.0, 1, kernel, tile)
+    return y, ref
+
+
+def conv_cat_bf16_delta_case(lib, dev, N, H, W, C1, C2, shared=False, seed=0):
+    """the concat formed on load, bit-exact: the identity over C1 + C2 channels on inputs full of ties.  Returns (y, reference)."""
+    x = bf16_tie_values(seed, "xt", (N, C1, H, W))
+    x2 = bf16_tie_values(seed, "x2t", (1 if shared else N, C2, H, W))
+    C = C1 + C2
+    w = _delta_weights(C, C, 1)
+    ref = bf16_round(torch.cat([x, x2.expand(N, -1, -1, -1)], dim=1))
+    return run_cat_op(lib, dev, x, x2, w, None, 1, 1), ref
+
+
+def conv_bf16_weight_case(lib, dev, Cin, Cout, k, stride, pad, reflect, seed=0, kernel=0, tile=0):
+    """BIT-EXACT weight rounding: one-hot inputs -- one 1.0 per input channel, at interior pixels spaced wider than the kernel (and at least
+    pad + 1 from every border, so that no reflection duplicates them) -- no transform, no bias, weights full of bf16 ties.  Every output is
+    one bf16-rounded weight or zero.  The frame (whole 4 x 32 output tiles) grows until Cin pixels fit.  Returns (y, reference), fp32 NCHW."""
+    sp = k + stride                                                   # no output window sees two one-hot pixels
+    H, W = 16 * stride, 32 * stride
+    while True:
+        pos = [(r, c) for r in range(pad + 1, H - pad - 1, sp) for c in range(pad + 1, W - pad - 1, sp)]
+        if len(pos) >= Cin:
+            break
+        H, W = (2 * H, W) if H < W else (H, 2 * W)
+    x = torch.zeros(1, Cin, H, W)
+    perm = torch.argsort(prng.uniform01(seed, "perm", (len(pos),)))
+    for c in range(Cin):
+        r, q = pos[int(perm[c])]
+        x[0, c, r, q] = 1.0
+    w = bf16_tie_values(seed, "wt", (Cout, Cin, k, k), -12, 2)
+    ref = bf16_conv_ref(x, w, None, None, None, False, stride, pad, reflect).float()
+    y = run_conv_op(lib, dev, x, w, None, None, None, False, k, stride, pad, reflect, 1.0, 1, kernel, tile)
+    return y, ref
+
+
+def conv_bf16_bound_case(lib, dev, N, H, W, Cin, Cout, k, stride, pad, reflect, norm=True, seed=0, kernel=0, tile=0):
+    """`bound` fixes the fp16 x 2 split's operand scale and nothing else: with bf16 operands the same call with bound 1e-30 and 1e30 must
+    give the same bits.  Returns the two outputs."""
+    x = _rand(seed, "x", (N, Cin, H, W))
+    w = _rand(seed, "w", (Cout, Cin, k, k)) * (2.0 / (Cin * k * k) ** 0.5)
+    b = _rand(seed, "b", (Cout,))
+    al = _rand(seed, "al", (N, Cin), 0.5, 1.5) if norm else None
+    be = _rand(seed, "be", (N, Cin), -0.3, 0.3) if norm else None
+    return [run_conv_op(lib, dev, x, w, b, al, be, norm, k, stride, pad, reflect, bound, 1, kernel, tile) for bound in (1e-30, 1e30)]
+
+
+# Every family and tile code tsnet_op_conv2d accepts with bf16 operands.  A case: (N, H, W, Cin, Cout, k, stride, pad, reflect, kernel, tile,
+# options).  The deep stride-2 schedule (12128) and conv_w1's chunks of 2 / 3 tiles are fp16 x 2 only (the planner refuses them).
+BF16_CASES = {
+    "H2": [(2, 8, 32, 48, 128, 3, 1, 1, True, 2, t, dict(norm=True)) for t in (0, 32, 64, 128, 2128, 3128)] + [
+        (1, 4, 32, 80, 96, 3, 1, 1, False, 2, 64, dict(norm=True, relu=False)),        # zero padding, a transform without ReLU, Cout 96
+        (1, 4, 64, 64, 128, 3, 1, 1, True, 2, 20032, dict(norm=True)),                 # the two-K-group tiles
+        (2, 4, 32, 64, 128, 3, 1, 1, False, 2, 20064, dict(norm=True, seed=1)),
+        (1, 4, 32, 16, 64, 3, 1, 1, True, 2, 64, dict(bias=False, scale=2.0 ** 40)),   # any fp16 intermediate / operand scale would show
+        (1, 4, 32, 16, 128, 3, 1, 1, True, 2, 128, dict(bias=False, scale=2.0 ** -40, seed=2))],
+    "H2D": [(2, 8, 64, 16, 128, 3, 2, 1, False, 2, t, dict(norm=True)) for t in (0, 64, 128, 2128)] + [
+        (1, 8, 64, 48, 96, 3, 2, 1, False, 2, 64, dict(norm=True, relu=False, seed=3)),
+        (1, 8, 64, 80, 128, 3, 2, 1, False, 2, 2128, dict(bias=False, scale=2.0 ** 40))],
+    "H2S": [(2, 4, 32, 8, 64, 7, 1, 3, True, 2, 0, dict()), (1, 8, 64, 8, 64, 7, 1, 3, True, 2, 0, dict(bias=False, scale=2.0 ** -40, seed=4))],
+    "H2S32": [(1, 4, 32, 32, 72, 7, 1, 3, True, 0, 0, dict()), (2, 8, 32, 32, 64, 7, 1, 3, True, 0, 0, dict(bias=False, scale=2.0 ** 40, seed=5))],
+    "G64": [(2, 8, 8, 128, 192, 1, 1, 0, False, 1, t, dict()) for t in (3064, 3128)] + [
+        (1, 16, 16, 64, 192, 3, 2, 1, False, 1, t, dict(norm=True)) for t in (3064, 3128)] + [
+        (2, 10, 12, 64, 256, 3, 1, 1, True, 1, 3064, dict(norm=True, relu=False, seed=6)),
+        (1, 9, 7, 192, 128, 3, 2, 1, False, 1, 3128, dict(bias=False, scale=2.0 ** -40, seed=7))],
+    "H2R": [(2, 12, 10, c, 24, k, s, p, r, 1, 64, dict(norm=n, seed=c)) for (k, s, p, r) in ((7, 1, 3, True), (3, 2, 1, False), (3, 1, 1, True))
+            for (c, n) in ((8, False), (48, True))] + [
+        (2, 12, 10, 16, 130, 3, 1, 1, True, 1, 128, dict(norm=True, relu=False)), (2, 5, 7, 16, 24, 1, 1, 0, False, 1, 64, dict()),
+        (1, 13, 11, 80, 128, 3, 2, 1, False, 1, 128, dict(bias=False, scale=2.0 ** 40, seed=8))],
+}
+
+
+def bf16_family_worst(lib, dev, family):
+    """the worst error relative to max|operand-exact reference| over BF16_CASES[family]"""
+    worst = 0.0
+    for (N, H, W, Ci, Co, k, s, p, r, kern, tile, kw) in BF16_CASES[family]:
+        worst = max(worst, conv_bf16_case(lib, dev, N, H, W, Ci, Co, k, s, p, r, kernel=kern, tile=tile, **kw))
+    return worst
+
+
+def bf16_w1_worst(lib, dev, big=False):
+    """conv_w1 with bf16 operands against the Winograd-domain model (w1_bf16_model): reflection and zero padding, the fused transform with
+    and without ReLU, odd slab counts, N > 1 with per-image alpha / beta, inputs scaled by 2^+-40 without bias"""
+    cases = [(2, 8, 32, 48, 96, True, dict(norm=True)), (1, 4, 32, 80, 64, False, dict(norm=True, relu=False, seed=1)),
+             (1, 8, 32, 16, 128, True, dict(seed=2)), (1, 4, 32, 32, 64, True, dict(bias=False, scale=2.0 ** 40, seed=3)),
+             (1, 4, 64, 32, 64, False, dict(bias=False, scale=2.0 ** -40, seed=4))]
+    if big:     # the ResnetBlock / FuseNet / first up-convolution shapes
+        cases += [(2, 32, 32, 512, 512, True, dict(norm=True)), (1, 32, 32, 1024, 1024, True, dict(norm=True, seed=5)),
+                  (1, 64, 64, 512, 256, False, dict(norm=True, relu=False, seed=6))]
+    worst = 0.0
+    for (N, H, W, Ci, Co, refl, kw) in cases:
+        worst = max(worst, conv_bf16_case(lib, dev, N, H, W, Ci, Co, 3, 1, 1, refl, kernel=3, ref="w1", **kw))
+    return worst
+
+
+# bit-exact cases per family: (N, H, W, Cin, Cout, k, stride, pad, reflect, kernel, tile); the stems take no transform
+BF16_EXACT_CASES = {
+    "H2": [(2, 8, 32, 48, 128, 3, 1, 1, True, 2, t) for t in (32, 64, 2128)] + [(1, 4, 32, 64, 128, 3, 1, 1, False, 2, t) for t in (128, 3128, 20032)],
+    "H2D": [(2, 8, 64, 48, 128, 3, 2, 1, False, 2, t) for t in (64, 128, 2128)],
+    "H2S": [(2, 8, 32, 8, 64, 7, 1, 3, True, 2, 0)],
+    "H2S32": [(1, 8, 32, 32, 64, 7, 1, 3, True, 0, 0)],
+    "G64": [(2, 8, 8, 64, 128, 1, 1, 0, False, 1, 3064), (1, 16, 16, 64, 128, 3, 2, 1, False, 1, 3128)],
+    "H2R": [(2, 12, 10, 16, 24, 3, 1, 1, True, 1, 64), (2, 12, 10, 8, 24, 7, 1, 3, True, 1, 64), (1, 13, 11, 16, 130, 3, 2, 1, False, 1, 128),
+            (2, 5, 7, 16, 24, 1, 1, 0, False, 1, 64)],
+}
+
+
+def bf16_exact_mismatches(lib, dev, family):
+    """BF16_EXACT_CASES[family] through the delta filter on ties (no transform; alpha = 2^j with and without ReLU; one random alpha / beta),
+    the one-hot input on tied weights and the two extreme bounds.  Returns the list of cases whose bits differ (empty: all exact)."""
+    bad = []
+    for i, (N, H, W, Ci, Co, k, s, p, r, kern, tile) in enumerate(BF16_EXACT_CASES[family]):
+        stem = k == 7
+        for tr, relu in ((None, False),) + (() if stem else (("pow2", False), ("pow2", True), ("rand", True))):
+            y, ref = conv_bf16_delta_case(lib, dev, N, H, W, Ci, Co, k, s, p, r, transform=tr, relu=relu, seed=i, kernel=kern, tile=tile)
+            if not torch.equal(y, ref):
+                bad.append(("delta", tr, relu, (N, H, W, Ci, Co, k, s, tile), int((y != ref).sum())))
+        y, ref = conv_bf16_weight_case(lib, dev, Ci, Co, k, s, p, r, seed=i, kernel=kern, tile=tile)
+        if not torch.equal(y, ref):
+            bad.append(("weights", (Ci, Co, k, s, tile), int((y != ref).sum())))
+        a, b = conv_bf16_bound_case(lib, dev, N, H, W, Ci, Co, k, s, p, r, norm=not stem, seed=i, kernel=kern, tile=tile)
+        if not torch.equal(a, b):
+            bad.append(("bound", (N, H, W, Ci, Co, k, s, tile)))
+    return bad
+
+
+def bf16_forward_layers(table):
+    """the distinct bf16-operand convolutions of the forward (nprod == 1 in tests/golden/conv_plan_table.json's layers), one per (shape,
+    family, tile) -> (config, layer, shape dict, kernel, tile code)"""
+    out, seen = [], set()
+    for c in table["layers"]:
+        s, p = c["shape"], c["plan"]
+        if s["nprod"] != 1:
+            continue
+        key = tuple(s[k] for k in ("ks", "stride", "pad", "reflect", "cin", "cout", "form", "H", "W", "csplit", "transform")) + \
+            tuple(p[k] for k in ("family", "rows", "width", "side_by_side", "sched"))
+        if key in seen:
+            continue
+        seen.add(key)
+        fam = p["family"]
+        if fam == "H2":
+            assert p["sched"] == "plain"
+            kernel, tile = 2, (3128 if p["side_by_side"] else (2128 if p["rows"] == 2 else p["width"]))
+        elif fam == "G64":
+            kernel, tile = 1, 3000 + p["rows"]
+        elif fam == "H2R":
+            kernel, tile = 1, p["width"]
+        elif fam in ("H2S", "H2S32"):
+            kernel, tile = 2 if fam == "H2S" else 0, 0
+        else:
+            raise AssertionError(f"no tile code for a bf16 layer on {fam}")
+        out.append((c["config"], c["layer"], s, kernel, tile))
+    return out
+
+
+def bf16_forward_layer_case(lib, dev, s, kernel, tile, seed=0):
+    """one bf16 layer of the forward with its own tile forced, at N <= 2 (a tile's bits do not depend on the batch: tests/test_conv_plan.py),
+    the producer's InstanceNorm + ReLU fused where the forward fuses it; error relative to max|operand-exact reference|"""
+    N = 2 if s["H"] * s["W"] <= 64 * 64 else 1
+    if s["csplit"]:         # dec.map_conv on cat(pg, sg): its own launch path, no tile request
+        return conv_cat_case(lib, dev, N, s["H"], s["W"], s["csplit"], s["cin"] - s["csplit"], s["cout"], k=s["ks"], seed=seed, nprod=1, ref="bf16")
+    return conv_bf16_case(lib, dev, N, s["H"], s["W"], s["cin"], s["cout"], s["ks"], s["stride"], s["pad"], bool(s["reflect"]),
+                          norm=bool(s["transform"]), seed=seed, kernel=kernel, tile=tile)

@@ -1,6 +1,8 @@
 """CPU tier: every HIP kernel of the hot path executed under the fiber emulator (tests/emu) through
 the C ABI and compared with PyTorch CPU ops.  This checks indexing / padding / MFMA fragment layout /
 reduction logic; numerics on real hardware are the GPU tier's job."""
+import os
+
 import pytest
 import torch
 
@@ -144,6 +146,60 @@ def test_bf16_wide_tile_side_by_side_waves(emu_lib):
         assert oc.conv_h2_case(emu_lib, "cpu", N, H, W, Ci, Co, refl, norm=norm, nprod=1, tile_n=3128) < 2e-2
     with pytest.raises(AssertionError, match="bf16 4 x 128"):
         oc.conv_h2_case(emu_lib, "cpu", 1, 4, 32, 32, 128, True, nprod=3, tile_n=3128)
+
+
+# ---- bf16 operands against the OPERAND-EXACT reference (op_cases.bf16_conv_ref): t = fp32(x*alpha + beta), ReLU, padding of t, bf16(t) and
+# bf16(w) by round-to-nearest-even, fp64 sums.  Every product is then exact in fp32; the only error left is the fp32 accumulation (measured
+# 1.1 - 3.4e-7 per family here), while rounding at another point or in another mode costs 1.4 - 3.8e-3.  The 2e-2 checks against fp64 above stay.
+REL_BF16 = oc.REL_BF16
+
+
+@pytest.mark.parametrize("family", list(oc.BF16_CASES))
+def test_bf16_operand_exact_reference(emu_lib, family):
+    """every family and tile code tsnet_op_conv2d takes with nprod = 1 (op_cases.BF16_CASES): ragged frames, odd slab counts, N > 1 with
+    per-image alpha / beta, Cout off the 64 grid, zero and reflection padding, a transform without ReLU, inputs scaled by 2^+-40 without bias"""
+    worst = oc.bf16_family_worst(emu_lib, "cpu", family)
+    print(f"bf16 {family}: worst {worst:.2e} of max|ref|")
+    assert worst < REL_BF16
+
+
+def test_bf16_winograd_form_against_its_domain_model(emu_lib):
+    """conv_w1 with bf16 operands rounds V = B^T d, not x: against the Winograd-domain model (op_cases.w1_bf16_model) it is fp32-class"""
+    worst = oc.bf16_w1_worst(emu_lib, "cpu")
+    print(f"bf16 W1: worst {worst:.2e} of max|model|")
+    assert worst < REL_BF16
+    assert oc.conv_bf16_case(emu_lib, "cpu", 1, 4, 32, 32, 64, 3, 1, 1, True, norm=True, kernel=3, ref="bf16") > 100 * REL_BF16   # not the x-rounded one
+
+
+def test_bf16_conv_cat(emu_lib):
+    """the concat formed on load with nprod = 1 (the bf16 forward's dec.map_conv), with and without a shared second tensor, 1 x 1 on conv_g64
+    and 3 x 3 on conv_h2r; the identity over C1 + C2 channels on ties gives bf16(x) bit for bit"""
+    worst = max(oc.conv_cat_case(emu_lib, "cpu", 2, 8, 8, 64, 64, 128, nprod=1, ref="bf16"),
+                oc.conv_cat_case(emu_lib, "cpu", 2, 8, 8, 128, 64, 256, shared=True, nprod=1, ref="bf16"),
+                oc.conv_cat_case(emu_lib, "cpu", 3, 5, 6, 16, 48, 24, k=3, shared=True, nprod=1, ref="bf16"))
+    print(f"bf16 concat: worst {worst:.2e} of max|ref|")
+    assert worst < REL_BF16
+    for shared in (False, True):
+        y, ref = oc.conv_cat_bf16_delta_case(emu_lib, "cpu", 2, 4, 8, 64, 64, shared=shared)
+        assert torch.equal(y, ref), shared
+
+
+@pytest.mark.parametrize("family", list(oc.BF16_EXACT_CASES))
+def test_bf16_rounding_bit_exact(emu_lib, family):
+    """bf16 rounding checked bit for bit (op_cases.bf16_exact_mismatches): a delta filter on inputs full of exact ties (even and odd kept LSB),
+    their one-ulp neighbours and 2^-100 .. 2^100 magnitudes, through no transform, alpha = 2^j (with and without ReLU) and a random
+    alpha / beta; one-hot inputs on tied weights; bound 1e-30 and 1e30 giving the same bits"""
+    assert oc.bf16_exact_mismatches(emu_lib, "cpu", family) == []
+
+
+def test_bf16_forward_layer_list():
+    """the GPU tier runs every distinct bf16 layer of the forward with its own tile (test_gpu_ops.py::test_bf16_forward_layers): 31 of them
+    across cfg2 / cfg4, each with a tile code"""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan_table.json")) as f:
+        layers = oc.bf16_forward_layers(json.load(f))
+    assert len(layers) == 31 and {c for c, *_ in layers} == {"cfg2", "cfg4"}
+    assert sum(1 for l in layers if l[2]["cin"] == 1024 and l[2]["ks"] == 3) == 2        # the K = 9216 ResnetBlock layers
 
 
 @pytest.mark.parametrize("C,H,W", [(8, 6, 5), (64, 16, 16), (24, 9, 3), (1024, 2, 2)])

@@ -223,6 +223,66 @@ def test_bf16_wide_tile_side_by_side_waves(lib):
         assert oc.conv_h2_case(lib, DEV, N, H, W, Ci, Co, refl, norm=True, nprod=1, tile_n=3128) < 2e-2
 
 
+# ---- bf16 operands against the OPERAND-EXACT reference (op_cases.bf16_conv_ref): the operands rounded where the kernels round them, fp64
+# sums -- what is left is the fp32 accumulation.  A rounding at another point or in another mode costs 1.4 - 3.8e-3 relative.  Measured on
+# an MI355X: <= 1.2e-6 on the forward's 512- and 1024-channel 3 x 3 layers, <= 6.9e-7 everywhere else; ties round as bf16_rne does.
+REL_BF16 = oc.REL_BF16
+
+
+@pytest.mark.parametrize("family", list(oc.BF16_CASES))
+def test_bf16_operand_exact_reference(lib, family):
+    """every family and tile code tsnet_op_conv2d takes with nprod = 1, the edges of op_cases.BF16_CASES"""
+    worst = oc.bf16_family_worst(lib, DEV, family)
+    print(f"bf16 {family}: worst {worst:.2e} of max|ref|")
+    assert worst < REL_BF16
+
+
+def test_bf16_winograd_form_against_its_domain_model(lib):
+    """conv_w1 with bf16 operands against the Winograd-domain model, also at the ResnetBlock / FuseNet / first up-convolution shapes"""
+    worst = oc.bf16_w1_worst(lib, DEV, big=True)
+    print(f"bf16 W1: worst {worst:.2e} of max|model|")
+    assert worst < REL_BF16
+
+
+def test_bf16_conv_cat(lib):
+    """dec.map_conv as the bf16 forward runs it (nprod = 1: conv_g64, the concat split at 512), a shared second tensor, the 3 x 3 concat on
+    conv_h2r; the identity over C1 + C2 channels on ties, bit for bit"""
+    worst = max(oc.conv_cat_case(lib, DEV, 2, 32, 32, 512, 512, 512, nprod=1, ref="bf16"),
+                oc.conv_cat_case(lib, DEV, 2, 8, 8, 128, 64, 256, shared=True, nprod=1, ref="bf16"),
+                oc.conv_cat_case(lib, DEV, 3, 5, 6, 16, 48, 24, k=3, shared=True, nprod=1, ref="bf16"))
+    print(f"bf16 concat: worst {worst:.2e} of max|ref|")
+    assert worst < REL_BF16
+    for shared in (False, True):
+        y, ref = oc.conv_cat_bf16_delta_case(lib, DEV, 2, 8, 8, 512, 512, shared=shared)
+        assert torch.equal(y, ref), shared
+
+
+@pytest.mark.parametrize("family", list(oc.BF16_EXACT_CASES))
+def test_bf16_rounding_bit_exact(lib, family):
+    """v_cvt_pk_bf16_f32 against round-to-nearest-even on exact ties, their one-ulp neighbours and 2^-100 .. 2^100 (delta filters), the
+    packed weights on tied values (one-hot inputs), and bound 1e-30 / 1e30 giving the same bits"""
+    assert oc.bf16_exact_mismatches(lib, DEV, family) == []
+
+
+def test_bf16_forward_layers(lib):
+    """every distinct bf16 layer of the forward (nprod = 1 in tests/golden/conv_plan_table.json: 31 across cfg2 / cfg4) with its own tile
+    forced, at N <= 2, against the operand-exact reference -- the 1024 -> 1024 ResnetBlock layers run the longest fp32 chain (K = 9216)"""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan_table.json")) as f:
+        layers = oc.bf16_forward_layers(json.load(f))
+    assert len(layers) == 31
+    worst, bad = {}, []
+    for (cfg, idx, s, kernel, tile) in layers:
+        e = oc.bf16_forward_layer_case(lib, DEV, s, kernel, tile, seed=idx)
+        fam = "cat" if s["csplit"] else f"{kernel}/{tile}"
+        worst[fam] = max(worst.get(fam, 0.0), e)
+        if not e < REL_BF16:
+            bad.append((cfg, idx, kernel, tile, e))
+    print("bf16 forward layers, worst per kernel / tile: " + ", ".join(f"{k} {v:.2e}" for k, v in sorted(worst.items())))
+    assert not bad, bad
+
+
 def test_conv_split_worst_case_dynamic_range(lib):
     """The fp16 x 2 split under an adversarial dynamic range inside ONE image at the ResnetBlock shape (512 -> 512, 32 x 32): 1 % of the
     activations at amax, the bulk at amax * 2^-12 / 2^-18 / 2^-24, weights likewise.  Absolute error within 3 x the exact-fp32 chain's
