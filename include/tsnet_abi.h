@@ -291,6 +291,25 @@ void tsnet_debug_counters(int64_t out[4], int reset);
 void tsnet_linspace(int n, float* out);
 void tsnet_coord_table(int H, int W, float* out);
 
+/* Frame loading: the image side of the reference's loaders (dataset/dataset_video_face.py:318-329, 391-401: self.crop, Image.resize to 256 x 256,
+ * RGB -> BGR, - mean; dataset/dataset_video_pose.py:346, 412-417, 450-457: crop, Image.resize to 128 x 256, resize_square, RGB -> BGR, - mean).
+ * Image.resize's default filter is bicubic; Pillow's 8-bit resampler is integer arithmetic on coefficient tables, reproduced here byte for byte.
+ * tsnet_bicubic_taps    -> the row stride of an axis' coefficient table, 2 * ceil(2 * max(n_in / n_out, 1)) + 1; negative on bad sizes.
+ * tsnet_bicubic_table   <- libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc for one axis, HOST code: first[n_out], count[n_out] (the
+ *                          window of every output index inside the n_in input pixels) and coef[n_out * taps] (22 fractional bits, unused taps 0).
+ * tsnet_prepare_frames  <- frame.crop((x0, y0, x1, y1)).resize((ow, oh)), centred in an OH x OW canvas at (pad_top, pad_left) whose other pixels are
+ *                          byte 0, channels reversed, minus mean_bgr.  frames: (F,h,w,3) device bytes, RGB interleaved; the box may leave the frame
+ *                          (Image.crop: those pixels read 0).  The x tables are those of (x1 - x0 -> ow), the y tables of (y1 - y0 -> oh): DEVICE
+ *                          ints; an axis that keeps its size is skipped and its tables are not read (may be NULL).  mean_bgr: 3 HOST floats.
+ *                          out: (F,3,OH,OW) device floats, planes B, G, R.  One kernel on `stream`: no allocation, no synchronisation.
+ *                          TSNET_ERR_ARG (nothing written): empty box, taps that are not those of the size ratio, padding that does not fit. */
+int tsnet_bicubic_taps(int n_in, int n_out);
+int tsnet_bicubic_table(int n_in, int n_out, int* first, int* count, int* coef);
+int tsnet_prepare_frames(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
+                         const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                         const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                         int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

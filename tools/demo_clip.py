@@ -53,7 +53,8 @@ def main():
     ap.add_argument("--n-blocks", type=int, default=4)
     ap.add_argument("--timing-frames", type=int, default=200)
     ap.add_argument("--clip", default=None, help="key points of a real demo clip (demo/face_examples/labels/<clip>, stored with the raster golden "
-                    "tests/golden/g7_raster_face.npz: test114 or val024) instead of the synthetic face; the frames' pixels stay synthetic")
+                    "tests/golden/g7_raster_face.npz: test114 or val024) instead of the synthetic face; the source frames' pixels are the clip's own "
+                    "(tests/golden/g11_frames_<clip>.npz through the device frame loader)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -80,6 +81,7 @@ def main():
         kp = z[f"{args.clip}_keypoints"].copy()                   # stored relative to the clip's crop: back to frame coordinates
         kp[:, :, 0] += meta["crop"][2]
         kp[:, :, 1] += meta["crop"][0]
+        kp_all = kp
         F = min(F, kp.shape[0] - K)
         kp = kp[:F + K]
     else:
@@ -103,9 +105,23 @@ def main():
         td = time.perf_counter()
         t_steps = {"fit (host) + draw (device)": tb - ta, "resize 2 maps": tc - tb, "one-hot": td - tc}
     assert torch.equal(e2, edges) and torch.equal(b2, bbox)
-    g = torch.Generator().manual_seed(1)
-    src_img = [(torch.rand((1, 3, 256, 256), generator=g) * 255.0 - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1)) for _ in range(K)]
-    runner = demo.ClipRunner(model, src_img, [lbl[i:i + 1] for i in range(K)], [box[i:i + 1] for i in range(K)])
+    if args.clip:
+        # the real source frames: the cropped regions of the clip's demo images (tests/golden/g11_frames_<clip>.npz) through the device frame
+        # loader, and the labels of the SAME frame indices, so that pixels and labels belong together
+        from wacv23_tsnet_amd import frames as frames_mod
+        zf = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", f"g11_frames_{args.clip}.npz"))
+        fmeta = json.loads(str(zf["meta"]))
+        x0, y0, x1, y1 = fmeta["box"]
+        assert [y0, y1, x0, x1] == list(crop)
+        img = frames_mod.FrameLoader(dev).face(zf["crops"], [0, y1 - y0, 0, x1 - x0])
+        src_img = [img[i:i + 1] for i in range(K)]
+        se, sb, _, _ = rs.rasterise(list(kp_all[[int(i) for i in fmeta["frames"]][:K]]), crop)
+        src_lbl, src_box = rs.vl2ch(demo.resize_label(se), 2), demo.resize_label(sb)
+    else:
+        g = torch.Generator().manual_seed(1)
+        src_img = [(torch.rand((1, 3, 256, 256), generator=g) * 255.0 - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1)) for _ in range(K)]
+        src_lbl, src_box = lbl[:K], box[:K]
+    runner = demo.ClipRunner(model, src_img, [src_lbl[i:i + 1] for i in range(K)], [src_box[i:i + 1] for i in range(K)])
     frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_face")
     print(f"[demo_clip] {demo.RESIZE_NOTE}")
     print(f"[demo_clip] {frames.shape[0]} frames written to {args.out} (crop {crop}, brush {bw}); rasterisation of {F + K} frames: {t_raster * 1e3:.2f} ms on the first call; "

@@ -40,6 +40,7 @@
 #include "kernels.hpp"
 #include "lmfit.hpp"
 #include "flow_warp.hpp"
+#include "frames.hpp"
 #include "head_conv.hpp"
 #include "norm_elementwise.hpp"
 #include "pack_weights.hpp"
@@ -1748,5 +1749,45 @@ void tsnet_debug_counters(int64_t out[4], int reset) {
 
 void tsnet_linspace(int n, float* out) { linspace_pm1(n, out); }
 void tsnet_coord_table(int H, int W, float* out) { coord_table(H, W, out); }
+
+int tsnet_bicubic_taps(int n_in, int n_out) {
+    if (n_in < 1 || n_out < 1) { g_op_error = "bicubic_taps: sizes must be positive"; return TSNET_ERR_ARG; }
+    return bicubic_taps(n_in, n_out);
+}
+
+int tsnet_bicubic_table(int n_in, int n_out, int* first, int* count, int* coef) {
+    OP_BEGIN
+    if (n_in < 1 || n_out < 1 || !first || !count || !coef) throw ArgError("bicubic_table: bad argument");
+    bicubic_table(n_in, n_out, first, count, coef);
+    OP_END
+}
+
+int tsnet_prepare_frames(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
+                         const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                         const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                         int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream) {
+    OP_BEGIN
+    if (!frames || !out || !mean_bgr) throw ArgError("prepare_frames: null tensor");
+    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("prepare_frames: bad frame shape");
+    if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000) throw ArgError("prepare_frames: empty or absurd crop box");
+    if (oh < 1 || ow < 1 || pad_top < 0 || pad_left < 0 || pad_top + oh > OH || pad_left + ow > OW || (double)OH * OW >= 2147483647.0 / 4)
+        throw ArgError("prepare_frames: the resized image and its padding do not fit the output");
+    const int cw = x1 - x0, ch = y1 - y0;
+    if (ow != cw && (!xfirst || !xcount || !xcoef)) throw ArgError("prepare_frames: the horizontal pass needs its tables");
+    if (oh != ch && (!yfirst || !ycount || !ycoef)) throw ArgError("prepare_frames: the vertical pass needs its tables");
+    // a table row holds `taps` coefficients: fewer than the size ratio needs (count > taps) cannot be a table of tsnet_bicubic_table
+    if (ow != cw && xtaps != bicubic_taps(cw, ow)) throw ArgError("prepare_frames: xtaps is not tsnet_bicubic_taps(x1 - x0, ow)");
+    if (oh != ch && ytaps != bicubic_taps(ch, oh)) throw ArgError("prepare_frames: ytaps is not tsnet_bicubic_taps(y1 - y0, oh)");
+    int th = kFrTileH;
+    while (th > 1 && frames_row_span(ch, oh, th) > kFrRows) th >>= 1;
+    if (frames_row_span(ch, oh, th) > kFrRows) throw ArgError("prepare_frames: vertical reduction too steep (more than 112 taps)");
+    const int gy = (OH + th - 1) / th;
+    if (gy > 65535) throw ArgError("prepare_frames: output too tall");
+    FrameArgs a{frames, out, xfirst, xcount, xcoef, yfirst, ycount, ycoef, h, w, x0, y0, cw, ch, ow, oh, xtaps, ytaps, pad_top, pad_left, OH, OW, th,
+                {mean_bgr[0], mean_bgr[1], mean_bgr[2]}};
+    hipLaunchKernelGGL(prepare_frames_kernel, dim3((OW + kFrTileW - 1) / kFrTileW, gy, F), dim3(256), 0, (hipStream_t)stream, a);
+    check_launch("prepare_frames");
+    OP_END
+}
 
 }  // extern "C"

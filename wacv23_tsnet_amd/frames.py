@@ -1,0 +1,148 @@
+"""Frame loading on the device: decoded video frames -> the image tensors `set_test_input` / `set_sources` take.
+
+The reference does this per frame on the host in its data loaders (dataset/dataset_video_face.py:318-329, 391-401; dataset/dataset_video_pose.py:346,
+412-417, 450-457): PIL `crop` to the clip's crop box, `Image.resize` with Pillow's default filter (bicubic) to 256 x 256 (face) or 128 x 256 (pose),
+for pose `resize_square` to 256 x 256 with black bars, RGB -> BGR, `- IMG_MEAN`; the fp32 result (12 bytes per pixel) is then uploaded.  Here the
+uint8 frames go to the device once (3 bytes per pixel) and one kernel (csrc/frames.hpp, `tsnet_prepare_frames`) does the rest.  Pillow's 8-bit
+resampler is integer arithmetic on coefficient tables; the tables are built on the host in Pillow's operation order (`bicubic_table`, a few hundred
+doubles per axis), so the tensors EQUAL the reference's, byte for byte before the mean subtraction (tests/test_frames.py).
+
+Decoding PNG / JPEG files stays with PIL on the host; the training loaders' random crop / scale / flip are out of scope."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .demo import IMG_MEAN
+
+PRECISION_BITS = 22
+
+
+def bicubic_taps(n_in: int, n_out: int) -> int:
+    """Row stride of an axis' coefficient table (ksize of Pillow's precompute_coeffs)."""
+    return int(math.ceil(2.0 * max(n_in / n_out, 1.0))) * 2 + 1
+
+
+def _bicubic(x: float, a: float = -0.5) -> float:
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def bicubic_table(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Pillow's coefficient table of one axis of `Image.resize((.., ..))` (bicubic, 8 bits per channel): (first[n_out], count[n_out],
+    coef[n_out, taps]) int32 -- libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc restated in their operation order.  Output pixel o
+    is clip8((2^21 + sum_j in[first[o] + j] * coef[o, j]) >> 22).  `tsnet_bicubic_table` is the same table from C; the tests hold them equal."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support, ss = 2.0 * fs, 1.0 / fs
+    taps = int(math.ceil(support)) * 2 + 1
+    first, count, coef = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32), np.zeros((n_out, taps), np.int32)
+    for o in range(n_out):
+        center = (o + 0.5) * scale
+        lo, hi = max(int(center - support + 0.5), 0), min(int(center + support + 0.5), n_in)
+        w = [_bicubic((j + lo - center + 0.5) * ss) for j in range(hi - lo)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for j, v in enumerate(w):
+            v = v / ww if ww != 0.0 else v
+            coef[o, j] = int(v * (1 << PRECISION_BITS) - 0.5) if v < 0 else int(v * (1 << PRECISION_BITS) + 0.5)
+        first[o], count[o] = lo, hi - lo
+    return first, count, coef
+
+
+def bicubic_table_c(lib, n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The same table from the library's host entry `tsnet_bicubic_table`."""
+    taps = lib.tsnet_bicubic_taps(n_in, n_out)
+    if taps < 0:
+        raise RuntimeError(f"tsnet_bicubic_taps failed ({taps}): {lib.tsnet_op_last_error().decode()}")
+    first, count, coef = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32), np.zeros((n_out, taps), np.int32)
+    rc = lib.tsnet_bicubic_table(n_in, n_out, first.ctypes.data, count.ctypes.data, coef.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"tsnet_bicubic_table failed ({rc}): {lib.tsnet_op_last_error().decode()}")
+    return first, count, coef
+
+
+class FrameLoader:
+    """Network-input image tensors of a clip's frames on `device`.
+
+    lib: tests pass the CPU emulation build; product code leaves it None (the in-tree HIP library, no fallback).
+    The coefficient tables of an (input size, output size) pair are built and uploaded once and kept; after that `prepare` on frames that are
+    already on the device only enqueues one kernel on the current stream (no allocation inside the library, no synchronisation)."""
+
+    def __init__(self, device, lib=None):
+        self.lib = lib if lib is not None else _lib.load()
+        self.device = torch.device(device)
+        self._tables = {}
+        self._keep = []
+
+    def _stream(self) -> Optional[int]:
+        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
+
+    def _axis(self, n_in: int, n_out: int):
+        """(device int32 tensor [first | count | coef], taps) of one axis, cached"""
+        key = (n_in, n_out)
+        if key not in self._tables:
+            first, count, coef = bicubic_table_c(self.lib, n_in, n_out)
+            flat = torch.from_numpy(np.concatenate([first, count, coef.ravel()])).to(self.device)
+            self._tables[key] = (flat, coef.shape[1])
+        return self._tables[key]
+
+    def prepare(self, frames, box: Sequence[int], size: Tuple[int, int], square: bool = False, mean=IMG_MEAN) -> torch.Tensor:
+        """frames: (F,h,w,3) uint8 RGB, tensor or array (uploaded once when on the host).  box: (x0, y0, x1, y1) in PIL order; it may leave the
+        frame (Image.crop: zeros there).  size: (ow, oh) as Image.resize takes it.  square: resize_square's centred padding with byte 0 to
+        max(ow, oh).  Returns (F,3,H,W) float32 on the device: BGR planes of frame.crop(box).resize(size) minus `mean` (B, G, R)."""
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
+            raise ValueError(f"expected uint8 frames of shape (F,h,w,3), got {tuple(frames.shape)} {frames.dtype}")
+        fr = frames.to(self.device).contiguous()
+        F, h, w, _ = fr.shape
+        x0, y0, x1, y1 = (int(v) for v in box)
+        ow, oh = int(size[0]), int(size[1])
+        S = max(ow, oh)
+        OH, OW = (S, S) if square else (oh, ow)
+        pad_top, pad_left = (OH - oh) // 2, (OW - ow) // 2
+        if x1 <= x0 or y1 <= y0:
+            raise ValueError(f"empty crop box {tuple(box)}")
+        xt, xtaps = self._axis(x1 - x0, ow)
+        yt, ytaps = self._axis(y1 - y0, oh)
+        m = np.asarray(mean, dtype=np.float32)
+        mean_c = (C.c_float * 3)(float(m[0]), float(m[1]), float(m[2]))
+        out = torch.empty((F, 3, OH, OW), dtype=torch.float32, device=self.device)
+        p = lambda t, off: t.data_ptr() + 4 * off
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        with ctx:
+            rc = self.lib.tsnet_prepare_frames(fr.data_ptr(), F, h, w, x0, y0, x1, y1,
+                                               p(xt, 0), p(xt, ow), p(xt, 2 * ow), xtaps, p(yt, 0), p(yt, oh), p(yt, 2 * oh), ytaps,
+                                               oh, ow, pad_top, pad_left, OH, OW, mean_c, out.data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tsnet_prepare_frames failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep = [fr]                                            # alive until the stream has consumed it
+        return out
+
+    def face(self, frames, crop: Sequence[int], size: Tuple[int, int] = (256, 256), mean=IMG_MEAN) -> torch.Tensor:
+        """The face loader's image: crop = [min_y, max_y, min_x, max_x] as raster.crop_coords returns it (get_crop_coords, not clipped to the frame)."""
+        min_y, max_y, min_x, max_x = crop
+        return self.prepare(frames, (min_x, min_y, max_x, max_y), size, square=False, mean=mean)
+
+    def pose(self, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mean=IMG_MEAN) -> torch.Tensor:
+        """The pose loader's image: crop = (xs, ys, xe, ye) as raster.pose_crop_coords returns it; 128 x 256, then padded to 256 x 256."""
+        return self.prepare(frames, crop, img_size, square=True, mean=mean)
+
+
+class _Null:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False
