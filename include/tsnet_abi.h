@@ -113,6 +113,14 @@ int tsnet_set_sources(tsnet_handle h, const float* const* src_img, const float* 
 int tsnet_forward_target(tsnet_handle h, const float* tar_lbl, const float* tar_bbox,
                          float* out_rgb, float* out_flow, int B, void* stream);
 
+/* Clip mode with ONE source set for every driving frame (demo/demo_face.py:185-192): src_img[i] (1,3,H,W), src_lbl[i] (1,L,H,W),
+ * src_bbox[i] (1,H,W).  Afterwards tsnet_forward_target accepts any B in 1..max_batch; frame b of its result has the bits of
+ * tsnet_forward on (the same sources, driving frame b).  The cache holds K encoded images (tsnet_set_sources: K*B); it is replaced
+ * or dropped by tsnet_forward, tsnet_set_sources and tsnet_set_source_divisors like the per-batch cache.  tsnet_train_extras after a
+ * forward on a shared source set returns TSNET_ERR_ARG (its src_img are per batch element). */
+int tsnet_set_sources_shared(tsnet_handle h, const float* const* src_img, const float* const* src_lbl,
+                             const float* const* src_bbox, void* stream);
+
 /* Training-mode extras of the forward (model/TSNet.py:327-331, 372-390, 402-405), computed
  * from the flows and features the LAST tsnet_forward / tsnet_forward_target left in the engine -- call it right after that
  * forward, same B, same source images.  src_img: n_source x (B,3,H,W) raw (the /255 of set_train_input is applied inside);
@@ -124,7 +132,7 @@ int tsnet_train_extras(tsnet_handle h, const float* const* src_img, const float*
                        float* warp_src_img, float* losses, void* stream);
 
 /* Device copies of the stage tensors of the last forward, for stage-wise parity tests
- * (NHWC fp32).  name: "src_fea" (K*B,h,w,c; n = i*B+b), "tar_fea" (B,h,w,c), "pg", "sg" (B,h,w,c),
+ * (NHWC fp32).  name: "src_fea" (K*B,h,w,c; n = i*B+b -- K images after a forward on a shared source set), "tar_fea" (B,h,w,c), "pg", "sg" (B,h,w,c),
  * "dec_map" (B,h,w,c), "dec_up<i>" (B, h<<(i+1), w<<(i+1), c>>(i+1)): RAW output of the i-th decoder
  * up-convolution, before its InstanceNorm + ReLU.  Returns the element count through *count. */
 int tsnet_stage_ptr(tsnet_handle h, const char* name, const float** dev_ptr, size_t* count);

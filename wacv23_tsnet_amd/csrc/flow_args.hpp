@@ -21,13 +21,14 @@ inline size_t flow_lds_bytes(int NT, int h, int w, int C) { return flow_lds_byte
 
 struct FlowArgs {
     const unsigned short* tq; // target planes of B images (l2norm_split_kernel)
-    const unsigned short* sq; // source planes of NB images, n = s*B + b
+    const unsigned short* sq; // source planes of K*SB images: (source s, driving frame b) reads image s*SB + b % SB
     const float* tar_bbox;    // (B, H, W)
-    const float* src_bbox[8]; // per source (B, H, W)
+    const float* src_bbox[8]; // per source (SB, H, W)
     const float* gx;          // (w) linspace(-1,1,w)
     const float* gy;          // (h)
     float* flow;              // (NB, P, 2)
     int B, P, C, h, w, H, W, sy, sx;
+    int SB;                   // source-batch extent: B (every driving frame has its own sources) or 1 (one source set shared by the batch)
     // flow_kernel_p only
     unsigned long long* part; // [NB][tiles][S][64][2]: (max, sum) and (x, y) of a slice's softmax state, two floats per 8-byte word
     int* cnt;                 // [B][tiles] arrival counters, zero between launches

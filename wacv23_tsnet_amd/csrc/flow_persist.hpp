@@ -62,6 +62,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
     const int item = xcd_item(blockIdx.x, (int)gridDim.x);
     const int t = item % tiles, gb = item / tiles;
     const int b = gb % a.B, g = gb / a.B;
+    const int bs = b % a.SB;                  // the frame's image within a source (flow_args.hpp)
     const int tb0 = t * NT;
 
     {   // the workgroup's target fragments: one contiguous region of the plane buffer
@@ -99,11 +100,11 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
         const int n = s_idx * a.B + b;
         const int buf = it & 1;
         const int sp_base = slice * nps;
-        const float* sb = a.src_bbox[s_idx] + (size_t)b * a.H * a.W;
+        const float* sb = a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
         float m_run[NT], l_run[NT], ax[NT], ay[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) { m_run[j] = -3.0e38f; l_run[j] = 0.f; ax[j] = 0.f; ay[j] = 0.f; }
-        const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)n * (a.P >> 5) * KC) * 2048 + lane * 16;
+        const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)(s_idx * a.SB + bs) * (a.P >> 5) * KC) * 2048 + lane * 16;
         for (int sp = sp_base + wave; sp < sp_base + nps; sp += kFlowWaves) {
             // this lane's share of the pair's source mask (F.interpolate(nearest)): source sp * 64 + lane; lands under the MFMA sweep
             float msl;

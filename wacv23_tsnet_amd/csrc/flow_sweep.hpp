@@ -32,6 +32,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
     const int item = xcd_item(blockIdx.x, (int)gridDim.x);
     const int n = item / tiles;
     const int s_idx = n / a.B, b = n - s_idx * a.B;
+    const int bs = b % a.SB;                                             // the frame's image within a source (flow_args.hpp)
     const int tb0 = (item - n * tiles) * NT;
 
     // the workgroup's target fragments: one contiguous region of the plane buffer
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
             for (int u = 0; u < 8; ++u) { const int i = i0 + u * NTH + tid; if (i < cnt) d[i] = v[u]; }
         }
     }
-    const float* sb = a.src_bbox[s_idx] + (size_t)b * a.H * a.W;
+    const float* sb = a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
     for (int p = tid; p < Ppad; p += NTH) {
         float v = 0.f;
         if (p < a.P) {
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
     float m_run[NT], l_run[NT], ax[NT], ay[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) { m_run[j] = -3.0e38f; l_run[j] = 0.f; ax[j] = 0.f; ay[j] = 0.f; }
-    const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)n * (Ppad >> 5) * KC) * 2048 + lane * 16;
+    const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)(s_idx * a.SB + bs) * (Ppad >> 5) * KC) * 2048 + lane * 16;
     const unsigned char* tbase = smem_raw + lane * 16;
     const int npair = Ppad >> 6;
     for (int sp = wave; sp < npair; sp += kFlowWaves) {

@@ -73,10 +73,11 @@ __global__ __launch_bounds__(256) void l2norm_split_kernel(const float* __restri
 // flow, fused with the mean over sources.  NHWC makes every neighbour a contiguous C-float row:
 // the "gather" is four fully coalesced row reads per (target, source).
 struct WarpArgs {
-    const float* src;    // (K*B, h, w, C), n = s*B+b
+    const float* src;    // (K*SB, h, w, C): (source s, driving frame b) reads image s*SB + b % SB
     const float* flow;   // (K*B, P, 2)
     float* out;          // (B, P, C)
     int B, K, h, w, C;
+    int SB;              // source-batch extent: B, or 1 for one source set shared by the batch
 };
 
 __global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
@@ -87,6 +88,7 @@ __global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
         const int c = (int)(i % c4n) * 4;
         const size_t bp = i / c4n;
         const int b = (int)(bp / P), p = (int)(bp - (size_t)b * P);
+        const int bs = b % a.SB;
         float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int s = 0; s < a.K; ++s) {
             const int n = s * a.B + b;
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
             const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
             const float wnw = (x1 - ix) * (y1 - iy), wne = (ix - x0) * (y1 - iy);
             const float wsw = (x1 - ix) * (iy - y0), wse = (ix - x0) * (iy - y0);
-            const float* base = a.src + ((size_t)n * P) * a.C + c;
+            const float* base = a.src + ((size_t)(s * a.SB + bs) * P) * a.C + c;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             const bool xin0 = x0 >= 0 && x0 < a.w, xin1 = x1 >= 0 && x1 < a.w;
             const bool yin0 = y0 >= 0 && y0 < a.h, yin1 = y1 >= 0 && y1 < a.h;

@@ -66,16 +66,17 @@ __global__ __launch_bounds__(256) void in_stats_partial_kernel(StatsArgs a) {
     }
 }
 
-// The same reduction fused with an addition: y[n] = x[n] + add[n % add_nmod], statistics of y.  FuseNet's first convolution is split at
+// The same reduction fused with an addition: y[n] = x[n (or its source image, x_sb)] + add[n % add_nmod], statistics of y.  FuseNet's first convolution is split at
 // the channel concat (TSNet.py:195-197: cat(src_fea, tar_fea) -> conv): the per-source half is computed once per source set
 // (tsnet_set_sources, cached in clip mode), the shared target half once per driving frame; this kernel joins them and produces the
 // InstanceNorm statistics of the sum.  One-shot forward and clip mode run the SAME kernels in the same order: bit-identical results.
 struct AddStatsArgs {
-    const float* x;      // (N, HW, C)
+    const float* x;      // (N / add_nmod * x_sb, HW, C): image n reads x[n / add_nmod * x_sb + n % add_nmod % x_sb] (x_sb = add_nmod: x[n])
     const float* add;    // (add_nmod, HW, C)
     float* y;            // (N, HW, C)
     double* part;        // (N, S, C, 2)
     int HW, C, S, rows_per_split, add_nmod;
+    int x_sb;            // source-batch extent of x: add_nmod, or 1 when the images n with one n / add_nmod share one image of x
 };
 
 __global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) {
@@ -93,8 +94,9 @@ __global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) 
     double sm[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0};
     if (rg < R && cq < cq_total) {
         const size_t cb = (size_t)cq * 4;
-        const float* bx = a.x + ((size_t)n * a.HW) * a.C + cb;
-        const float* ba = a.add + ((size_t)(n % a.add_nmod) * a.HW) * a.C + cb;
+        const int nb = n % a.add_nmod;
+        const float* bx = a.x + ((size_t)(n / a.add_nmod * a.x_sb + nb % a.x_sb) * a.HW) * a.C + cb;
+        const float* ba = a.add + ((size_t)nb * a.HW) * a.C + cb;
         float* by = a.y + ((size_t)n * a.HW) * a.C + cb;
         for (int r = r0 + rg; r < r1; r += R) {
             const float4 u = *reinterpret_cast<const float4*>(bx + (size_t)r * a.C);
@@ -243,17 +245,18 @@ __global__ __launch_bounds__(256) void norm_act_kernel(NormActArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// FuseNet tail: zbar[b,p,:] = (1/K) * sum_i ( cat(src_fea[i*B+b], tar_fea[b])[p,:] + IN(y2[i*B+b])[p,:] )
+// FuseNet tail: zbar[b,p,:] = (1/K) * sum_i ( cat(src_fea[i*SB+b%SB], tar_fea[b])[p,:] + IN(y2[i*B+b])[p,:] )
 // The 1x1 `fuse_net.conv` that follows is linear, so it is applied once to the mean
 // (mean_i conv(z_i)+bias == conv(mean_i z_i)+bias).
 struct FuseTailArgs {
-    const float* src_fea;   // (K*B, P, C1)
+    const float* src_fea;   // (K*SB, P, C1): (source s, driving frame b) reads image s*SB + b % SB
     const float* tar_fea;   // (B, P, C1)
     const float* y2;        // (K*B, P, 2*C1)
     const float* alpha;     // (K*B * 2*C1)
     const float* beta;
     float* zbar;            // (B, P, 2*C1)
     int B, K, P, C1;
+    int SB;                 // source-batch extent: B, or 1 for one source set shared by the batch
 };
 
 __global__ __launch_bounds__(256) void fuse_resid_mean_kernel(FuseTailArgs a) {
@@ -265,11 +268,12 @@ __global__ __launch_bounds__(256) void fuse_resid_mean_kernel(FuseTailArgs a) {
         const size_t bp = i / c4n;                  // b*P + p
         const int b = (int)(bp / a.P);
         const int p = (int)(bp - (size_t)b * a.P);
+        const int bs = b % a.SB;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int s = 0; s < a.K; ++s) {
             const int n = s * a.B + b;
             float4 xr;
-            if (c < a.C1) xr = *reinterpret_cast<const float4*>(a.src_fea + ((size_t)n * a.P + p) * a.C1 + c);
+            if (c < a.C1) xr = *reinterpret_cast<const float4*>(a.src_fea + ((size_t)(s * a.SB + bs) * a.P + p) * a.C1 + c);
             else          xr = *reinterpret_cast<const float4*>(a.tar_fea + ((size_t)b * a.P + p) * a.C1 + (c - a.C1));
             const float4 y = *reinterpret_cast<const float4*>(a.y2 + ((size_t)n * a.P + p) * C + c);
             const float4 al = *reinterpret_cast<const float4*>(a.alpha + (size_t)n * C + c);

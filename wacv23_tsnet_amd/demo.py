@@ -133,23 +133,28 @@ class ClipRunner:
       * the K source frames are encoded ONCE (`tsnet_set_sources`; the reference re-encodes them for every driving frame, :187-192);
       * every driving frame is one `tsnet_forward_target` at batch 1, re-normalised to the first source image's statistics and turned
         into RGB bytes on the device (`DemoPostprocessor`); only the bytes cross PCIe;
+      * with batch > 1 the one source set is cached for the whole batch (`tsnet_set_sources_shared`: K encoded images, not K * batch) and
+        `run()` walks the clip in groups of `batch` driving frames with a ragged last group -- the same bytes as batch 1, at the batch rate;
       * the three-panel strips and the GIF are written with PIL.
     model: a wacv23_tsnet_amd.model.TSNet on the GPU.
 
-    The runner OWNS an engine -- a second copy of the packed weights (~350 MB for the 67 M-parameter net) plus a batch-1 arena on the device.
+    The runner OWNS an engine -- a second copy of the packed weights (~350 MB for the 67 M-parameter net) plus an arena for `batch` frames on the device.
     Release it with `close()` or use the runner as a context manager (`with ClipRunner(...) as r:`); `__del__` is only a fallback (at
     interpreter shutdown the library may already be gone)."""
 
-    def __init__(self, model, src_img: Sequence[torch.Tensor], src_lbl: Sequence[torch.Tensor], src_bbox: Sequence[torch.Tensor]):
+    def __init__(self, model, src_img: Sequence[torch.Tensor], src_lbl: Sequence[torch.Tensor], src_bbox: Sequence[torch.Tensor], batch: int = 1):
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
         self.model = model
-        # its OWN engine (batch 1, the model's weights at this moment, default /255 source divisors): the model's shared engine is
+        self.batch = batch
+        # its OWN engine (the model's weights at this moment, default /255 source divisors): the model's shared engine is
         # re-created when a later forward() needs a larger batch or new weights, and carries the divisors of the last set_train_input
-        self.eng = model._new_engine(1)
+        self.eng = model._new_engine(batch)
         K = model.n_source
         dev = model._device()
         mv = lambda t: t.to(dev, dtype=torch.float32).contiguous()
         self.src_img = [mv(x) for x in src_img[:K]]
-        self.eng.set_sources(self.src_img, [mv(x) for x in src_lbl[:K]], [mv(x) for x in src_bbox[:K]])
+        self.eng.set_sources(self.src_img, [mv(x) for x in src_lbl[:K]], [mv(x) for x in src_bbox[:K]], shared=batch > 1)
         self.post = DemoPostprocessor(self.src_img[0])              # ref_img_list[0] (:180)
 
     def close(self):
@@ -170,17 +175,23 @@ class ClipRunner:
         except Exception:
             pass
 
-    def frame(self, tar_lbl: torch.Tensor, tar_bbox: torch.Tensor) -> torch.Tensor:
-        """one driving frame (1,L,H,W), (1,H,W) -> (H,W,3) uint8 RGB on the device"""
+    def frames(self, tar_lbl: torch.Tensor, tar_bbox: torch.Tensor) -> torch.Tensor:
+        """n <= batch driving frames (n,L,H,W), (n,H,W) in one forward_target -> (n,H,W,3) uint8 RGB on the device"""
+        if tar_lbl.shape[0] > self.batch:
+            raise ValueError(f"{tar_lbl.shape[0]} driving frames, runner built for batch {self.batch}")
         dev = self.src_img[0].device
         rec, _ = self.eng.forward_target(tar_lbl.to(dev, dtype=torch.float32), tar_bbox.to(dev, dtype=torch.float32))
-        return self.post(rec)[0]
+        return self.post(rec)
+
+    def frame(self, tar_lbl: torch.Tensor, tar_bbox: torch.Tensor) -> torch.Tensor:
+        """one driving frame (1,L,H,W), (1,H,W) -> (H,W,3) uint8 RGB on the device"""
+        return self.frames(tar_lbl, tar_bbox)[0]
 
     def run(self, tar_lbls: torch.Tensor, tar_bboxs: torch.Tensor, out_dir: str = None, tar_imgs: torch.Tensor = None, name: str = "clip"):
         """tar_lbls (F,L,H,W), tar_bboxs (F,H,W); returns the generated frames (F,H,W,3) uint8 (host).  With out_dir: strips + GIF."""
         import os
-        frames = [self.frame(tar_lbls[i:i + 1], tar_bboxs[i:i + 1]) for i in range(tar_lbls.shape[0])]
-        out = torch.stack(frames).cpu().numpy()
+        groups = [self.frames(tar_lbls[i:i + self.batch], tar_bboxs[i:i + self.batch]) for i in range(0, tar_lbls.shape[0], self.batch)]
+        out = torch.cat(groups).cpu().numpy()
         if out_dir:
             os.makedirs(out_dir, exist_ok=True)
             strips = []

@@ -192,16 +192,24 @@ class TSNetEngine:
         with self._on_device():
             self._check(self.lib.tsnet_set_source_divisors(self._h, arr, len(d)), "tsnet_set_source_divisors")
 
-    def set_sources(self, src_img, src_lbl, src_bbox):
+    def set_sources(self, src_img, src_lbl, src_bbox, shared: bool = False):
+        """tsnet_set_sources: encode and cache the K sources of a batch; forward_target then takes driving frames of that batch.
+        shared=True (tsnet_set_sources_shared): ONE source set, tensors of batch 1, for every driving frame -- forward_target then
+        takes any batch up to max_batch, and frame b of its result has the bits of forward() on (these sources, frame b)."""
         B = src_img[0].shape[0]
+        if shared and B != 1:
+            raise ValueError(f"shared sources must have batch 1, got {B}")
         H, W, L, K = self.cfg.height, self.cfg.width, self.cfg.label_nc, self.K
         si = [self._prep(src_img[i], (B, 3, H, W), f"src_img[{i}]") for i in range(K)]
         sl = [self._prep(src_lbl[i], (B, L, H, W), f"src_lbl[{i}]") for i in range(K)]
         sb = [self._prep(src_bbox[i], (B, H, W), f"src_bbox[{i}]") for i in range(K)]
         self._same_device(*si, *sl, *sb)
         with self._on_device():
-            rc = self.lib.tsnet_set_sources(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), B, _stream_of(si[0]))
-        self._check(rc, "tsnet_set_sources")
+            if shared:
+                rc = self.lib.tsnet_set_sources_shared(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), _stream_of(si[0]))
+            else:
+                rc = self.lib.tsnet_set_sources(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), B, _stream_of(si[0]))
+        self._check(rc, "tsnet_set_sources_shared" if shared else "tsnet_set_sources")
         self._keep_src = (si, sl, sb)
 
     def forward_target(self, tar_lbl, tar_bbox, return_flow: bool = False):
