@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE ONLY -- runs conv_plan.hpp's pure launch planner on the host for tests/test_conv_plan.py.  One query per input line:
 //   P ks stride pad reflect cin cout npad kpad form N H W csplit transform nprod fin_counter cus  -> plan_conv with the default request
+//   R <the P fields> kernel rows width alt sched chunk xcd_gn [x2_nmod]                           -> plan_conv with that request (x2_nmod: images of the second tensor, default 1)
 //   T kernel tile                                                                                 -> decode_tile_code
 //   V variant                                                                                     -> decode_bench_variant
 //   C code                                                                                        -> decode_head_code
@@ -26,13 +27,21 @@ int main() {
         char q = 0;
         in >> q;
         try {
-            if (q == 'P') {
+            if (q == 'P' || q == 'R') {
                 ConvShape s;
-                int transform = 0, fin = 0, cus = 0;
+                ConvRequest r;
+                int transform = 0, fin = 0, cus = 0, kernel = 0, alt = 0, sched = 0;
                 in >> s.ks >> s.stride >> s.pad >> s.reflect >> s.cin >> s.cout >> s.npad >> s.kpad >> s.form >> s.N >> s.H >> s.W >> s.csplit >> transform
                    >> s.nprod >> fin >> cus;
                 s.transform = transform != 0; s.fin_counter = fin != 0;
-                const ConvPlan p = plan_conv(s, ConvRequest{}, cus);
+                if (q == 'R') {
+                    in >> kernel >> r.rows >> r.width >> alt >> sched >> r.chunk >> r.xcd_gn;
+                    if (!in || kernel < 0 || kernel > 2 || sched < 0 || sched > 2) throw std::invalid_argument("R: seven request fields, kernel and sched 0 to 2");
+                    r.kernel = static_cast<ConvKernel>(kernel); r.alt = alt != 0; r.sched = static_cast<ConvSched>(sched);
+                    int nmod = 0;
+                    if (in >> nmod) s.x2_nmod = nmod;
+                }
+                const ConvPlan p = plan_conv(s, r, cus);
                 o << (int)p.family << ' ' << p.rows << ' ' << p.width << ' ' << (int)p.side_by_side << ' ' << (int)p.sched << ' ' << p.w1_chunk << ' '
                   << p.w1_tab2 << ' ' << p.xcd_gn << ' ' << p.tpi << ' ' << p.tiles_m << ' ' << p.tiles_n << ' ' << (int)p.fin;
             } else if (q == 'T') {

@@ -454,6 +454,111 @@ def conv_h2s32_cases(lib, dev, big=False):
     return worst
 
 
+# ---- the request grid: what tsnet_op_conv2d accepts ------------------------------------------------------------------------------------
+# One layer of every kind, each the smallest shape at which its kernel has a whole tile, crossed with kernel 0..3, every documented tile
+# code (kernel 3: tiles per workgroup) and nprod 1 / 3 / 4.  "What the planner accepts is what is built": an accepted entry runs and
+# matches the reference, a refused one returns TSNET_ERR_ARG before the convolution is launched.  The table below was generated once from
+# the planner (tests/emu/plan_driver.cpp, query R) and is read from here on: tests/test_conv_plan.py holds the planner to it entry by entry,
+# tests/test_emu_ops.py and tests/test_gpu_ops.py walk it through the operator.
+REQUEST_LAYERS = {   # name: (N, H, W, Cin, Cout, k, stride, pad, reflect, norm)
+    "s1_c32": (1, 4, 32, 32, 128, 3, 1, 1, True, True),
+    "s1_c48": (1, 4, 32, 48, 128, 3, 1, 1, True, True),          # three 16-channel slabs: no two-K-group tile
+    "s2_c16": (1, 8, 64, 16, 128, 3, 2, 1, False, True),
+    "stem_c8": (1, 4, 32, 8, 64, 7, 1, 3, True, False),
+    "stem_c32": (1, 4, 32, 32, 64, 7, 1, 3, True, False),
+    "p1_c16": (1, 5, 7, 16, 24, 1, 1, 0, False, False),
+    "p1_c64": (1, 8, 8, 64, 128, 1, 1, 0, False, False),
+}
+REQUEST_TILES = (0, 1, 2, 3, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064)
+# (layer, kernel) -> nprod -> the tile codes accepted; every other tile code of REQUEST_TILES is refused.  (The stems' kernels have one
+# tile and take any decodable code for it.)
+_REQUEST_ACCEPTED = {
+    ("s1_c32", 0): {1: (0, 32, 64, 128, 2128, 3128, 20032, 20064), 3: (0, 32, 64, 128, 2128, 20032, 20064), 4: (0, 64, 128)},
+    ("s1_c32", 1): {1: (0, 64, 128), 3: (0, 64, 128), 4: ()},
+    ("s1_c32", 2): {1: (0, 32, 64, 128, 2128, 3128, 20032, 20064), 3: (0, 32, 64, 128, 2128, 20032, 20064), 4: (0, 64, 128)},
+    ("s1_c32", 3): {1: (0, 1), 3: (0, 1), 4: ()},
+    ("s1_c48", 0): {1: (0, 32, 64, 128, 2128, 3128), 3: (0, 32, 64, 128, 2128), 4: (0, 64, 128)},
+    ("s1_c48", 1): {1: (0, 64, 128), 3: (0, 64, 128), 4: ()},
+    ("s1_c48", 2): {1: (0, 32, 64, 128, 2128, 3128), 3: (0, 32, 64, 128, 2128), 4: (0, 64, 128)},
+    ("s1_c48", 3): {1: (0, 1), 3: (0, 1), 4: ()},
+    ("s2_c16", 0): {1: (0, 64, 128), 3: (0, 64, 128), 4: ()},
+    ("s2_c16", 1): {1: (0, 64, 128), 3: (0, 64, 128), 4: ()},
+    ("s2_c16", 2): {1: (0, 64, 128, 2128), 3: (0, 64, 128, 2128, 12128), 4: ()},
+    ("s2_c16", 3): {1: (), 3: (), 4: ()},
+    ("stem_c8", 0): {1: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 3: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 4: ()},
+    ("stem_c8", 1): {1: (0, 64), 3: (0, 64), 4: ()},
+    ("stem_c8", 2): {1: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 3: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 4: ()},
+    ("stem_c8", 3): {1: (), 3: (), 4: ()},
+    ("stem_c32", 0): {1: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 3: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 4: ()},
+    ("stem_c32", 1): {1: (0, 64), 3: (0, 64), 4: ()},
+    ("stem_c32", 2): {1: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 3: (0, 32, 64, 128, 2128, 3064, 3128, 12128, 20032, 20064), 4: ()},
+    ("stem_c32", 3): {1: (), 3: (), 4: ()},
+    ("p1_c16", 0): {1: (0, 64), 3: (0, 64), 4: ()},
+    ("p1_c16", 1): {1: (0, 64), 3: (0, 64), 4: ()},
+    ("p1_c16", 2): {1: (), 3: (), 4: ()},
+    ("p1_c16", 3): {1: (), 3: (), 4: ()},
+    ("p1_c64", 0): {1: (0, 64, 3064, 3128), 3: (0, 64, 3064, 3128), 4: ()},
+    ("p1_c64", 1): {1: (0, 64, 3064, 3128), 3: (0, 64, 3064, 3128), 4: ()},
+    ("p1_c64", 2): {1: (), 3: (), 4: ()},
+    ("p1_c64", 3): {1: (), 3: (), 4: ()},
+}
+REQUEST_GRID = [dict(layer=l, kernel=k, tile=t, nprod=n, accepted=t in _REQUEST_ACCEPTED[(l, k)][n])
+                for l in REQUEST_LAYERS for k in (0, 1, 2, 3) for n in (1, 3, 4) for t in REQUEST_TILES]
+TSNET_ERR_ARG = -1
+
+
+def request_shape(e, cus=256):
+    """the ConvShape fields of a REQUEST_GRID entry as tests/emu/plan_driver.cpp reads them (tsnet_op_conv2d's OpLayer padding rules)"""
+    N, H, W, Ci, Co, k, st, pad, refl, norm = REQUEST_LAYERS[e["layer"]]
+    form = int(e["kernel"] == 3)
+    kpad = (12 * Ci if form else k * k * Ci) + 31 & ~31
+    npad = Co + 127 & ~127 if Co >= 128 else Co + 63 & ~63
+    return [k, st, pad, int(refl), Ci, Co, npad, kpad, form, N, H, W, 0, int(norm), e["nprod"], 0, cus]
+
+
+def request_grid_walk(lib, dev, rel3, rel1, entries=REQUEST_GRID):
+    """`entries` of REQUEST_GRID through tsnet_op_conv2d on a NaN-filled output.  Accepted: rc == 0 and max|d| / max|fp64 reference| below
+    rel3 (3 / 4 products) or rel1 (bf16 operands).  Refused: TSNET_ERR_ARG, a message, the output untouched.  One input set and one fp64
+    reference per layer.  Returns (accepted, refused) counts."""
+    data, count, reasons = {}, [0, 0], set()
+    for e in entries:
+        N, H, W, Ci, Co, k, st, pad, refl, norm = REQUEST_LAYERS[e["layer"]]
+        if e["layer"] not in data:
+            x = _rand(1, "x", (N, Ci, H, W))
+            w = _rand(1, "w", (Co, Ci, k, k)) * (2.0 / (Ci * k * k) ** 0.5)
+            b = _rand(1, "b", (Co,))
+            al = _rand(1, "al", (N, Ci), 0.5, 1.5) if norm else None
+            be = _rand(1, "be", (N, Ci), -0.3, 0.3) if norm else None
+            xin = F.relu(x * al[:, :, None, None] + be[:, :, None, None]) if norm else x
+            xp = F.pad(xin.double(), (pad,) * 4, mode="reflect" if refl else "constant")
+            ref = F.conv2d(xp, w.double(), b.double(), stride=st)
+            dv = [None if t is None else t.contiguous().to(dev) for t in (nhwc(x), w, b, al, be)]
+            data[e["layer"]] = (dv, ref, float(xin.abs().max()) * 1.0001)
+        (xd, wd, bd, ald, bed), ref, bound = data[e["layer"]]
+        y = torch.full((N, ref.shape[2], ref.shape[3], Co), float("nan"), device=dev)
+        rc = lib.tsnet_op_conv2d(xd.data_ptr(), N, H, W, Ci, wd.data_ptr(), bd.data_ptr(), Co, k, st, pad, int(refl), _p(ald), _p(bed), int(norm),
+                                 bound, e["nprod"], e["kernel"], e["tile"], y.data_ptr(), None)
+        _sync(dev)
+        if e["accepted"]:
+            assert rc == 0, (e, lib.tsnet_op_last_error().decode())
+            err = _rel(nchw(y.cpu()), ref)
+            assert err < (rel1 if e["nprod"] == 1 else rel3), (e, err)
+        else:
+            msg = lib.tsnet_op_last_error().decode()       # (kept from the last failing call: it must be this entry's own)
+            assert rc == TSNET_ERR_ARG and msg.startswith("conv"), (e, rc, msg)
+            if e["kernel"] != 3 and e["tile"] in (1, 2, 3):
+                assert msg.endswith(f"unknown tile code {e['tile']}"), (e, msg)
+            if e["kernel"] == 3 and k != 3:
+                assert "Winograd" in msg, (e, msg)
+            if e["nprod"] == 4 and e["kernel"] == 1 and e["tile"] in (0, 64):
+                assert "products" in msg, (e, msg)
+            reasons.add(msg)
+            assert torch.isnan(y).all().item(), e
+        count[0 if e["accepted"] else 1] += 1
+    assert entries is not REQUEST_GRID or len(reasons) >= 12, reasons      # the whole grid's refusals name a dozen different reasons
+    return tuple(count)
+
+
 # ---- bf16 operands (nprod = 1, tsnet_cfg.operand_mode 1 / 2) against an OPERAND-EXACT reference ------------------------------------------
 # A bf16 conversion is exactly specified: with both operands rounded to nearest even, every product is exact in fp32 and the only error left
 # is the fp32 accumulation.  The reference therefore rounds where the kernels round -- t = fp32(x*alpha + beta) (one rounding: the staging's

@@ -7,12 +7,16 @@
 (b) the choices a frame's bits depend on -- family, tile rows, statistics tiling -- are the same in every batch, and so are the tile width
     and wave grid outside conv_h2 / conv_h2r (whose one-group tiles give the same bits: tests/test_emu_ops.py, tests/test_gpu_ops.py);
 (c) the packed integers of the ABI (tile codes, tsnet_bench_conv's variant bits, tsnet_op_head's flags) decode as documented and
-    undocumented values are refused."""
+    undocumented values are refused;
+(d) what the planner accepts is what is built: it agrees with op_cases.REQUEST_GRID (which the emulator and the GPU walk through the
+    operator) entry by entry, and refuses every layer geometry the kernels cannot index."""
 import json
 import os
 import subprocess
 
 import pytest
+
+import op_cases as oc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "emu", "plan_driver.cpp")
@@ -141,6 +145,9 @@ def test_bench_variant_bits(plan):
         64 | (7 << 16) | (1 << 23) | (8 << 24) | (1 << 22): ([0, 0, 64, 0, 0, 0, 3, 7, 8 | 16 | 32, -1], 3, 0, 0),
         128 | (1 << 28): ([0, 0, 128, 0, 0, 0, 3, 0, 0, 0], 3, 0, 0),
         128 | (5 << 28): ([0, 0, 128, 0, 0, 0, 3, 0, 0, 8], 3, 0, 0),
+        # deep prefetch + two K groups alone is the product's two-group schedule, not an experiment; with an ablation it stays a mask
+        64 | (1 << 23) | (8 << 24): ([0, 0, 64, 0, TWO_GROUPS, 0, 3, 0, 0, -1], 3, 0, 0),
+        64 | (1 << 16) | (1 << 23) | (8 << 24): ([0, 0, 64, 0, 0, 0, 3, 1, 24, -1], 3, 0, 0),
     }
     for v, line in zip(cases, plan([f"V {v}" for v in cases])):
         req, nprod, form, cold = cases[v]
@@ -158,3 +165,78 @@ def test_head_flags_and_rows(plan):
     # head_conv3 on 256^2 (8 column tiles): 32 rows from B = 4 on, 16 at B = 2, 8 for one frame; other CU counts scale the thresholds
     q = [f"H {b} 8 256 {cus}" for cus in (256, 128) for b in (1, 2, 4, 8)]
     assert [int(v) for v in plan(q)] == [8, 16, 32, 32, 16, 32, 32, 32]
+
+
+def _request_query(e, shape=None, request=None):
+    """the R query of a REQUEST_GRID entry; `request`: (kernel, rows, width, alt, sched, chunk, xcd_gn) instead of the entry's tile code"""
+    return "R " + " ".join(str(v) for v in (shape or oc.request_shape(e)) + list(request))
+
+
+def _requests_of(plan, entries):
+    """decode_tile_code of every entry -> its request fields (None where the code itself is refused)"""
+    out = []
+    for e, line in zip(entries, plan([f"T {e['kernel']} {e['tile']}" for e in entries])):
+        v = None if line.startswith("ERR") else _ints(line)
+        out.append(None if v is None else v[:6] + [v[9]])
+    return out
+
+
+def test_request_grid(plan):
+    """the planner agrees with op_cases.REQUEST_GRID entry by entry, and the combinations that used to plan a kernel that is not built are
+    refused, each for its own reason"""
+    grid = oc.REQUEST_GRID
+    assert len(grid) == 7 * 4 * 3 * 13 and sum(e["accepted"] for e in grid) == 217
+    reqs = _requests_of(plan, grid)
+    live = [(e, r) for e, r in zip(grid, reqs) if r is not None]
+    assert all(not e["accepted"] for e, r in zip(grid, reqs) if r is None)
+    why = {}
+    for (e, r), line in zip(live, plan([_request_query(e, request=r) for e, r in live])):
+        assert (not line.startswith("ERR")) == e["accepted"], (e, line)
+        why[(e["layer"], e["kernel"], e["tile"], e["nprod"])] = line
+    gaps = {   # (layer, kernel, tile, nprod): a word of the refusal
+        ("s1_c32", 2, 12128, 3): "deep schedule",                 # 2 x 128 deep on a 3 x 3 / stride-1 layer
+        ("s1_c48", 2, 20032, 3): "even number", ("s1_c48", 2, 20064, 1): "even number",      # two K groups on three slabs
+        ("s1_c32", 2, 20064, 4): "products", ("s1_c32", 2, 32, 4): "products", ("s1_c32", 2, 2128, 4): "products",
+        ("s2_c16", 2, 64, 4): "products", ("stem_c8", 2, 0, 4): "products", ("stem_c32", 0, 0, 4): "products",
+        ("s1_c32", 1, 64, 4): "products", ("p1_c64", 1, 3064, 4): "products", ("s1_c32", 3, 0, 4): "products",
+        ("s2_c16", 2, 32, 3): "4x64", ("s2_c16", 2, 12128, 1): "fp16 x 2",
+        ("stem_c8", 1, 128, 3): "128-wide", ("p1_c16", 1, 128, 3): "128-wide", ("stem_c32", 1, 128, 1): "128-wide",
+    }
+    for k, word in gaps.items():
+        assert why[k].startswith("ERR") and word in why[k], (k, why[k])
+    # requests no tile code spells: two rows at the planner's width (2 x 64 is not built), the side-by-side grid on two rows,
+    # a 1 x 1 layer with 8 input channels on the general kernel
+    s1, s2 = dict(layer="s1_c32", kernel=2, nprod=3), dict(layer="s2_c16", kernel=2, nprod=3)
+    s1_64 = oc.request_shape(s1)
+    s1_64[5] = s1_64[6] = 64                                   # 64 output channels: the planner's width is 64
+    s2_64 = oc.request_shape(s2)
+    s2_64[5] = s2_64[6] = 64
+    p1_8 = oc.request_shape(dict(layer="p1_c16", kernel=1, nprod=3))
+    p1_8[4], p1_8[7] = 8, 32
+    s1_8 = oc.request_shape(dict(layer="s1_c32", kernel=1, nprod=3))
+    s1_8[4], s1_8[7] = 8, 96                                   # a 3 x 3 layer with 8 input channels: no 128-wide tile of the general kernel
+    w1 = dict(layer="s1_c32", kernel=3, nprod=3)               # the Winograd form takes no schedule
+    q = [_request_query(s1, s1_64, (KERNEL_PATCH, 2, 0, 0, PLAIN, 0, -1)), _request_query(s2, s2_64, (KERNEL_PATCH, 2, 0, 0, PLAIN, 0, -1)),
+         _request_query(dict(layer="s1_c32", kernel=2, nprod=1), None, (KERNEL_PATCH, 2, 128, 1, PLAIN, 0, -1)),
+         _request_query(None, p1_8, (KERNEL_GENERAL, 0, 64, 0, PLAIN, 0, -1)), _request_query(None, s1_8, (KERNEL_GENERAL, 0, 128, 0, PLAIN, 0, -1)),
+         _request_query(w1, None, (KERNEL_OWN, 0, 0, 0, TWO_GROUPS, 0, -1))]
+    for line, word in zip(plan(q), ("4x32, 4x64", "4x64 (four waves)", "bf16 4 x 128", "1x1 layers", "128-wide", "conv(w1)")):
+        assert line.startswith("ERR") and word in line, line
+
+
+def test_geometry_is_refused_by_the_planner(plan):
+    """the layer / tensor checks of conv_plan.hpp's validate_conv (run_conv keeps only what depends on pointers): each refuses through the driver, by name"""
+    ok = dict(ks=3, stride=1, pad=1, reflect=1, cin=64, cout=64, npad=64, kpad=576, form=0, N=1, H=8, W=8, csplit=0, transform=0, nprod=3, fin_counter=0)
+    bad = [(dict(ks=5, kpad=1600), "kernel size"), (dict(cin=24, kpad=224), "input channels"), (dict(H=0), "empty"), (dict(N=0), "empty"),
+           (dict(ks=7, pad=3, H=3, kpad=3136), "reflection pad"), (dict(pad=8), "reflection pad"), (dict(csplit=24), "channel split"),
+           (dict(csplit=64), "channel split"), (dict(N=64, H=512, W=512, cin=32, kpad=288), "32-bit"), (dict(N=32, H=1024, W=1024, cin=8, kpad=96), "32-bit"),
+           (dict(cin=4112, kpad=37024), "transform table"), (dict(stride=0), "stride"), (dict(nprod=2), "products")]
+    q = ["P " + " ".join(str({**ok, **d}[k]) for k in SHAPE_KEYS) + " 256" for d, _ in [({}, "")] + bad]
+    got = plan(q)
+    assert not got[0].startswith("ERR"), got[0]
+    for (d, word), line in zip(bad, got[1:]):
+        assert line.startswith("ERR") and word in line, (d, line)
+    # the second tensor of a concat has its own extent: 16 of 48 channels from x, 32 from x2 with x2_nmod images
+    cat = " ".join(str({**ok, "cin": 48, "kpad": 448, "csplit": 16, "N": 2, "H": 512, "W": 512}[k]) for k in SHAPE_KEYS) + f" 256 {KERNEL_OWN} 0 0 0 {PLAIN} 0 -1"
+    few, many = plan([f"R {cat} 1", f"R {cat} 64"])
+    assert not few.startswith("ERR") and many.startswith("ERR") and "32-bit" in many, (few, many)

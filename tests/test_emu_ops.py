@@ -148,6 +148,13 @@ def test_bf16_wide_tile_side_by_side_waves(emu_lib):
         oc.conv_h2_case(emu_lib, "cpu", 1, 4, 32, 32, 128, True, nprod=3, tile_n=3128)
 
 
+def test_request_grid_through_the_operator(emu_lib):
+    """op_cases.REQUEST_GRID (seven layer kinds x kernel 0..3 x every tile code x nprod 1 / 3 / 4) through tsnet_op_conv2d: what the planner
+    accepts runs and matches the fp64 reference (REL for 3 / 4 products, 2e-2 with bf16 operands); everything else returns TSNET_ERR_ARG with a
+    message and leaves the NaN-filled output untouched.  All 1092 entries, none thinned: 217 accepted, 875 refused."""
+    assert oc.request_grid_walk(emu_lib, "cpu", REL, 2e-2) == (217, 875)
+
+
 # ---- bf16 operands against the OPERAND-EXACT reference (op_cases.bf16_conv_ref): t = fp32(x*alpha + beta), ReLU, padding of t, bf16(t) and
 # bf16(w) by round-to-nearest-even, fp64 sums.  Every product is then exact in fp32; the only error left is the fp32 accumulation (measured
 # 1.1 - 3.4e-7 per family here), while rounding at another point or in another mode costs 1.4 - 3.8e-3.  The 2e-2 checks against fp64 above stay.

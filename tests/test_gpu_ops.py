@@ -19,6 +19,12 @@ def lib():
 REL = 1e-6     # conv error relative to max|fp64 reference| (fp32-class: exact fp16 x 2 products, two-level fp32 accumulation)
 
 
+def test_request_grid_through_the_operator(lib):
+    """op_cases.REQUEST_GRID through tsnet_op_conv2d (tests/test_emu_ops.py has the same walk): all 1092 entries, 217 accepted -- they run and
+    match the fp64 reference -- and 875 refused with TSNET_ERR_ARG, a message and an untouched output, before the convolution is launched"""
+    assert oc.request_grid_walk(lib, DEV, REL, 2e-2) == (217, 875)
+
+
 # ---- the general implicit-GEMM kernel (conv_h2r.hpp): layers / frame sizes without a patch kernel
 @pytest.mark.parametrize("k,stride,pad,reflect", [(7, 1, 3, True), (3, 2, 1, False), (3, 1, 1, True), (1, 1, 0, False)])
 @pytest.mark.parametrize("norm", [False, True])

@@ -9,39 +9,26 @@ namespace {
 
 template <int KS, int BN, int NPROD, bool SMALL>
 void go(const ConvArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)h2r_lds_bytes(a.Cin);
-    if (a.in_alpha) {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(conv_h2r_kernel<KS, BN, 2, 2, NPROD, true, SMALL>), lds);
-        hipLaunchKernelGGL((conv_h2r_kernel<KS, BN, 2, 2, NPROD, true, SMALL>), dim3(a.tiles_m * a.tiles_n), dim3(256), lds, s, a);
-    } else {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(conv_h2r_kernel<KS, BN, 2, 2, NPROD, false, SMALL>), lds);
-        hipLaunchKernelGGL((conv_h2r_kernel<KS, BN, 2, 2, NPROD, false, SMALL>), dim3(a.tiles_m * a.tiles_n), dim3(256), lds, s, a);
-    }
+    launch_tiles(a.in_alpha ? conv_h2r_kernel<KS, BN, 2, 2, NPROD, true, SMALL> : conv_h2r_kernel<KS, BN, 2, 2, NPROD, false, SMALL>, 256, (size_t)h2r_lds_bytes(a.Cin), a, s);
 }
 
 template <int NPROD>
-void go_np(const ConvArgs& a, int ks, int bn, hipStream_t s) {
+void go_np(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     const bool small = a.Cin == 8;
-    if (bn == 128) {
-        if (ks != 3 || small) throw std::invalid_argument("conv(h2r): 128-wide tiles are built for 3x3 layers with at least 16 input channels");
-        go<3, 128, NPROD, false>(a, s);
-        return;
+    if (p.width == 128) {
+        if (a.taps == 9 && !small) return go<3, 128, NPROD, false>(a, s);
+    } else if (p.width == 64) {
+        if (a.taps == 1 && !small) return go<1, 64, NPROD, false>(a, s);
+        if (a.taps == 9) return small ? go<3, 64, NPROD, true>(a, s) : go<3, 64, NPROD, false>(a, s);
+        if (a.taps == 49) return small ? go<7, 64, NPROD, true>(a, s) : go<7, 64, NPROD, false>(a, s);
     }
-    if (bn != 64) throw std::invalid_argument("conv(h2r): tile width must be 64 or 128");
-    switch (ks) {
-        case 1: if (small) throw std::invalid_argument("conv(h2r): 1x1 layers need at least 16 input channels"); go<1, 64, NPROD, false>(a, s); break;
-        case 3: if (small) go<3, 64, NPROD, true>(a, s); else go<3, 64, NPROD, false>(a, s); break;
-        case 7: if (small) go<7, 64, NPROD, true>(a, s); else go<7, 64, NPROD, false>(a, s); break;
-        default: throw std::invalid_argument("conv: kernel size must be 1, 3 or 7");
-    }
+    plan_not_built(p, NPROD);
 }
 
 }  // namespace
 
-void launch_conv_h2r(const ConvArgs& a, int ks, int bn, int nprod, hipStream_t s) {
-    if (nprod == 3) go_np<3>(a, ks, bn, s);
-    else if (nprod == 1) go_np<1>(a, ks, bn, s);
-    else throw std::invalid_argument("conv(h2r): 1 (bf16 operands) or 3 products");
+void launch_conv_h2r(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_t s) {
+    nprod == 3 ? go_np<3>(a, p, s) : go_np<1>(a, p, s);
 }
 
 }  // namespace tsnet

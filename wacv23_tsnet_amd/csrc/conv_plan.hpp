@@ -1,5 +1,8 @@
 // conv_plan.hpp -- which kernel, tile and schedule a convolution launch runs on.  Plain C++17: no HIP, no device code, so that every launch
-// choice can be checked on the CPU (tests/test_conv_plan.py).  engine.cpp's run_conv validates its arguments, asks plan_conv, launches.
+// choice can be checked on the CPU (tests/test_conv_plan.py).  The planner VALIDATES AND CHOOSES: plan_conv refuses (std::invalid_argument)
+// every layer geometry the kernels cannot index (validate_conv) and every request whose kernel the product build does not instantiate, so
+// a ConvPlan always names a kernel that exists.  engine.cpp's run_conv checks what depends on pointers, asks plan_conv, fills ConvArgs from
+// the plan and hands both to the family's launcher (kernels.hpp), which only dispatches: no launcher repeats a rule written here.
 //
 // The promise these rules keep: the kernel family and the tile rows (and with them the statistics tiling) depend on the layer and the frame
 // size only -- never on the batch (the patch kernels sum K slab-major, the general one tap-major; a tile's rows decide how the statistics
@@ -30,6 +33,7 @@ struct ConvShape {
     int form = 0;                // 1: packed in the Winograd-along-x form (conv_w1.hpp)
     int N = 0, H = 0, W = 0;
     int csplit = 0;              // > 0: channels >= csplit come from a second tensor (concat on load)
+    int x2_nmod = 1;             // images of that second tensor (image n reads its image n % x2_nmod)
     bool transform = false;      // the producer's InstanceNorm (+ ReLU) applied while the operand is staged
     int nprod = 3;               // 1 = bf16 operands, 3 or 4 fp16 x 2 products
     bool fin_counter = false;    // output statistics with arrival counters supplied: the in-kernel finalize is possible
@@ -97,6 +101,8 @@ inline BenchVariant decode_bench_variant(int variant) {
     b.cold = (v & (1 << 21)) != 0;
     b.req.abl = (v >> 16) & 31;
     b.req.opt = ((v >> 24) & 15) | ((v & (1 << 23)) ? 16 : 0) | ((v & (1 << 22)) ? 32 : 0);
+    // deep prefetch + two K groups and nothing else is no experiment: the product's two-group tiles (tile codes 20032 / 20064)
+    if (!b.req.abl && b.req.opt == (8 | 16)) { b.req.sched = ConvSched::TwoGroups; b.req.opt = 0; }
     const int gx = (v >> 28) & 7;                  // 0 the planner's, 1 linear, 2..5 a grid with 1, 2, 4, 8 columns
     if (gx > 5) throw std::invalid_argument("bench_conv: XCD grid code 0 to 5");
     b.req.xcd_gn = gx == 0 ? -1 : (gx == 1 ? 0 : 1 << (gx - 2));
@@ -114,14 +120,31 @@ inline HeadRequest decode_head_code(int code) {
     return r;
 }
 
-inline size_t w1_lds_bytes_host(int Cin, int tables) {       // conv_w1.hpp w1_lds_bytes for the two-plane stages
+constexpr size_t w1_lds_bytes_host(int Cin, int tables) {       // conv_w1.hpp w1_lds_bytes for the two-plane stages
     return 3 * (size_t)(2 * (4 * 2 * 2 * (96 * 16 + 64) + 32)) + (size_t)tables * 2 * ((Cin + 31) / 32 * 32) * 4;
 }
 // a layer packed in the Winograd-along-x form runs conv_w1 and nothing else: 3 x 3 / stride 1 / pad 1 on frames of whole 4 x 32 tiles
 inline bool w1_eligible(int ks, int stride, int pad, int cin, int H, int W) {
-    // (the three V stages + the transform table of 2 Cin floats must fit the CU's 160 KiB beside the epilogue's 64 B of static LDS)
+    // (the three V stages + the transform table of 2 Cin floats must fit the CU's 160 KiB beside the epilogue's 64 B of static LDS: 1216
+    // channels at most, inside the two channels per thread that the prologue's table request covers -- conv_w1_launch.cpp asserts it)
     return ks == 3 && stride == 1 && pad == 1 && cin >= 16 && (cin & 15) == 0 && H >= 4 && W >= 32 && H % kPlanTileRows == 0 && W % kPlanTileCols == 0 &&
            w1_lds_bytes_host(cin, 1) + 256 <= 160 * 1024;
+}
+
+// What every convolution kernel assumes of a layer and a call: a refusal here comes before anything is launched.
+inline void validate_conv(const ConvShape& s) {
+    auto refuse = [](const char* why) { throw std::invalid_argument(why); };
+    if (s.ks != 1 && s.ks != 3 && s.ks != 7) refuse("conv: kernel size must be 1, 3 or 7");
+    if (s.cin != 8 && (s.cin < 16 || (s.cin & 15))) refuse("conv: input channels must be 8 or a multiple of 16 (pad with zeros)");
+    if (s.stride < 1 || s.pad < 0) refuse("conv: the stride must be positive, the padding not negative");
+    if (s.N < 1 || s.H < 1 || s.W < 1 || s.H + 2 * s.pad < s.ks || s.W + 2 * s.pad < s.ks || s.cout < 1) refuse("conv: empty tensor");
+    if (s.reflect && (s.pad >= s.H || s.pad >= s.W)) refuse("conv: reflection pad needs pad < input size");
+    if (s.csplit && ((s.csplit & 15) || s.csplit < 0 || s.csplit >= s.cin)) refuse("conv: channel split must be a multiple of 16 inside the channel range");
+    const double px = (double)s.H * s.W * 4, c1 = s.csplit ? s.csplit : s.cin;
+    if (s.N * px * c1 >= 2147483648.0 || s.x2_nmod * px * (s.cin - c1) >= 2147483648.0 || (double)s.N * s.ho() * s.wo() * s.cout >= 2147483647.0 ||
+        (double)s.kpad * s.npad * 2 >= 2147483648.0)
+        refuse("conv: tensor too large for 32-bit buffer offsets");
+    if ((size_t)2 * s.cin * 4 > 32 * 1024) refuse("conv: too many input channels for the transform table");
 }
 
 // Kernel class of a layer at a frame size.  The patch kernels sum K slab-major, the general one tap-major: the class must depend on the
@@ -195,13 +218,13 @@ inline void plan_w1_chunk(const ConvShape& s, const ConvRequest& r, int cus, Con
 }
 
 inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
+    validate_conv(s);
     const bool bf16 = s.nprod == 1;
     const int Ho = s.ho(), hw = Ho * s.wo();
     ConvPlan p;
     if (s.form == 1) {
         if (s.csplit || !w1_eligible(s.ks, s.stride, s.pad, s.cin, s.H, s.W))
             throw std::invalid_argument("conv(w1): the layer is packed in the Winograd form, which needs a single source and whole 4 x 32 tiles");
-        if (s.nprod == 4) throw std::invalid_argument("conv(w1): 1 or 3 products");
         p.family = ConvFamily::W1;
     } else if (r.kernel == ConvKernel::General) {
         p.family = ConvFamily::H2R;
@@ -209,6 +232,8 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         p.family = conv_class(s, r.rows == 2 ? 2 : kPlanTileRows, r.kernel == ConvKernel::Patch);
         if (r.kernel == ConvKernel::Patch && p.family == ConvFamily::H2R) throw std::invalid_argument("conv: this layer / frame size has no patch kernel");
     }
+    if (s.nprod != 1 && s.nprod != 3 && (s.nprod != 4 || p.family != ConvFamily::H2))
+        throw std::invalid_argument("conv: 1 (bf16 operands) or 3 products; four on the 3x3 / stride-1 patch kernel's plain 4x64 and 4x128 tiles");
     auto set_tiles = [&](int rows_per_tile_m, int bn) {     // rows_per_tile_m: output positions of an M tile (patch: PR * 32; general: 128)
         p.tpi = (hw + rows_per_tile_m - 1) / rows_per_tile_m;
         p.tiles_m = s.N * p.tpi; p.tiles_n = (s.cout + bn - 1) / bn;
@@ -218,7 +243,7 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
     };
     switch (p.family) {
     case ConvFamily::W1:
-        if (r.opt) throw std::invalid_argument("conv(w1): no experiment variants");
+        if (r.opt || r.sched != ConvSched::Plain) throw std::invalid_argument("conv(w1): no experiment variants");
         p.rows = kPlanTileRows; p.width = 64;
         set_tiles(kPlanTileRows * kPlanTileCols, 64);
         p.xcd_gn = xcd_grid(s, r.xcd_gn, p.tiles_m, p.tiles_n, "conv(w1)");
@@ -249,8 +274,16 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         // up-convolution (profiles/round6_h2_1x4.txt).  Same K order and chains: the same bits as the 2 x 2 form (tests).  Tile code 3128
         // forces it, 128 the 2 x 2 form.
         p.side_by_side = r.alt || (!r.width && bf16 && pr == 4 && bn == 128);
-        if (p.side_by_side && (!bf16 || bn != 128)) throw std::invalid_argument("conv(h2): the 1 x 4 wave grid is the bf16 4 x 128 tile's");
-        if ((pr != 2 && pr != 4) || Ho % pr) throw std::invalid_argument("conv(h2): the output height must be a multiple of the tile's rows (2 or 4)");
+        // what conv_h2_launch.cpp instantiates
+        if (p.side_by_side && (!bf16 || bn != 128 || pr != 4)) throw std::invalid_argument("conv(h2): the 1 x 4 wave grid is the bf16 4 x 128 tile's");
+        if (!(pr == 4 && (bn == 32 || bn == 64 || bn == 128)) && !(pr == 2 && bn == 128)) throw std::invalid_argument("conv(h2): tile must be 4x32, 4x64, 4x128 or 2x128");
+        if (Ho % pr) throw std::invalid_argument("conv(h2): the output height must be a multiple of the tile's rows (2 or 4)");
+        if (s.nprod == 4 && (pr != 4 || bn == 32 || r.sched != ConvSched::Plain)) throw std::invalid_argument("conv(h2): four products on the plain 4x64 and 4x128 tiles");
+        if (r.sched == ConvSched::Deep) throw std::invalid_argument("conv(h2): the deep schedule (1xxxx) is the stride-2 2 x 128 tile's");
+        if (r.sched == ConvSched::TwoGroups && (pr != 4 || bn == 128 || r.abl || r.opt))
+            throw std::invalid_argument("conv(h2): the two-group tiles are 4x32 and 4x64, without experiment variants");
+        if ((r.sched == ConvSched::TwoGroups || (r.opt & 16)) && (s.cin >> 4) % 2)       // (opt bit 4: the tools build's two-group experiments)
+            throw std::invalid_argument("conv(h2): two K groups need an even number of 16-channel slabs");
         if (s.npad % bn) throw std::invalid_argument("conv(h2): the tile width must divide the padded output width");
         p.rows = pr; p.width = bn; p.sched = r.sched;
         set_tiles(pr * kPlanTileCols, bn);
@@ -273,6 +306,8 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
             bn = 64;
             if (s.npad % 128 == 0 && s.cout > 64 && Ho % 2 == 0) { pr = 2; bn = 128; }
         }
+        if (!(pr == 4 && (bn == 64 || bn == 128)) && !(pr == 2 && bn == 128))
+            throw std::invalid_argument("conv(h2d): tile must be 4x64 (four waves), 4x128 (eight waves) or 2x128 (four waves)");
         if (s.npad % bn) throw std::invalid_argument("conv(h2d): the tile width must divide the padded output width");
         if (Ho % pr) throw std::invalid_argument("conv(h2d): the output height must be a multiple of the tile's rows");
         p.rows = pr; p.width = bn;
@@ -281,19 +316,19 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         // workgroup's memory round trips (72 -> us on the 64-tile launch).  Same bits: the choice may follow the batch.  Tile code 12128 forces
         // it, 2128 the plain schedule.
         const bool deep = r.width ? r.sched == ConvSched::Deep : (pr == 2 && bn == 128 && s.nprod == 3 && (long)p.tiles_m * p.tiles_n <= 2L * cus);
+        if (deep && (pr != 2 || bn != 128 || s.nprod != 3)) throw std::invalid_argument("conv(h2d): the deep schedule is the 2 x 128 tile's, fp16 x 2 operands");
         p.sched = deep ? ConvSched::Deep : ConvSched::Plain;
         break;
     }
     case ConvFamily::H2R:
     case ConvFamily::G64: {
         if (r.abl || r.opt) throw std::invalid_argument("conv: experiment variants exist for the 3x3 / stride-1 patch kernel only");
-        if (r.rows || r.sched != ConvSched::Plain || r.width == 32) throw std::invalid_argument("conv(h2r): the tile width must be 64 or 128");
+        if (r.rows || r.sched != ConvSched::Plain || (r.width && r.width != 64 && r.width != 128)) throw std::invalid_argument("conv(h2r): the tile width must be 64 or 128");
         // 64-deep K steps (conv_g64.hpp: the same bits, a quarter of the barriers and address computations, whole cache lines per
         // load) wherever the layer allows: 1 x 1 / 3 x 3, input channels (and the concat split) multiples of 64, 128-wide output.  In the
         // forward: the two 1 x 1 convolutions, the 64 -> 128 stride-2 layer and, with bf16 operands, every stride-2 layer.  Tile codes
         // 3064 / 3128 (with kernel = general) request it with 64 / 128 rows; 64 / 128 request conv_h2r with that width.
-        const bool g64_ok = (s.ks == 1 || s.ks == 3) && (s.cin & 63) == 0 && (!s.csplit || (s.csplit & 63) == 0) && s.npad % 128 == 0 && s.cout > 64 &&
-                            (s.nprod == 1 || s.nprod == 3);
+        const bool g64_ok = (s.ks == 1 || s.ks == 3) && (s.cin & 63) == 0 && (!s.csplit || (s.csplit & 63) == 0) && s.npad % 128 == 0 && s.cout > 64;
         if (r.alt || (!r.width && g64_ok)) {
             if (!g64_ok) throw std::invalid_argument("conv(g64): needs a 1 x 1 / 3 x 3 layer, input channels in multiples of 64 and more than 64 output channels");
             // rows per tile: 64 in every batch (with statistics the tile decides the partial sums' grouping, so it may never depend on the
@@ -306,6 +341,8 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         } else {
             const long tm = (long)s.N * ((hw + 127) / 128);
             const int bn = r.width ? r.width : ((s.ks == 3 && s.cin >= 16 && wide_pays(s, tm, 1.15, cus)) ? 128 : 64);
+            if (bn == 128 && (s.ks != 3 || s.cin == 8)) throw std::invalid_argument("conv(h2r): 128-wide tiles are built for 3x3 layers with at least 16 input channels");
+            if (s.ks == 1 && s.cin == 8) throw std::invalid_argument("conv(h2r): 1x1 layers need at least 16 input channels");
             if (s.npad % bn) throw std::invalid_argument("conv(h2r): the tile width must divide the padded output width");
             p.family = ConvFamily::H2R;
             p.rows = 128; p.width = bn;
@@ -315,6 +352,20 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
     }
     }
     return p;
+}
+
+// g_launch_counters[3] (tsnet_launch_counters: bench.py labels the roofline kernel with it): rows * 1000 + width of a 3 x 3 / stride-1 tile,
+// 3xxx its side-by-side wave grid, + 20000 two K groups, + 30000 the Winograd form; 0: the family has no code
+inline int plan_tile_code(const ConvPlan& p) {
+    if (p.family == ConvFamily::W1) return 30000 + p.rows * 1000 + p.width;
+    if (p.family != ConvFamily::H2) return 0;
+    return (p.side_by_side ? 3 : p.rows) * 1000 + p.width + (p.sched == ConvSched::TwoGroups ? 20000 : 0);
+}
+
+// A launcher handed a plan it has no kernel for: the planner and the launcher disagree -- a bug, not a user error.
+[[noreturn]] inline void plan_not_built(const ConvPlan& p, int nprod) {
+    throw std::logic_error("conv: no kernel for plan family " + std::to_string((int)p.family) + ", tile " + std::to_string(p.rows) + " x " + std::to_string(p.width) +
+                           (p.side_by_side ? " side by side" : "") + ", schedule " + std::to_string((int)p.sched) + ", " + std::to_string(nprod) + " products");
 }
 
 // RGB head (head_conv.hpp head_conv3_kernel): tile rows by the number of workgroups -- the tallest tile that still gives every CU one: 32

@@ -7,29 +7,26 @@
 
 namespace tsnet {
 
+static_assert(w1_lds_bytes_host(2 * 64 * kW1Waves + 16, 1) + 256 > 160 * 1024, "w1_eligible's LDS budget must stop within the two channels per thread of the prologue's table request");
+
 namespace {
 
 // a launch of one tile per workgroup runs the one-tile kernel (conv_w1_one.hpp: round 4's, shorter prologue); chunks run conv_w1.hpp's
 template <int NPROD, bool AFFINE, int OPT>
 void go_w1_one(const ConvArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)w1_lds_bytes(a.Cin, NPROD == 1 ? 1 : 2, 1);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(conv_w1_one_kernel<NPROD, AFFINE, OPT>), lds);
-    hipLaunchKernelGGL((conv_w1_one_kernel<NPROD, AFFINE, OPT>), dim3(a.tiles_m * a.tiles_n), dim3(64 * kW1Waves), lds, s, a);
+    launch_tiles(conv_w1_one_kernel<NPROD, AFFINE, OPT>, 64 * kW1Waves, (size_t)w1_lds_bytes(a.Cin, NPROD == 1 ? 1 : 2, 1), a, s);
 }
 
 template <int NPROD, bool AFFINE, int OPT>
 void go_w1_k(const ConvArgs& a, size_t lds, hipStream_t s) {
     ensure_dynamic_lds(reinterpret_cast<const void*>(conv_w1_kernel<NPROD, AFFINE, OPT>), lds);
-    const int c = a.w1_chunk > 1 ? a.w1_chunk : 1;
-    if (c > 1 && (a.tiles_m % ((a.xcd_gn > 0 ? 8 / a.xcd_gn : 8) * c) || (a.xcd_gn > 0 && a.tiles_n % a.xcd_gn)))
-        throw std::invalid_argument("conv(w1): the chunk size must divide every XCD's rows of the tile matrix");
+    const int c = a.w1_chunk > 1 ? a.w1_chunk : 1;       // (plan_w1_chunk: divides every XCD's rows of the tile matrix)
     hipLaunchKernelGGL((conv_w1_kernel<NPROD, AFFINE, OPT>), dim3(a.tiles_m * a.tiles_n / c), dim3(64 * kW1Waves), lds, s, a);
 }
 
 template <int NPROD>
 void go_w1(const ConvArgs& a, hipStream_t s) {
     const size_t lds = (size_t)w1_lds_bytes(a.Cin, NPROD == 1 ? 1 : 2, a.w1_tab2 ? 2 : 1);
-    if (NPROD == 1 && a.w1_chunk > 1) throw std::invalid_argument("conv(w1): chunks of several tiles need the two-plane stages");
     if (a.w1_chunk <= 1) {
         if (!a.in_alpha && !a.in_relu) go_w1_one<NPROD, false, 2>(a, s);
         else if (!a.in_alpha) go_w1_one<NPROD, false, 0>(a, s);
@@ -48,7 +45,6 @@ void go_w1(const ConvArgs& a, hipStream_t s) {
 }  // namespace
 
 void launch_conv_w1(const ConvArgs& a, int nprod, int abl, hipStream_t s) {
-    if (a.Cin > 2 * 64 * kW1Waves) throw std::invalid_argument("conv(w1): the prologue's table request covers two channels per thread");      // (the LDS budget stops at ~1200)
     if (abl) {
 #ifdef TSNET_TOOLS
         const size_t lds = (size_t)w1_lds_bytes(a.Cin, 2, a.w1_tab2 ? 2 : 1);
@@ -63,9 +59,7 @@ void launch_conv_w1(const ConvArgs& a, int nprod, int abl, hipStream_t s) {
         throw std::invalid_argument("conv(w1): ablation variants are only built into the tools library");
 #endif
     }
-    if (nprod == 3) go_w1<3>(a, s);
-    else if (nprod == 1) go_w1<1>(a, s);
-    else throw std::invalid_argument("conv(w1): 1 (bf16 operands) or 3 products");
+    nprod == 3 ? go_w1<3>(a, s) : go_w1<1>(a, s);
 }
 
 }  // namespace tsnet

@@ -241,68 +241,54 @@ inline int h2_scale_log2(float bound) {
     return sa;
 }
 
+// What depends on pointers is checked here; the layer, the geometry and the request by plan_conv (conv_plan.hpp), before anything is launched.
 void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req = {}) {
     const bool bf16 = c.nprod == 1;
     if (!L.wq) throw ArgError("conv: layer has no packed weights");
-    if (L.ks != 1 && L.ks != 3 && L.ks != 7) throw ArgError("conv: kernel size must be 1, 3 or 7");
-    if (L.cin_pad != 8 && (L.cin_pad < 16 || (L.cin_pad & 15))) throw ArgError("conv: input channels must be 8 or a multiple of 16 (pad with zeros)");
+    if (c.alpha && !c.beta) throw ArgError("conv: alpha without beta");
+    if ((c.x_bf16 || c.y_bf16) && !bf16) throw ArgError("conv: bf16 storage goes with bf16 operands");
+    if (c.x_bf16 && c.x2) throw ArgError("conv: bf16 storage of a concatenated input is not built");
+    if (c.x2 && c.csplit == 0) throw ArgError("conv: a second tensor needs a channel split");
+#ifdef TSNET_TOOLS
+    req.chunk_cap = g_tools_knob[0];          // tools/forward_ab.py: the same forward with and without chunks, one process
+#endif
+    ConvShape sh;
+    sh.ks = L.ks; sh.stride = L.stride; sh.pad = L.pad; sh.reflect = L.reflect; sh.cin = L.cin_pad; sh.cout = L.cout; sh.npad = L.npad; sh.kpad = L.kpad;
+    sh.form = L.form; sh.N = c.N; sh.H = c.H; sh.W = c.W; sh.csplit = c.x2 ? c.csplit : 0; sh.x2_nmod = c.x2_nmod > 0 ? c.x2_nmod : 1;
+    sh.transform = c.alpha != nullptr; sh.nprod = c.nprod; sh.fin_counter = c.stat_part && c.fin_counter;
+    ConvPlan p;
+    try { p = plan_conv(sh, req, ctx.cus); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     ConvArgs g{};
     g.x = c.x; g.x2 = c.x2; g.in_alpha = c.alpha; g.in_beta = c.alpha ? c.beta : nullptr; g.in_relu = c.relu;
-    if (c.alpha && !c.beta) throw ArgError("conv: alpha without beta");
     const int sa = (bf16 || c.in_amax) ? 0 : h2_scale_log2(L.form == 1 ? 2.f * c.bound : c.bound);   // Winograd: |V| <= 2 max |x|
     g.in_scale = std::ldexp(1.0f, sa); g.in_unscale = std::ldexp(1.0f, -sa);
     g.in_amax = bf16 ? nullptr : c.in_amax; g.in_bound_add = c.bound_add; g.amax_out = c.amax_out;
     g.w = L.wq; g.w_unscale = bf16 ? nullptr : L.w_unscale; g.bias = L.bias; g.y = c.y;
     g.stat_part = c.stat_part; g.addend = c.addend; g.add_nmod = c.add_nmod > 0 ? c.add_nmod : 1;
     g.x_bf16 = c.x_bf16; g.y_bf16 = c.y_bf16;
-    if ((c.x_bf16 || c.y_bf16) && !bf16) throw ArgError("conv: bf16 storage goes with bf16 operands");
-    if (c.x_bf16 && c.x2) throw ArgError("conv: bf16 storage of a concatenated input is not built");
     g.N = c.N; g.H = c.H; g.W = c.W; g.Cin = L.cin_pad; g.cin_log2 = ilog2(L.cin_pad);
-    g.Csplit = c.x2 ? c.csplit : L.cin_pad; g.x2_nmod = c.x2_nmod > 0 ? c.x2_nmod : 1;
-    g.Ho = (c.H + 2 * L.pad - L.ks) / L.stride + 1; g.Wo = (c.W + 2 * L.pad - L.ks) / L.stride + 1;
+    g.Csplit = c.x2 ? c.csplit : L.cin_pad; g.x2_nmod = sh.x2_nmod;
+    g.Ho = sh.ho(); g.Wo = sh.wo();
     g.Cout = L.cout; g.Npad = L.npad; g.stride = L.stride; g.pad = L.pad; g.reflect = L.reflect;
     g.taps = L.form == 1 ? 12 : L.ks * L.ks; g.nchunks = (g.taps * g.Cin + 15) / 16; g.M = c.N * g.Ho * g.Wo;
-    if (c.N < 1 || g.Ho < 1 || g.Wo < 1) throw ArgError("conv: empty tensor");
-    if (L.reflect && (L.pad >= c.H || L.pad >= c.W)) throw ArgError("conv: reflection pad needs pad < input size");
-    if (c.x2 && ((g.Csplit & 15) || g.Csplit <= 0 || g.Csplit >= g.Cin)) throw ArgError("conv: channel split must be a multiple of 16 inside the channel range");
-    if ((double)c.N * c.H * c.W * g.Csplit * 4 >= 2147483648.0 || (double)g.x2_nmod * c.H * c.W * (g.Cin - g.Csplit) * 4 >= 2147483648.0 ||
-        (double)g.M * L.cout >= 2147483647.0 || (double)L.kpad * L.npad * 2 >= 2147483648.0)
-        throw ArgError("conv: tensor too large for 32-bit buffer offsets");
-    if ((size_t)2 * g.Cin * 4 > 32 * 1024) throw ArgError("conv: too many input channels for the transform table");
-#ifdef TSNET_TOOLS
-    req.chunk_cap = g_tools_knob[0];          // tools/forward_ab.py: the same forward with and without chunks, one process
-#endif
-    ConvShape sh;
-    sh.ks = L.ks; sh.stride = L.stride; sh.pad = L.pad; sh.reflect = L.reflect; sh.cin = L.cin_pad; sh.cout = L.cout; sh.npad = L.npad; sh.kpad = L.kpad;
-    sh.form = L.form; sh.N = c.N; sh.H = c.H; sh.W = c.W; sh.csplit = c.x2 ? c.csplit : 0; sh.transform = c.alpha != nullptr; sh.nprod = c.nprod;
-    sh.fin_counter = c.stat_part && c.fin_counter;
+    g.fin_alpha = c.fin_alpha; g.fin_beta = c.fin_beta; g.fin_eps = 1e-5f;
+    // the one place a plan's launch geometry enters the kernel arguments
+    g.tpi = p.tpi; g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n; g.fin_S = p.tpi; g.xcd_gn = p.xcd_gn;
+    g.w1_chunk = p.w1_chunk; g.w1_tab2 = p.w1_tab2; g.fin_counter = p.fin ? c.fin_counter : nullptr;
     TimeScope ts(ctx, c.tclass);
     try {
-        const ConvPlan p = plan_conv(sh, req, ctx.cus);
-        g.tpi = p.tpi; g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n; g.fin_S = p.tpi; g.xcd_gn = p.xcd_gn;
-        g.fin_alpha = c.fin_alpha; g.fin_beta = c.fin_beta; g.fin_eps = 1e-5f; g.fin_counter = p.fin ? c.fin_counter : nullptr;
-        g.w1_chunk = p.w1_chunk; g.w1_tab2 = p.w1_tab2;
-        const bool res = c.tclass == TSNET_T_CONV_RES;
         switch (p.family) {
-        case ConvFamily::W1:
-            launch_conv_w1(g, c.nprod, req.abl, ctx.stream);
-            ++g_launch_counters[0];
-            if (res) g_launch_counters[3] = 4064 + 30000;      // 4 x 32 pixels x 64 channels, Winograd form
-            break;
-        case ConvFamily::H2: {
-            const int opt = req.opt | (p.sched == ConvSched::TwoGroups ? 24 : (p.sched == ConvSched::Deep ? 8 : 0));   // deep prefetch (+ two K groups)
-            launch_conv_h2(g, p.side_by_side ? 5 : p.rows, p.width, c.nprod, req.abl, opt, ctx.stream);
-            ++g_launch_counters[0];
-            if (res) g_launch_counters[3] = (p.side_by_side ? 3 : p.rows) * 1000 + p.width + ((opt & 16) ? 20000 : 0);
-            break;
+        case ConvFamily::W1: launch_conv_w1(g, c.nprod, req.abl, ctx.stream); break;
+        case ConvFamily::H2: launch_conv_h2(g, p, c.nprod, req.abl, req.opt, ctx.stream); break;
+        case ConvFamily::H2S: launch_conv_h2s(g, c.nprod, ctx.stream); break;
+        case ConvFamily::H2S32: launch_conv_h2s32(g, c.nprod, ctx.stream); break;
+        case ConvFamily::H2D: launch_conv_h2d(g, p, c.nprod, ctx.stream); break;
+        case ConvFamily::G64: launch_conv_g64(g, p, c.nprod, ctx.stream); break;
+        case ConvFamily::H2R: launch_conv_h2r(g, p, c.nprod, ctx.stream); break;
         }
-        case ConvFamily::H2S: launch_conv_h2s(g, c.nprod, ctx.stream); ++g_launch_counters[0]; break;
-        case ConvFamily::H2S32: launch_conv_h2s32(g, c.nprod, ctx.stream); ++g_launch_counters[0]; break;
-        case ConvFamily::H2D: launch_conv_h2d(g, p.rows, p.width, c.nprod, p.sched == ConvSched::Deep, ctx.stream); ++g_launch_counters[0]; break;
-        case ConvFamily::G64: launch_conv_g64(g, L.ks, p.rows, c.nprod, ctx.stream); ++g_launch_counters[1]; break;
-        case ConvFamily::H2R: launch_conv_h2r(g, L.ks, p.width, c.nprod, ctx.stream); ++g_launch_counters[1]; break;
-        }
-    } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }      // a tools-build variant that is not instantiated
+    ++g_launch_counters[p.family == ConvFamily::G64 || p.family == ConvFamily::H2R ? 1 : 0];
+    if (c.tclass == TSNET_T_CONV_RES && plan_tile_code(p)) g_launch_counters[3] = plan_tile_code(p);
     check_launch("conv");
     c.stat_S = !c.stat_part ? 0 : (g.fin_counter ? -1 : g.tpi);
 }

@@ -5,26 +5,29 @@
 #include <hip/hip_runtime.h>
 
 #include "conv_common.hpp"
+#include "conv_plan.hpp"
 #include "flow_args.hpp"
 
 namespace tsnet {
 
-// conv_h2.hpp -- patch kernels.  a.tiles_m / tiles_n / tpi are set by the caller; throws std::invalid_argument for a combination that
-// is not instantiated.  nprod: 1 (bf16 operands), 3, or 4 (h2 only); affine = a.in_alpha != null.
-//   h2  (3x3 / stride 1): pr x bn in {4x32, 4x64, 4x128, 2x128}; abl / opt: tools build only (ablation / experiment masks)
+// The convolution launchers DISPATCH: run_conv fills ConvArgs from the ConvPlan (conv_plan.hpp: plan_conv has validated the layer and plans
+// instantiated kernels only); a family with several tiles takes the plan and runs the instantiation it names -- none is a bug, std::logic_error.
+// nprod: 1 (bf16 operands), 3, or 4 (h2 only); affine = a.in_alpha != null; kernel size from a.taps.  abl / opt: tools build only, outside the plan.
+// conv_h2.hpp -- patch kernels:
+//   h2  (3x3 / stride 1): rows x width in {4x32, 4x64, 4x128, 2x128}, the bf16 4x128 tile's side-by-side wave grid, two K groups (4x32, 4x64)
 //   h2s (7x7 stem, 8 input channels): 4 x 64
-//   h2d (3x3 / stride 2): bn = 64 (four waves) or 128 (eight waves)
-void launch_conv_h2(const ConvArgs& a, int pr, int bn, int nprod, int abl, int opt, hipStream_t s);
+//   h2d (3x3 / stride 2): 4x64 (four waves), 4x128 (eight waves), 2x128 (four waves) and its deep schedule
+void launch_conv_h2(const ConvArgs& a, const ConvPlan& p, int nprod, int abl, int opt, hipStream_t s);
 void launch_conv_h2s(const ConvArgs& a, int nprod, hipStream_t s);
-void launch_conv_h2d(const ConvArgs& a, int pr, int bn, int nprod, bool deep, hipStream_t s);
+void launch_conv_h2d(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_t s);
 // conv_w1.hpp -- 3x3 / stride 1 / pad 1 as Winograd F(2,3) along x: 4 x 32 pixels x 64 channels per tile (eight waves); the layer's
 // weights are the TRANSFORMED filters (12 "taps": tap row ky x position p, pack_weights_kernel with kh = 3, kw = 4)
 void launch_conv_w1(const ConvArgs& a, int nprod, int abl, hipStream_t s);      // abl: tools build only
-// conv_h2r.hpp -- general implicit GEMM: ks in {1, 3, 7}, bn = 64 (any) or 128 (ks = 3, Cin >= 16); Cin = 8 or a power of two >= 16
-void launch_conv_h2r(const ConvArgs& a, int ks, int bn, int nprod, hipStream_t s);
+// conv_h2r.hpp -- general implicit GEMM: ks in {1, 3, 7}, 128 positions x 64 (any) or 128 (ks = 3, Cin >= 16) channels; Cin = 8 or a multiple of 16
+void launch_conv_h2r(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_t s);
 // conv_g64.hpp -- the same GEMM in 64-deep K steps (Cin, and the concat split, multiples of 64; Npad a multiple of 128): ks in {1, 3},
-// bm = 64 (four waves) or 128 (eight waves) rows x 128 channels; the same bits as conv_h2r
-void launch_conv_g64(const ConvArgs& a, int ks, int bm, int nprod, hipStream_t s);
+// 64 (four waves) or 128 (eight waves) positions x 128 channels; the same bits as conv_h2r
+void launch_conv_g64(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_t s);
 // conv_h2s32.hpp -- 7 x 7 stems at 32 raw input channels (the pose model) as a patch kernel: 4 x 32 pixels x 64 channels; the same bits as conv_h2r
 void launch_conv_h2s32(const ConvArgs& a, int nprod, hipStream_t s);
 
@@ -35,5 +38,11 @@ void launch_flow(const FlowArgs& a, int NT, size_t lds, unsigned grid, hipStream
 
 // dynamic LDS above the default limit needs hipFuncAttributeMaxDynamicSharedMemorySize: set once per (kernel, device), not per launch
 void ensure_dynamic_lds(const void* kernel, size_t bytes);
+// a convolution kernel on one workgroup per tile of the plan
+template <class Kernel>
+void launch_tiles(Kernel k, int threads, size_t lds, const ConvArgs& a, hipStream_t s) {
+    ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds);
+    hipLaunchKernelGGL(k, dim3(a.tiles_m * a.tiles_n), dim3(threads), lds, s, a);
+}
 
 }  // namespace tsnet
