@@ -12,6 +12,9 @@
  * Threading: one host thread per handle; handles are independent (one per GPU / process).
  * Errors: 0 = ok, negative = failure; tsnet_last_error(h) returns a message owned by the handle
  *         (tsnet_last_error(NULL) returns the message of the last failed tsnet_create).
+ *
+ * Additions within TSNET_ABI_VERSION 5 (new entry points only; nothing that existed changed): tsnet_face_adapt_stats,
+ * tsnet_face_adapt_apply, tsnet_smooth_keypoints -- the face loader's key-point preparation of a cross-identity pair.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -23,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
+#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
 #define TSNET_MAX_SOURCES 8
 
 enum {
@@ -249,6 +252,25 @@ int tsnet_demo_postprocess(const float* rec, int B, int H, int W, const float* g
 int tsnet_fit_face_curves(const double* keypoints, int F, double* curves);
 int tsnet_raster_face(const double* keypoints, const double* curves, int F, int h, int w, int bw, unsigned char* edges, unsigned char* bbox, void* stream);
 int tsnet_vl2ch(const float* labels, int B, int HW, int num_classes, float* out, void* stream);
+
+/* Key-point preparation of a cross-identity face pair (dataset/dataset_video_face.py FaceDatasetTest.__getitem__ :335, :355-379), HOST code on
+ * HOST doubles, once per clip, between reading the landmarks and tsnet_fit_face_curves (csrc/face_adapt.hpp).  Every operation is the
+ * reference's, in its order: the results carry the bits of its float64 arrays.
+ * tsnet_face_adapt_stats <- normalize_faces(is_ref=True) (:411-441) on the SUBJECT clip.  kp (F,68,2), (x, y) relative to the clip's crop;
+ *                      stats: 77 doubles = ref_dist_x[38] | ref_dist_y[38] | width.  Per landmark group of :418-424, ref_dist_x is the mean over all
+ *                      frames and the group's points of |point - group centroid|, ref_dist_y the same mean of |group centroid - face centre|
+ *                      (landmark 8 of the frame; counted once per point), each + 1e-3; width = max x - min x of the FIRST frame.
+ * tsnet_face_adapt_apply <- normalize_faces(is_ref=False) (:411-454) on the DRIVING clip, in place.  img_scale = stats width / (max x - min x of
+ *                      the driving clip's first frame); per group sx = ref_dist_x / mean_dist_x / img_scale, sy likewise with the driving clip's
+ *                      own means; every point becomes (p - c) * sx + (c - fc) * sy + fc (c the group's centroid in that frame, fc the frame's
+ *                      face centre before any point moved).  TSNET_ERR_ARG: F < 1, a driving (or subject) width that is zero or not finite,
+ *                      key points or statistics that are not finite.
+ * tsnet_smooth_keypoints <- the five-frame moving average of :357-379 over the frames of in (F,P,2), per point and coordinate, through the running
+ *                      sum c: out[0] = in[0], out[1] = c[2] / 3, out[2] = c[4] / 5, out[i] = (c[i+2] - c[i-3]) / 5 for 3 <= i <= F-3,
+ *                      out[F-2] = (c[F-1] - c[F-4]) / 3, out[F-1] = in[F-1].  out may be in.  TSNET_ERR_ARG: F < 5 (the reference cannot run), P < 1. */
+int tsnet_face_adapt_stats(const double* kp, int F, double* stats);
+int tsnet_face_adapt_apply(const double* stats, double* kp, int F);
+int tsnet_smooth_keypoints(const double* in, int F, int P, double* out);
 
 /* Pose clips (dataset/dataset_video_pose.py PoseDatasetTestVideo.get_image / get_smooth_lbl :489-536, test mode).
  * tsnet_fit_pose_curves <- interp_points (utils/keypoint2img_posenorm.py:490-516) of every stroke of connect_keypoints (:265-311), HOST code as

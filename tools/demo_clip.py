@@ -8,6 +8,12 @@ and the demo-shaped throughput figure (B=1, n_blocks=4, K=3, clip mode).  No pre
 reference's .pth schema {'img_enc','lbl_enc','dec','fuse_net'} (train_face.py:350-355): the frames are noise, the path is the real one.
 
     python tools/demo_clip.py --out gpurun_out/demo --frames 16
+
+Cross-identity (demo/demo_face.py with different subject and driving clips): `--clip SUBJECT --drive DRIVER` takes the source pixels and labels
+from SUBJECT and the driving labels from DRIVER's key points as the reference's loader prepares them -- adapted to the subject's face proportions
+and smoothed over the clip (raster.face_driving_keypoints), then drawn from the fractional points (rasterise(relative=True)).
+
+    python tools/demo_clip.py --out demo_out --clip test114 --drive val024 --frames 16
 """
 import argparse
 import os
@@ -46,6 +52,31 @@ def synthetic_face_keypoints(n_frames: int, seed: int = 0) -> np.ndarray:
     return np.round(out)
 
 
+GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+
+
+def clip_keypoints(clip: str):
+    """(F,68,2) key points of a real demo clip in FRAME coordinates and the clip's metadata (tests/golden/g7_raster_face.npz stores them
+    relative to the clip's crop; the landmark files hold integers, so adding the crop back is exact)"""
+    import json
+    z = np.load(os.path.join(GOLD, "g7_raster_face.npz"))
+    meta = json.loads(str(z["meta"]))["clips"][clip]
+    kp = z[f"{clip}_keypoints"].copy()
+    kp[:, :, 0] += meta["crop"][2]
+    kp[:, :, 1] += meta["crop"][0]
+    return kp, meta
+
+
+def crossid_labels(rs, subject_kps, driving_kps, size=(256, 256)):
+    """Driving labels of a cross-identity pair, the reference loader's way (dataset/dataset_video_face.py:335-398): the driving clip's key points
+    adapted to the subject's face and smoothed (host code of the library), drawn at the driving crop's resolution from the fractional points,
+    resized, one-hot.  rs: a raster.FaceRasteriser (its device and library are used throughout).  Key points in frame coordinates.
+    Returns (labels (F,2,H,W), bbox (F,H,W), driving crop, bw)."""
+    pts, crop, bw = raster.face_driving_keypoints(subject_kps, driving_kps, lib=rs.lib)
+    edges, bbox, _, _ = rs.rasterise(list(pts), crop, relative=True)
+    return rs.vl2ch(demo.resize_label(edges, size, lib=rs.lib), 2), demo.resize_label(bbox, size, lib=rs.lib), crop, bw
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="gpurun_out/demo")
@@ -57,7 +88,11 @@ def main():
     ap.add_argument("--clip", default=None, help="key points of a real demo clip (demo/face_examples/labels/<clip>, stored with the raster golden "
                     "tests/golden/g7_raster_face.npz: test114 or val024) instead of the synthetic face; the source frames' pixels are the clip's own "
                     "(tests/golden/g11_frames_<clip>.npz through the device frame loader)")
+    ap.add_argument("--drive", default=None, help="with --clip: a second demo clip whose key points drive the subject given by --clip (cross-identity); "
+                    "the driving labels are adapted to the subject's face proportions and smoothed as the reference's loader does")
     args = ap.parse_args()
+    if args.drive and not args.clip:
+        ap.error("--drive needs --clip (the subject)")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     os.makedirs(args.out, exist_ok=True)
@@ -78,11 +113,7 @@ def main():
     crop_in = None
     if args.clip:
         import json
-        z = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "g7_raster_face.npz"))
-        meta = json.loads(str(z["meta"]))["clips"][args.clip]
-        kp = z[f"{args.clip}_keypoints"].copy()                   # stored relative to the clip's crop: back to frame coordinates
-        kp[:, :, 0] += meta["crop"][2]
-        kp[:, :, 1] += meta["crop"][0]
+        kp, meta = clip_keypoints(args.clip)
         kp_all = kp
         F = min(F, kp.shape[0] - K)
         kp = kp[:F + K]
@@ -111,7 +142,7 @@ def main():
         # the real source frames: the cropped regions of the clip's demo images (tests/golden/g11_frames_<clip>.npz) through the device frame
         # loader, and the labels of the SAME frame indices, so that pixels and labels belong together
         from wacv23_tsnet_amd import frames as frames_mod
-        zf = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", f"g11_frames_{args.clip}.npz"))
+        zf = np.load(os.path.join(GOLD, f"g11_frames_{args.clip}.npz"))
         fmeta = json.loads(str(zf["meta"]))
         x0, y0, x1, y1 = fmeta["box"]
         assert [y0, y1, x0, x1] == list(crop)
@@ -123,8 +154,17 @@ def main():
         g = torch.Generator().manual_seed(1)
         src_img = [(torch.rand((1, 3, 256, 256), generator=g) * 255.0 - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1)) for _ in range(K)]
         src_lbl, src_box = lbl[:K], box[:K]
+    tar_lbl, tar_box, name = lbl[K:], box[K:], args.clip or "synthetic_face"
+    if args.drive:
+        # the whole driving clip is prepared (the moving average runs over the clip), then the first F frames drive
+        t0 = time.perf_counter()
+        tar_lbl, tar_box, dcrop, dbw = crossid_labels(rs, kp_all, clip_keypoints(args.drive)[0])
+        torch.cuda.synchronize()
+        F = min(F, tar_lbl.shape[0])
+        print(f"[demo_clip] driving labels of {args.drive} adapted to {args.clip}: {tar_lbl.shape[0]} frames (crop {dcrop}, brush {dbw}) in {(time.perf_counter() - t0) * 1e3:.2f} ms")
+        tar_lbl, tar_box, name = tar_lbl[:F], tar_box[:F], f"{args.clip}_by_{args.drive}"
     runner = demo.ClipRunner(model, src_img, [src_lbl[i:i + 1] for i in range(K)], [src_box[i:i + 1] for i in range(K)], batch=args.batch)
-    frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_face")
+    frames = runner.run(tar_lbl, tar_box, out_dir=args.out, name=name)
     print(f"[demo_clip] {demo.RESIZE_NOTE}")
     print(f"[demo_clip] {frames.shape[0]} frames written to {args.out} (crop {crop}, brush {bw}); rasterisation of {F + K} frames: {t_raster * 1e3:.2f} ms on the first call; "
           f"steady state " + ", ".join(f"{k} {v * 1e3:.2f} ms" for k, v in t_steps.items()) + f" = {sum(t_steps.values()) / (F + K) * 1e3:.3f} ms per frame")
@@ -134,8 +174,8 @@ def main():
     steps = (args.timing_frames + nb - 1) // nb
     groups = []                                                  # gathered ahead of the timed loop (the sequence of groups has period <= F)
     for i in range(min(steps, F)):
-        j = (K + (torch.arange(nb) + i * nb) % F).to(dev)
-        groups.append((lbl[j], box[j]))
+        j = ((torch.arange(nb) + i * nb) % F).to(dev)
+        groups.append((tar_lbl[j], tar_box[j]))
     for _ in range(20):
         runner.frames(*groups[0])
     torch.cuda.synchronize()

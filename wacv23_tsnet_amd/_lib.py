@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "tsnet_op_conv2d", "tsnet_op_conv2d_cat", "tsnet_op_head", "tsnet_op_instnorm_stats", "tsnet_op_norm_act", "tsnet_op_upsample2x",
     "tsnet_op_flow", "tsnet_op_flow_k", "tsnet_flow_plan", "tsnet_op_warp", "tsnet_op_warp_k", "tsnet_op_last_error", "tsnet_frame_stats", "tsnet_demo_postprocess", "tsnet_fit_face_curves", "tsnet_raster_face", "tsnet_vl2ch", "tsnet_fit_pose_curves", "tsnet_raster_pose", "tsnet_label_bbox", "tsnet_resize_pad", "tsnet_resize_label", "tsnet_bench_conv", "tsnet_debug_counters", "tsnet_linspace", "tsnet_coord_table",
     "tsnet_bicubic_taps", "tsnet_bicubic_table", "tsnet_prepare_frames",
+    "tsnet_face_adapt_stats", "tsnet_face_adapt_apply", "tsnet_smooth_keypoints",
 )
 
 
@@ -107,6 +108,10 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.tsnet_bicubic_taps.argtypes = [C.c_int, C.c_int]
         lib.tsnet_bicubic_table.argtypes = [C.c_int, C.c_int, _vp, _vp, _vp]
         lib.tsnet_prepare_frames.argtypes = [_vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_fp, _vp, _vp]
+    if hasattr(lib, "tsnet_face_adapt_stats"):   # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_face_adapt_stats.argtypes = [_vp, C.c_int, _vp]
+        lib.tsnet_face_adapt_apply.argtypes = [_vp, _vp, C.c_int]
+        lib.tsnet_smooth_keypoints.argtypes = [_vp, C.c_int, C.c_int, _vp]
     return lib
 
 

@@ -39,6 +39,7 @@
 #include "conv_plan.hpp"
 #include "kernels.hpp"
 #include "lmfit.hpp"
+#include "face_adapt.hpp"
 #include "flow_warp.hpp"
 #include "frames.hpp"
 #include "head_conv.hpp"
@@ -1577,6 +1578,25 @@ int tsnet_fit_face_curves(const double* keypoints, int F, double* curves) {
             }
             lm::fit_piece(pts, n, curves + ((size_t)f * kFaceSubEdges + e) * kCurveRec);
         }
+    OP_END
+}
+
+// key-point preparation of a cross-identity face pair (csrc/face_adapt.hpp): host arithmetic, no device work
+int tsnet_face_adapt_stats(const double* kp, int F, double* stats) {
+    OP_BEGIN
+    if (const char* err = face_adapt::stats(kp, F, stats)) throw ArgError(err);
+    OP_END
+}
+
+int tsnet_face_adapt_apply(const double* stats, double* kp, int F) {
+    OP_BEGIN
+    if (const char* err = face_adapt::apply(stats, kp, F)) throw ArgError(err);
+    OP_END
+}
+
+int tsnet_smooth_keypoints(const double* in, int F, int P, double* out) {
+    OP_BEGIN
+    if (const char* err = face_adapt::smooth(in, F, P, out)) throw ArgError(err);
     OP_END
 }
 

@@ -3,7 +3,9 @@
 (dataset/dataset_video_face.py:283-330, FaceDatasetTest.__getitem__); here the key points of a whole clip go to the device once
 and three kernels (csrc/raster.hpp) produce every frame's edge map, bounding-box mask and one-hot label.
 
-Only the crop arithmetic (a handful of integer operations per clip, dataset_video_face.py:507-518) stays on the host.
+Only the crop arithmetic (a handful of integer operations per clip, dataset_video_face.py:507-518) stays on the host, and for a
+cross-identity pair the loader's key-point preparation of the driving clip (`FaceAdapter`, `smooth_keypoints`, `face_driving_keypoints`:
+normalize_faces :411-454 and the five-frame moving average :357-379), a few hundred double operations per frame in the library's host code.
 
 Pose clips (dataset/dataset_video_pose.py:304-461, PoseDatasetTestVideo.__getitem__): `PoseRasteriser` takes the OpenPose points of a clip to the
 device once; the colour-coded skeleton (as class indices), its crop, the bounding-box mask, the nearest-neighbour resize to 128 x 256, the
@@ -50,17 +52,22 @@ class FaceRasteriser:
     def _stream(self) -> Optional[int]:
         return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
 
-    def rasterise(self, keypoints: Sequence[np.ndarray], crop: Optional[Tuple[int, int, int, int]] = None):
+    def rasterise(self, keypoints: Sequence[np.ndarray], crop: Optional[Tuple[int, int, int, int]] = None, relative: bool = False):
         """keypoints: F arrays (68,2) in frame coordinates.  crop: (min_y, max_y, min_x, max_x); default = crop_coords of the first
-        frame (fix_crop_pos=True, :294-299).  Returns (edges (F,h,w) uint8, bbox (F,h,w) uint8, crop, bw)."""
+        frame (fix_crop_pos=True, :294-299).  relative=True: the points are already relative to `crop` (which must be given) and go to the
+        fit untouched -- the way for fractional points such as face_driving_keypoints', where (a + c) - c is not a.
+        Returns (edges (F,h,w) uint8, bbox (F,h,w) uint8, crop, bw)."""
         kp = np.stack([np.asarray(k, dtype=np.float64) for k in keypoints])
         if kp.ndim != 3 or kp.shape[1:] != (68, 2):
             raise ValueError(f"expected F x 68 x 2 key points, got {kp.shape}")
+        if relative and crop is None:
+            raise ValueError("relative=True: key points relative to a crop need that crop")
         if crop is None:
             crop = crop_coords(kp[0])
         kp = kp.copy()
-        kp[:, :, 0] -= crop[2]                                     # read_keypoints (:497-505)
-        kp[:, :, 1] -= crop[0]
+        if not relative:
+            kp[:, :, 0] -= crop[2]                                 # read_keypoints (:497-505)
+            kp[:, :, 1] -= crop[0]
         h, w = crop[1] - crop[0], crop[3] - crop[2]
         bw = max(1, h // 256)                                      # :295
         F = kp.shape[0]
@@ -95,6 +102,83 @@ class FaceRasteriser:
             raise RuntimeError(f"tsnet_vl2ch failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
         self._keep_l = lab
         return out
+
+
+# ------------------------------------------------------------------------------------------------- cross-identity face pairs
+def _clip_array(kps, what: str) -> np.ndarray:
+    kp = np.ascontiguousarray(np.stack([np.asarray(k, dtype=np.float64) for k in kps]))
+    if kp.ndim != 3 or kp.shape[1:] != (68, 2):
+        raise ValueError(f"{what}: expected F x 68 x 2 key points, got {kp.shape}")
+    return kp
+
+
+class FaceAdapter:
+    """FaceDatasetTest.normalize_faces (dataset_video_face.py:411-454): `fit` measures the subject clip's face proportions (is_ref=True, :335),
+    `apply` re-scales every mirror-symmetric landmark group of a driving clip to them (is_ref=False, :355).  Key points are relative to their
+    clip's crop, as read_keypoints (:497-505) leaves them.  The arithmetic is host code of the library (csrc/face_adapt.hpp) and returns the
+    reference's float64 bits.
+
+    lib: tests pass the CPU emulation build; product code leaves it None (the in-tree HIP library, no fallback)."""
+
+    def __init__(self, lib=None):
+        self.lib = lib if lib is not None else _lib.load()
+        self._stats = None
+
+    @property
+    def stats(self) -> np.ndarray:
+        """77 doubles: ref_dist_x[38] | ref_dist_y[38] | the subject's face width in its first frame"""
+        if self._stats is None:
+            raise RuntimeError("FaceAdapter: fit() a subject clip first")
+        return self._stats.copy()
+
+    def fit(self, subject_kps_rel) -> "FaceAdapter":
+        kp = _clip_array(subject_kps_rel, "FaceAdapter.fit")
+        stats = np.empty(77, dtype=np.float64)
+        rc = self.lib.tsnet_face_adapt_stats(kp.ctypes.data, kp.shape[0], stats.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"tsnet_face_adapt_stats failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._stats = stats
+        return self
+
+    def apply(self, driving_kps_rel) -> np.ndarray:
+        """-> (F,68,2) float64, a new array: the driving clip with the subject's proportions"""
+        if self._stats is None:
+            raise RuntimeError("FaceAdapter: fit() a subject clip first")
+        kp = _clip_array(driving_kps_rel, "FaceAdapter.apply").copy()
+        rc = self.lib.tsnet_face_adapt_apply(self._stats.ctypes.data, kp.ctypes.data, kp.shape[0])
+        if rc != 0:
+            raise RuntimeError(f"tsnet_face_adapt_apply failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        return kp
+
+
+def smooth_keypoints(kps, lib=None) -> np.ndarray:
+    """The loader's five-frame moving average of a driving clip's key points over its frames (dataset_video_face.py:357-379): (F,P,2) -> a new
+    (F,P,2) float64 array, the reference's bits.  F >= 5."""
+    lib = lib if lib is not None else _lib.load()
+    kp = np.ascontiguousarray(np.stack([np.asarray(k, dtype=np.float64) for k in kps]))
+    if kp.ndim != 3 or kp.shape[2] != 2:
+        raise ValueError(f"expected F x P x 2 key points, got {kp.shape}")
+    out = np.empty_like(kp)
+    rc = lib.tsnet_smooth_keypoints(kp.ctypes.data, kp.shape[0], kp.shape[1], out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"tsnet_smooth_keypoints failed ({rc}): {lib.tsnet_op_last_error().decode()}")
+    return out
+
+
+def face_driving_keypoints(subject_kps, driving_kps, lib=None):
+    """The driving key points of a cross-identity pair in the order FaceDatasetTest.__getitem__ prepares them (fix_crop_pos=True, as the demo
+    runs): each clip is cropped by the crop of its own first frame (:299-308, :344-353), the driving clip is adapted to the subject's face
+    proportions (:335, :355) and then smoothed over its frames (:357-379); the subject clip is neither adapted nor smoothed.
+    subject_kps, driving_kps: F arrays (68,2) in frame coordinates, as `read_keypoints` returns them.
+    Returns (points (F,68,2) float64 relative to the driving crop, driving crop (min_y, max_y, min_x, max_x), bw): what
+    `FaceRasteriser.rasterise(points, crop, relative=True)` takes."""
+    sub, drv = _clip_array(subject_kps, "subject").copy(), _clip_array(driving_kps, "driving").copy()
+    sub_crop, crop = crop_coords(sub[0]), crop_coords(drv[0])
+    for kp, c in ((sub, sub_crop), (drv, crop)):
+        kp[:, :, 0] -= c[2]                                        # read_keypoints (:497-505)
+        kp[:, :, 1] -= c[0]
+    points = smooth_keypoints(FaceAdapter(lib).fit(sub).apply(drv), lib)
+    return points, crop, max(1, (crop[1] - crop[0]) // 256)       # :347
 
 
 # ---------------------------------------------------------------------------------------------------------------- pose clips
