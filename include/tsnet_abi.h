@@ -58,8 +58,14 @@ typedef struct tsnet_cfg {
                           *     one MFMA product, fp32 accumulate, fp32 InstanceNorm / softmax / RGB head.  Own tolerance.
                           * 2 = mode 1 + bf16 STORAGE of the large convolution-to-convolution activations (the encoders' 256^2 .. 64^2 maps,
                           *     the decoder's up-convolution outputs and upsampled inputs): statistics from the fp32 accumulators, the
-                          *     stored tensor rounded once, widened exactly by its consumer. */
+                          *     stored tensor rounded once, widened exactly by its consumer.
+                          * 3 = fp16 operands: every convolution input and weight is scaled by a power of two (the bounds and per-layer weight
+                          *     scales of mode 0) and rounded to fp16 -- 11 significant bits against bf16's 8 -- one MFMA product at the cost of
+                          *     mode 1's, fp32 accumulate and fp32 storage; everything else as in mode 1.  Own tolerance. */
 } tsnet_cfg;
+
+/* tsnet_op_conv2d / tsnet_op_conv2d_cat `nprod`: ONE product on one fp16 plane rne16(operand * 2^s) -- the arithmetic of operand_mode = 3 */
+#define TSNET_NPROD_F16 16
 
 /* ---- lifecycle ---------------------------------------------------------------------------
  * tsnet_create          <- TSNet(...) construction                       (model/TSNet.py:204-264)
@@ -161,14 +167,16 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  *   y (N,Ho,Wo,Cout).  ksize 1, 3 or 7; pad_mode 0 = zero, 1 = reflect.  in_alpha / in_beta (N*Cin each) or NULL: the producer's
  *   nn.InstanceNorm2d (+ nn.ReLU when in_relu) applied while the operand tile is staged, x' = max(alpha*x + beta, 0); zero padding pads x'.
  *   bound = an upper bound of |operand| after that transform (it fixes the power-of-two operand scale of the fp16 x 2 split).
- *   nprod = 3 (lo*hi, hi*lo, hi*hi), 4 (+ lo*lo; 3x3 / stride-1 patch kernel only) or 1 (bf16 operands, tsnet_cfg.operand_mode = 1).
+ *   nprod = 3 (lo*hi, hi*lo, hi*hi), 4 (+ lo*lo; 3x3 / stride-1 patch kernel only), 1 (bf16 operands, tsnet_cfg.operand_mode = 1; `bound`
+ *   is not used) or TSNET_NPROD_F16 = 16 (one fp16 plane, tsnet_cfg.operand_mode = 3: `bound` fixes the operand scale as for nprod = 3; every
+ *   kernel and tile of nprod = 1 except kernel = 3, and no deep schedule 12128).
  *   kernel: 0 = the kernel the forward runs this layer on at this frame size (patch kernels of conv_h2.hpp where the output splits into
  *   4 x 32 rectangles: 3x3 / stride 1, 3x3 / stride 2 / zero pad, 7x7 stem with 8 input channels; the general implicit GEMM of conv_h2r.hpp
  *   elsewhere), 1 = the general kernel, 2 = the patch kernel (error if the layer has none), 3 = the Winograd F(2,3)-along-x form of a
  *   3x3 / stride-1 / pad-1 layer on frames of whole 4 x 32 tiles (conv_w1.hpp: the kernel the forward runs its ResnetBlock / FuseNet / first
  *   up-convolution layers on; the op packs the transformed filters itself; `tile` = tiles per workgroup, 1, 2 or 3, 0 = the launcher's choice).
- *   tile: 0 = the launcher's choice; patch 3x3 / stride 1: 32, 64, 128 (4-row tiles), 2128 (2 rows x 128), 3128 (nprod = 1 only: 4 rows x 128
- *   with the four waves side by side, the bf16 modes' own tile), 20032 / 20064 (two-K-group tiles); patch 3x3 / stride 2: 64, 128 (4 rows)
+ *   tile: 0 = the launcher's choice; patch 3x3 / stride 1: 32, 64, 128 (4-row tiles), 2128 (2 rows x 128), 3128 (nprod = 1 / 16 only: 4 rows x 128
+ *   with the four waves side by side, the one-product modes' own tile), 20032 / 20064 (two-K-group tiles); patch 3x3 / stride 2: 64, 128 (4 rows)
  *   or 2128 (2 rows x 128: the forward's shape; 12128: its deep schedule, what a launch of at most two workgroups per CU runs); general kernel: 64 or 128 (16-deep steps, conv_h2r.hpp), 3064 / 3128 (64-deep steps,
  *   conv_g64.hpp, 64 / 128 rows: where the layer allows, the forward's choice).
  *   All one-group tiles of one kernel produce identical bits, and so do the two two-group tiles among themselves (tested); the two-group

@@ -1,7 +1,12 @@
-"""GPU box: the two bf16 modes side by side -- operand_mode 1 (bf16 operands) and 2 (+ bf16 storage of the large activations) -- at the
-shapes of BASELINE.json configs[2] (n_blocks = 4, bs = 8, 256^2) and configs[4] (512^2, K = 5, one pair per GPU): frames/s and, with
---report, the distances to the oracle that rounds at the same points (tests/helpers.bf16_mode_report).
-usage: bf16_modes.py [--report]"""
+"""GPU box: the one-product modes side by side -- operand_mode 1 (bf16 operands), 2 (+ bf16 storage of the large activations) and 3 (fp16
+operands) -- at the shapes of BASELINE.json configs[2] (n_blocks = 4, bs = 8, 256^2) and configs[4] (512^2, K = 5, one pair per GPU):
+frames/s and, with --report, for the modes bf16s and fp16 the distances to the oracle that rounds at the same points
+(tests/helpers.bf16_mode_report; for fp16 the oracle's rounding is tests/fp16_cases.r16; the bf16 mode's are the GPU tests').
+--repeats 1 (the default): one engine at a time, one measurement per mode, `ms_per_step` is that measurement.
+--repeats R > 1: the engines of all modes of a shape are alive together (memory: R does not matter, the number of modes does) and timed R
+times each, the modes interleaved; `ms_repeats` lists every repeat -- their spread is what a difference between two modes has to exceed --
+and `ms_per_step` is the BEST of them.
+usage: bf16_modes.py [--report] [--modes bf16,bf16s,fp16] [--repeats R]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -9,22 +14,48 @@ import torch
 from wacv23_tsnet_amd import synth
 from wacv23_tsnet_amd.engine import TSNetEngine
 
+
+def _opt(name, default):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+
+
+MODES = _opt("--modes", "bf16,bf16s,fp16").split(",")
+REPEATS = int(_opt("--repeats", "1"))
 CASES = {"cfg2": (dict(label_nc=2, n_blocks=4, n_downsampling=3, n_source=3), 8, 256, 256), "cfg4": (dict(label_nc=2, n_blocks=0, n_downsampling=3, n_source=5), 1, 512, 512)}
 out = {}
 for tag, (kw, B, H, W) in CASES.items():
-    for mode in ("bf16", "bf16s"):
+    inp = [[t.cuda() for t in x] if isinstance(x, list) else x.cuda() for x in synth.inputs(kw["n_source"], 2, B, H, W, seed=3)]
+    def make(mode):
         eng = TSNetEngine(height=H, width=W, max_batch=B, operands=mode, **kw)
         eng.load_state_dict(synth.state_dict(eng.param_shapes(), seed=0)); eng.finalize("cuda")
-        inp = [[t.cuda() for t in x] if isinstance(x, list) else x.cuda() for x in synth.inputs(kw["n_source"], 2, B, H, W, seed=3)]
+        return eng
+
+    def measure(eng):
         for _ in range(5): eng.forward(*inp)
         torch.cuda.synchronize(); n = 30; t0 = time.perf_counter()
         for _ in range(n): eng.forward(*inp)
-        torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / n
-        out[f"{tag}_{mode}"] = {"ms_per_step": round(dt * 1e3, 3), "frames_per_s": round(B / dt, 1)}
-        eng.close(); del eng; torch.cuda.empty_cache()
+        torch.cuda.synchronize(); return (time.perf_counter() - t0) / n * 1e3
+
+    if REPEATS == 1:
+        for mode in MODES:
+            eng = make(mode); ms = measure(eng)
+            out[f"{tag}_{mode}"] = {"ms_per_step": round(ms, 3), "frames_per_s": round(B / ms * 1e3, 1)}
+            eng.close(); del eng; torch.cuda.empty_cache()
+        continue
+    engs = {mode: make(mode) for mode in MODES}
+    ms = {mode: [] for mode in MODES}
+    for _ in range(REPEATS):
+        for mode in MODES:
+            ms[mode].append(measure(engs[mode]))
+    for mode in MODES:
+        best = min(ms[mode])
+        out[f"{tag}_{mode}"] = {"ms_per_step": round(best, 3), "frames_per_s": round(B / best * 1e3, 1), "ms_repeats": [round(v, 3) for v in ms[mode]]}
+        engs[mode].close()
+    del engs; torch.cuda.empty_cache()
 print(json.dumps(out))
 if "--report" in sys.argv:
     import helpers as Hh
+    import fp16_cases as fc
     from oracle import tsnet_oracle as O
     torch.set_num_threads(min(16, torch.get_num_threads()))
     for tag, cfg, B, H, W, ws, isd, mask in (("cfg2", O.TSNetConfig(label_nc=2, n_blocks=4, n_source=3), 8, 256, 256, 21, 22, "box"),
@@ -33,8 +64,16 @@ if "--report" in sys.argv:
                                              ("cfg4", O.TSNetConfig(label_nc=2, n_blocks=0, n_source=5), 1, 512, 512, 35, 36, "bernoulli")):
         sd = O.synth_state_dict(cfg, seed=ws, bias_std=0.02)
         inp = O.synth_inputs(cfg, B, H, W, seed=isd, mask_mode=mask)
-        eng = Hh.make_engine(cfg, sd, H, W, B, "cuda", operands="bf16s")
-        rec, _ = Hh.run_engine(eng, inp, "cuda")
-        r = Hh.bf16_mode_report(eng, cfg, sd, inp, rec, B, "cuda", mode="bf16s")
-        eng.close()
-        print(f"[{tag} bf16s w{ws} i{isd}] " + " ".join(f"{k}={v:.3e}" for k, v in r.items()), flush=True)
+        for mode in (m for m in MODES if m != "bf16"):
+            eng = Hh.make_engine(cfg, sd, H, W, B, "cuda", operands=mode)
+            rec, _ = Hh.run_engine(eng, inp, "cuda")
+            if mode == "fp16":           # the oracle's operand rounding replaced by fp16 after a power-of-two scale, as the GPU tests do
+                keep, O._r = O._r, fc.r16
+                try:
+                    r = Hh.bf16_mode_report(eng, cfg, sd, inp, rec, B, "cuda", mode="bf16")
+                finally:
+                    O._r = keep
+            else:
+                r = Hh.bf16_mode_report(eng, cfg, sd, inp, rec, B, "cuda", mode=mode)
+            eng.close()
+            print(f"[{tag} {mode} w{ws} i{isd}] " + " ".join(f"{k}={v:.3e}" for k, v in r.items()), flush=True)

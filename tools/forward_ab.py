@@ -16,7 +16,7 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--knob", type=int, default=0)
 ap.add_argument("--values", default="3,1")
-ap.add_argument("--operands", default="fp32", help="fp32 | bf16 | bf16s (tsnet_cfg.operand_mode)")
+ap.add_argument("--operands", default="fp32", help="fp32 | bf16 | bf16s | fp16 (tsnet_cfg.operand_mode)")
 ap.add_argument("--lib2", default=None)
 ap.add_argument("--reps", type=int, default=6, help="engine instantiations per build (--lib2)")
 a = ap.parse_args()

@@ -9,6 +9,9 @@
 // construction (an InstanceNorm output is <= sqrt(HW-1) in magnitude) or their producer publishes max |x| per image; weights are scaled
 // per layer from their maximum.  The epilogue multiplies by 2^-(sa+sw) (exact) before bias, statistics and store.
 // bf16-operand mode (tsnet_cfg.operand_mode = 1, BASELINE.json configs[2] / [4]): ONE bf16 plane per operand, one product, no scales.
+// fp16-operand mode (tsnet_cfg.operand_mode = 3): ONE fp16 plane per operand -- the hi plane above and nothing else, rne16(x*s) with the
+// same power-of-two scales -- one product on v_mfma_f32_32x32x16_f16 (the cycles of the bf16 form), the same epilogue un-scale: the bf16
+// mode's schedule with 11 significant bits per operand instead of 8.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +23,11 @@ struct alignas(16) F4 { float v[4]; };
 constexpr unsigned kOOB = 0x80000000u;                    // voffset of a lane that must read zeros (tensors are < 2 GiB, checked on the host)
 constexpr int kPatchCols = 32;                            // a patch tile is PR x 32 output pixels of one image (PR = 2 or 4 rows)
 constexpr int kPatchRows = 4;
+
+// The kernels' NPROD template argument: 3 or 4 products on fp16 x 2 operands, or ONE product on a single plane -- 1 = a bf16 plane of the
+// operand itself, 16 = an fp16 plane of the scaled operand (TSNET_NPROD_F16 in include/tsnet_abi.h).
+constexpr int kNprodF16 = 16;
+constexpr bool one_product(int nprod) { return nprod == 1 || nprod == kNprodF16; }
 
 // ---- hardware hooks (tests/emu predefines these names to run the kernels on the CPU) ----
 #ifndef TSNET_BUF_LOAD16
@@ -148,6 +156,28 @@ __device__ __forceinline__ unsigned tsnet_cvt_pk_bf16(float a, float b) {
 #define TSNET_CVT_PK_BF16(a, b) tsnet_cvt_pk_bf16((a), (b))
 #endif
 
+// two floats -> one dword of two fp16 (round to nearest even), low half = a: the fp16-operand mode's staging conversion, one instruction
+// per pair like the bf16 one.  The host form (the CPU emulation of the kernels) gives the same bits for finite inputs.
+#ifndef TSNET_CVT_PK_F16
+__device__ __forceinline__ unsigned tsnet_cvt_pk_f16(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned r;
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    const _Float16 h0 = (_Float16)a, h1 = (_Float16)b;
+    return (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+#endif
+}
+#define TSNET_CVT_PK_F16(a, b) tsnet_cvt_pk_f16((a), (b))
+#endif
+// the single operand plane of a one-product kernel: two values -> one dword of bf16 or (F16) fp16
+template <bool F16>
+__device__ __forceinline__ unsigned cvt_pk_one(float a, float b) {
+    if constexpr (F16) return TSNET_CVT_PK_F16(a, b);
+    else return TSNET_CVT_PK_BF16(a, b);
+}
+
 // max |v| of the workgroup's values -> ONE atomic per workgroup (atomics on one address serialise at ~12 ns each; non-negative
 // floats order like their bit patterns, and a max is order-independent: deterministic).  Every thread of the workgroup must call it.
 __device__ __forceinline__ void tsnet_publish_amax(unsigned* slot, float m) {
@@ -173,7 +203,7 @@ struct ConvArgs {
     int in_relu;
     float in_scale, in_unscale;               // 2^sa, 2^-sa from the host's a-priori bound, or:
     const unsigned* in_amax; float in_bound_add;   // in_amax[image] = float bits of max |x| published by x's producer; bound = that + in_bound_add
-    const unsigned short* w;   // operand planes [NPL][K/16][Npad][2 swizzled octets][8] of w * 2^sw (fp16 hi, lo) or of w (one bf16 plane)
+    const unsigned short* w;   // operand planes [NPL][K/16][Npad][2 swizzled octets][8] of w * 2^sw (fp16 hi, lo; or hi alone) or of w (one bf16 plane)
     const float* w_unscale;    // device scalar 2^-sw (lives in the packed weight buffer: replicas receive it with the broadcast), or null
     const float* bias;
     float* y;                  // (N,Ho,Wo,Cout) fp32 NHWC, raw convolution output
@@ -218,7 +248,10 @@ __device__ __forceinline__ void load_x_octet(const tsnet_brsrc_t& rs, bool xb16,
     }
 }
 
-// power-of-two operand scale for |x| <= bound: |x * 2^sa| <= 2^15 (the host's h2_scale_log2, engine.cpp)
+// power-of-two operand scale for |x| <= bound: |x * 2^sa| <= 2^15 (the host's h2_scale_log2, engine.cpp).  |sa| <= 24 for EVERY operand
+// kind: the host widens the limit to 64 for the one-plane fp16 kind with an a-priori bound (operator calls scaled far outside fp16's
+// range), this path does not -- it serves the forward's layers whose producer publishes max |y|, activations of order 1 (2^-9 .. 2^39
+// scale exactly; beyond that the clamp holds the scale and the plane under- or overflows as the split's does).
 __device__ __forceinline__ void h2_device_scale(const unsigned* amax, float add, float& scale, float& unscale) {
     const float bound = __builtin_bit_cast(float, __hip_atomic_load(amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + add;
     int e = 0;
@@ -248,13 +281,14 @@ __device__ __forceinline__ void split_h2_octet(const F4& x0, const F4& x1, F4& H
     for (int e = 0; e < 4; ++e) { H.v[e] = __builtin_bit_cast(float, hw[e]); L.v[e] = __builtin_bit_cast(float, lw[e]); }
 }
 
-// eight consecutive channels -> one octet of bf16 (round to nearest even): the bf16-operand mode's single plane
-__device__ __forceinline__ void bf16_octet(const F4& x0, const F4& x1, F4& H) {
+// eight consecutive channels -> one octet of bf16 or (F16: already scaled) fp16, round to nearest even: the single plane of the one-product modes
+template <bool F16 = false>
+__device__ __forceinline__ void one_plane_octet(const F4& x0, const F4& x1, F4& H) {
     unsigned hw[4];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-        hw[e] = TSNET_CVT_PK_BF16(x0.v[2 * e], x0.v[2 * e + 1]);
-        hw[2 + e] = TSNET_CVT_PK_BF16(x1.v[2 * e], x1.v[2 * e + 1]);
+        hw[e] = cvt_pk_one<F16>(x0.v[2 * e], x0.v[2 * e + 1]);
+        hw[2 + e] = cvt_pk_one<F16>(x1.v[2 * e], x1.v[2 * e + 1]);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) H.v[e] = __builtin_bit_cast(float, hw[e]);

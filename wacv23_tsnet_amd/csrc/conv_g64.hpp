@@ -29,8 +29,9 @@ void conv_g64_kernel(ConvArgs a) {
     constexpr int MT = 2, NTL = 1;                                   // wave tile 64 rows x 32 channels
     constexpr int RS = 2;                                            // row slots per thread: rows r and r + BM / 2, eight lanes per row
     static_assert(BM == 64 || BM == 128, "64 or 128 rows");
-    static_assert(NPROD == 1 || NPROD == 3, "one (bf16 operands) or three products");
-    constexpr int NPL = NPROD == 1 ? 1 : 2;
+    constexpr bool ONEP = one_product(NPROD), F16P = NPROD == kNprodF16;
+    static_assert(ONEP || NPROD == 3, "one (a bf16 or an fp16 plane) or three products");
+    constexpr int NPL = ONEP ? 1 : 2;
     constexpr int GP = g64_group_pitch(BM), PLANE = g64_plane_bytes(BM), STAGE = NPL * PLANE;
     constexpr int OFF_TAB = 2 * STAGE + 64;                          // (alpha*s, beta*s) of the tile's image behind the two stages
 
@@ -145,9 +146,9 @@ void conv_g64_kernel(ConvArgs a) {
                     for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaxf(ar[s][h].v[e] * in_scale, relu_floor);
                 }
                 unsigned char* dst = base + lds_w[s] + h * 2 * GP;
-                if (NPROD == 1) {
+                if (ONEP) {
                     uint2 w;
-                    w.x = TSNET_CVT_PK_BF16(t[0], t[1]); w.y = TSNET_CVT_PK_BF16(t[2], t[3]);
+                    w.x = cvt_pk_one<F16P>(t[0], t[1]); w.y = cvt_pk_one<F16P>(t[2], t[3]);
                     *reinterpret_cast<uint2*>(dst) = w;
                 } else {
                     unsigned h0, l0, h1, l1;
@@ -213,7 +214,7 @@ void conv_g64_kernel(ConvArgs a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             frag_a(stage, g);
-            if (NPROD == 1) {
+            if (ONEP) {
                 product(g, 0, 0, g == 0);
             } else {
                 product(g, 1, 0, g == 0);                            // lo * hi; chains of 4 k-groups counted from k = 0 (conv_h2r's association)

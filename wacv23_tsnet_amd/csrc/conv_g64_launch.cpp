@@ -11,7 +11,7 @@ namespace {
 
 template <int KS, int BM, int NPROD>
 void go(const ConvArgs& a, hipStream_t s) {
-    launch_tiles(a.in_alpha ? conv_g64_kernel<KS, BM, NPROD, true> : conv_g64_kernel<KS, BM, NPROD, false>, BM * 4, (size_t)g64_lds_bytes(BM, NPROD == 1 ? 1 : 2, a.Cin), a, s);
+    launch_tiles(a.in_alpha ? conv_g64_kernel<KS, BM, NPROD, true> : conv_g64_kernel<KS, BM, NPROD, false>, BM * 4, (size_t)g64_lds_bytes(BM, one_product(NPROD) ? 1 : 2, a.Cin), a, s);
 }
 
 template <int NPROD>
@@ -26,11 +26,12 @@ void go_np(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
 }  // namespace
 
 void launch_conv_g64(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_t s) {
-    nprod == 3 ? go_np<3>(a, p, s) : go_np<1>(a, p, s);
+    nprod == 3 ? go_np<3>(a, p, s) : (nprod == kNprodF16 ? go_np<kNprodF16>(a, p, s) : go_np<1>(a, p, s));
 }
 
 void launch_conv_h2s32(const ConvArgs& a, int nprod, hipStream_t s) {
     if (nprod == 3) launch_tiles(conv_h2s32_kernel<3>, 256, (size_t)h2s32_lds_bytes(2), a, s);
+    else if (nprod == kNprodF16) launch_tiles(conv_h2s32_kernel<kNprodF16>, 256, (size_t)h2s32_lds_bytes(1), a, s);
     else launch_tiles(conv_h2s32_kernel<1>, 256, (size_t)h2s32_lds_bytes(1), a, s);
 }
 

@@ -24,7 +24,8 @@
 
 namespace tsnet {
 
-// NPROD = 3: lo*hi, hi*lo, hi*hi;  NPROD = 4: lo*lo first (kept for the accuracy comparison in the op tests);  NPROD = 1: bf16 operands.
+// NPROD = 3: lo*hi, hi*lo, hi*hi;  NPROD = 4: lo*lo first (kept for the accuracy comparison in the op tests);  NPROD = 1: bf16 operands;
+// NPROD = 16 (kNprodF16): one fp16 plane of the scaled operand -- the schedule of NPROD = 1, the scales of NPROD = 3.
 // Tile shapes (PR rows x BN channels, waves WARPS_M x WARPS_N, wave tile (PR/WARPS_M * 32) x (BN/WARPS_N)):
 //   4 x 64  (2 x 2, 64 x 32)   768 tiles = three per CU on the ResnetBlock layers at the headline batch
 //   4 x 128 (2 x 2, 64 x 64)   half the LDS / L1 bytes per MFMA, two workgroups per CU (FuseNet, decoder)
@@ -41,11 +42,12 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
     constexpr int BM = PR * kPatchCols;
     constexpr int NW = WARPS_M * WARPS_N;
     static_assert(NW == 4, "four waves: patch blocks are dealt w, w+4");
-    static_assert(NPROD == 1 || NPROD == 3 || NPROD == 4, "one (bf16 operands), three or four products");
-    constexpr int NPL = NPROD == 1 ? 1 : 2;                          // operand planes
+    static_assert(one_product(NPROD) || NPROD == 3 || NPROD == 4, "one (a bf16 or an fp16 plane), three or four products");
+    constexpr bool ONEP = one_product(NPROD), F16P = NPROD == kNprodF16;
+    constexpr int NPL = ONEP ? 1 : 2;                                // operand planes
     constexpr bool DEEP = (OPT & 8) != 0;
     constexpr int BD = DEEP ? 9 : ((OPT & 32) ? 6 : 3);              // weight register sets: fragments are fetched BD - 1 steps ahead (3, 6, 9: divisors of the 18 steps of a slab pair)
-    constexpr bool ONE_LEVEL = NPROD == 1;                            // bf16 operands (2^-9 each): one fp32 chain over all of K -- the second
+    constexpr bool ONE_LEVEL = ONEP;                                 // one 16-bit plane (2^-9 / 2^-12 each): one fp32 chain over all of K -- the second
                                                                      // level buys nothing below the operand rounding and costs 16 VGPRs per tile
     constexpr bool ZPAD_KEEP = (OPT & 1) != 0;
     constexpr int CH = (OPT & 2) ? 1 : ((OPT & 4) ? 4 : 2);          // slabs per accumulation chain
@@ -140,8 +142,8 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         // a block past the patch does not exist: its wave writes into the sink (wave-uniform select, no branch)
         unsigned char* dst = gbase + (b < PBLK ? par * PATCH_BYTES + oct * REGION + b * 512 : OFF_SINK + oct * 512) + (lane & 31) * 16;
         F4 Hh, Ll;
-        if (NPROD == 1) {
-            bf16_octet(t[0], t[1], Hh);
+        if (ONEP) {
+            one_plane_octet<F16P>(t[0], t[1], Hh);
             *reinterpret_cast<F4*>(dst) = Hh;
         } else {
             split_h2_octet(t[0], t[1], Hh, Ll);
@@ -230,8 +232,8 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         if (s == 0 && !(HABL & 1)) stage_load_x(cc + 1, 0);
         if (s == (DEEP ? 1 : 3) && !(HABL & 1)) stage_load_x(cc + 1, 1);
         const int SB = (par * 9 + s) % BD;
-        if (NPROD == 1) {
-            product(kx, ky, SB, 0, 0, fresh);                        // bf16 * bf16
+        if (ONEP) {
+            product(kx, ky, SB, 0, 0, fresh);                        // the one plane
         } else {
             if (NPROD == 4) product(kx, ky, SB, NPL - 1, NPL - 1, fresh);    // lo * lo
             product(kx, ky, SB, NPL - 1, 0, fresh && NPROD == 3);    // lo * hi
@@ -337,7 +339,7 @@ constexpr int h2_lds_bytes(int PR, int Cin, int KG = 1) { return KG * (2 * 2 * 2
 
 // workgroups per CU the tile is built for
 template <int PR, int BN, int WARPS_M, int WARPS_N, int NPROD, int OPT>
-constexpr int h2_wgs_per_cu() { return (OPT & 16) ? 1 : ((BN / WARPS_N) * (PR / WARPS_M) * ((OPT & 8) ? 2 : 1) <= (NPROD == 1 ? 128 : 64) ? ((OPT & 64) ? 4 : 3) : 2); }
+constexpr int h2_wgs_per_cu() { return (OPT & 16) ? 1 : ((BN / WARPS_N) * (PR / WARPS_M) * ((OPT & 8) ? 2 : 1) <= (one_product(NPROD) ? 128 : 64) ? ((OPT & 64) ? 4 : 3) : 2); }
 
 template <int PR, int BN, int WARPS_M, int WARPS_N, int NPROD, bool AFFINE, int HABL = 0, int OPT = 0>
 __global__ __launch_bounds__((OPT & 16) ? 512 : 256, (h2_wgs_per_cu<PR, BN, WARPS_M, WARPS_N, NPROD, OPT>()))
@@ -361,10 +363,11 @@ void conv_h2_kernel(ConvArgs a) {
 template <int NPROD>
 __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_raw, const int tile_m, const int n0) {
     constexpr int BN = 64, WARPS_M = 2, WARPS_N = 2, MT = 2, NTL = 1;
-    constexpr int NPL = NPROD == 1 ? 1 : 2;
+    constexpr bool ONEP = one_product(NPROD), F16P = NPROD == kNprodF16;
+    constexpr int NPL = ONEP ? 1 : 2;
     constexpr int PC = kPatchCols + 6, PR = kPatchRows + 6, PP = PR * PC;       // 38 x 10 = 380 patch pixels
     constexpr int PLANE_S = 384 * 16;                                             // one plane: a 16-byte octet per pixel slot
-    static_assert(NPROD == 1 || NPROD == 3, "one (bf16 operands) or three products");
+    static_assert(one_product(NPROD) || NPROD == 3, "one (a bf16 or an fp16 plane) or three products");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -411,8 +414,8 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
         for (int e = 0; e < 4; ++e) { x0.v[e] *= in_scale; x1.v[e] *= in_scale; }
         if (pp < 384) {                                               // slots 380..383 hold zeros (never read, kept finite)
             F4 Hh, Ll;
-            if (NPROD == 1) {
-                bf16_octet(x0, x1, Hh);
+            if (ONEP) {
+                one_plane_octet<F16P>(x0, x1, Hh);
                 *reinterpret_cast<F4*>(smem_raw + pp * 16) = Hh;
             } else {
                 split_h2_octet(x0, x1, Hh, Ll);
@@ -469,7 +472,7 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
         load_b((j + 2) % 3, st + 2);
         load_a((j + 1) & 1, st + 1 < 25 ? st + 1 : 24);
         const int SA = j & 1, SB = j % 3;
-        if (NPROD == 1) {
+        if (ONEP) {
             product(SA, SB, 0, 0, j == 0);
         } else {
             product(SA, SB, 1, 0, j == 0);                            // lo * hi
@@ -540,8 +543,9 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
     constexpr int BM = PR * kPatchCols;
     constexpr int WARPS_M = PR / 2, WARPS_N = NWV / WARPS_M;
     static_assert((NWV == 4 || NWV == 8) && (PR == 2 || PR == 4), "four or eight waves, two output rows per wave");
-    static_assert(NPROD == 1 || NPROD == 3, "one (bf16 operands) or three products");
-    constexpr int NPL = NPROD == 1 ? 1 : 2;
+    static_assert(one_product(NPROD) || NPROD == 3, "one (a bf16 or an fp16 plane) or three products");
+    constexpr bool ONEP = one_product(NPROD), F16P = NPROD == kNprodF16;
+    constexpr int NPL = ONEP ? 1 : 2;
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
     constexpr int MT = WM / 32, NTL = WN / 32;
     static_assert(MT == 2 && NTL == 1, "wave tile 64 x 32");
@@ -624,8 +628,8 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
         const bool real = so >= 0;
         unsigned char* dst = smem_raw + (real ? (cn & 1) * PATCH_BYTES + oct * REGION + so : OFF_SINK + (lane & 63) * 16);
         F4 Hh, Ll;
-        if (NPROD == 1) {
-            bf16_octet(t[0], t[1], Hh);
+        if (ONEP) {
+            one_plane_octet<F16P>(t[0], t[1], Hh);
             *reinterpret_cast<F4*>(dst) = Hh;
         } else {
             split_h2_octet(t[0], t[1], Hh, Ll);
@@ -704,7 +708,7 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
             if (t == 6) stage_load_x(cc + 1, 2);
         }
         const int SB = t % BD;
-        if (NPROD == 1) {
+        if (ONEP) {
             product(SA, SB, 0, 0, fresh);
         } else {
             product(SA, SB, NPL - 1, 0, fresh);                      // lo * hi

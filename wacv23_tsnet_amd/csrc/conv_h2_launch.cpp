@@ -42,7 +42,7 @@ void go_h2(const ConvArgs& a, hipStream_t s) {
     else go_h2_k<PR, BN, WM, WN, NPROD, true, HABL, OPT | 1>(a, lds, 256 * KG, s);
 }
 
-// the one-group tiles, 1 or 3 products (conv_plan.hpp plan_conv, case H2, lists the same tiles)
+// the one-group tiles, one product (a bf16 or an fp16 plane) or three (conv_plan.hpp plan_conv, case H2, lists the same tiles)
 template <int NPROD>
 void go_h2_shape(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     const int pr = p.rows, bn = p.width;
@@ -50,8 +50,8 @@ void go_h2_shape(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     if (pr == 4 && bn == 64) return go_h2<4, 64, 2, 2, NPROD>(a, s);
     if (pr == 4 && bn == 128 && !p.side_by_side) return go_h2<4, 128, 2, 2, NPROD>(a, s);
     if (pr == 2 && bn == 128) return go_h2<2, 128, 1, 4, NPROD>(a, s);
-    if constexpr (NPROD == 1) {                      // 4 rows x 128 channels with the four waves side by side (1 x 4, wave tile 128 x 32): every weight fragment is loaded once per workgroup
-        if (pr == 4 && bn == 128) return go_h2<4, 128, 1, 4, 1>(a, s);
+    if constexpr (one_product(NPROD)) {              // 4 rows x 128 channels with the four waves side by side (1 x 4, wave tile 128 x 32): every weight fragment is loaded once per workgroup
+        if (pr == 4 && bn == 128) return go_h2<4, 128, 1, 4, NPROD>(a, s);
     }
     plan_not_built(p, NPROD);
 }
@@ -66,8 +66,8 @@ void go_h2d(const ConvArgs& a, hipStream_t s) {
 void launch_conv_h2(const ConvArgs& a, const ConvPlan& p, int nprod, int abl, int opt, hipStream_t s) {
     const int pr = p.rows, bn = p.width;
     if (p.sched == ConvSched::TwoGroups) {           // single-frame launches: deep prefetch + two K groups, eight waves (conv_h2.hpp); no experiment variants
-        if (pr == 4 && bn == 32) return nprod == 3 ? go_h2<4, 32, 4, 1, 3, 0, 24>(a, s) : go_h2<4, 32, 4, 1, 1, 0, 24>(a, s);
-        if (pr == 4 && bn == 64) return nprod == 3 ? go_h2<4, 64, 2, 2, 3, 0, 24>(a, s) : go_h2<4, 64, 2, 2, 1, 0, 24>(a, s);
+        if (pr == 4 && bn == 32) return nprod == 3 ? go_h2<4, 32, 4, 1, 3, 0, 24>(a, s) : (nprod == kNprodF16 ? go_h2<4, 32, 4, 1, kNprodF16, 0, 24>(a, s) : go_h2<4, 32, 4, 1, 1, 0, 24>(a, s));
+        if (pr == 4 && bn == 64) return nprod == 3 ? go_h2<4, 64, 2, 2, 3, 0, 24>(a, s) : (nprod == kNprodF16 ? go_h2<4, 64, 2, 2, kNprodF16, 0, 24>(a, s) : go_h2<4, 64, 2, 2, 1, 0, 24>(a, s));
         plan_not_built(p, nprod);
     }
     if (abl || opt) {
@@ -98,6 +98,7 @@ void launch_conv_h2(const ConvArgs& a, const ConvPlan& p, int nprod, int abl, in
     }
     if (nprod == 3) go_h2_shape<3>(a, p, s);
     else if (nprod == 1) go_h2_shape<1>(a, p, s);
+    else if (nprod == kNprodF16) go_h2_shape<kNprodF16>(a, p, s);
     else if (pr == 4 && bn == 64) go_h2<4, 64, 2, 2, 4>(a, s);
     else if (pr == 4 && bn == 128) go_h2<4, 128, 2, 2, 4>(a, s);
     else plan_not_built(p, nprod);
@@ -105,6 +106,7 @@ void launch_conv_h2(const ConvArgs& a, const ConvPlan& p, int nprod, int abl, in
 
 void launch_conv_h2s(const ConvArgs& a, int nprod, hipStream_t s) {
     if (nprod == 3) hipLaunchKernelGGL((conv_h2s_kernel<3>), dim3(a.tiles_m * a.tiles_n), dim3(256), kH2sLds, s, a);
+    else if (nprod == kNprodF16) hipLaunchKernelGGL((conv_h2s_kernel<kNprodF16>), dim3(a.tiles_m * a.tiles_n), dim3(256), kH2sLds, s, a);
     else hipLaunchKernelGGL((conv_h2s_kernel<1>), dim3(a.tiles_m * a.tiles_n), dim3(256), kH2sLds, s, a);
 }
 
@@ -113,9 +115,9 @@ void launch_conv_h2d(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_
     if (p.sched == ConvSched::Deep) {  // launches that cannot fill the chip: weights eight steps ahead, the three staging rounds in flight together (conv_h2.hpp)
         if (pr == 2 && bn == 128 && nprod == 3) return go_h2d<128, 4, 3, 2, true>(a, s);
     } else {
-        if (pr == 4 && bn == 64) return nprod == 3 ? go_h2d<64, 4, 3>(a, s) : go_h2d<64, 4, 1>(a, s);
-        if (pr == 4 && bn == 128) return nprod == 3 ? go_h2d<128, 8, 3>(a, s) : go_h2d<128, 8, 1>(a, s);
-        if (pr == 2 && bn == 128) return nprod == 3 ? go_h2d<128, 4, 3, 2>(a, s) : go_h2d<128, 4, 1, 2>(a, s);
+        if (pr == 4 && bn == 64) return nprod == 3 ? go_h2d<64, 4, 3>(a, s) : (nprod == kNprodF16 ? go_h2d<64, 4, kNprodF16>(a, s) : go_h2d<64, 4, 1>(a, s));
+        if (pr == 4 && bn == 128) return nprod == 3 ? go_h2d<128, 8, 3>(a, s) : (nprod == kNprodF16 ? go_h2d<128, 8, kNprodF16>(a, s) : go_h2d<128, 8, 1>(a, s));
+        if (pr == 2 && bn == 128) return nprod == 3 ? go_h2d<128, 4, 3, 2>(a, s) : (nprod == kNprodF16 ? go_h2d<128, 4, kNprodF16, 2>(a, s) : go_h2d<128, 4, 1, 2>(a, s));
     }
     plan_not_built(p, nprod);
 }

@@ -23,8 +23,9 @@ void conv_h2r_kernel(ConvArgs a) {
     constexpr int BM = 128;
     constexpr int NW = WARPS_M * WARPS_N;
     static_assert(NW == 4, "256 threads: one 16-byte slot of the A tile per thread and plane");
-    static_assert(NPROD == 1 || NPROD == 3, "one (bf16 operands) or three products");
-    constexpr int NPL = NPROD == 1 ? 1 : 2;
+    constexpr bool ONEP = one_product(NPROD), F16P = NPROD == kNprodF16;
+    static_assert(ONEP || NPROD == 3, "one (a bf16 or an fp16 plane) or three products");
+    constexpr int NPL = ONEP ? 1 : 2;
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
     constexpr int MT = WM / 32, NTL = WN / 32;
     constexpr int PLANE_A = BM * 32, STAGE = 2 * PLANE_A;           // 8 KiB per stage (two planes)
@@ -116,8 +117,8 @@ void conv_h2r_kernel(ConvArgs a) {
         transform_octet<AFFINE>(ar[set], tab + ac0[set], a.Cin, in_scale, relu_floor, am[set], t);
         unsigned char* dst = smem_raw + stage * STAGE + tid * 16;
         F4 Hh, Ll;
-        if (NPROD == 1) {
-            bf16_octet(t[0], t[1], Hh);
+        if (ONEP) {
+            one_plane_octet<F16P>(t[0], t[1], Hh);
             *reinterpret_cast<F4*>(dst) = Hh;
         } else {
             split_h2_octet(t[0], t[1], Hh, Ll);
@@ -172,7 +173,7 @@ void conv_h2r_kernel(ConvArgs a) {
         load_b((u + 1) & 1, kc + 1);
         store_a((u + 1) & 1, (u + 1) & 1);                           // A(kc+1): loaded during step kc-1
         load_a(kc + 2, u & 1);                                       // register set u&1 held A(kc), already in LDS
-        if (NPROD == 1) {
+        if (ONEP) {
             product(u & 1, 0, 0, u == 0);
         } else {
             product(u & 1, 1, 0, u == 0);                            // lo * hi; chains of 4 k-groups counted from k = 0

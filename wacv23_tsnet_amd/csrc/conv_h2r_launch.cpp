@@ -28,7 +28,7 @@ void go_np(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
 }  // namespace
 
 void launch_conv_h2r(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_t s) {
-    nprod == 3 ? go_np<3>(a, p, s) : go_np<1>(a, p, s);
+    nprod == 3 ? go_np<3>(a, p, s) : (nprod == kNprodF16 ? go_np<kNprodF16>(a, p, s) : go_np<1>(a, p, s));
 }
 
 }  // namespace tsnet

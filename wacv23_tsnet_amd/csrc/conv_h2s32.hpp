@@ -25,11 +25,12 @@ template <int NPROD>
 __global__ __launch_bounds__(256, 3)
 void conv_h2s32_kernel(ConvArgs a) {
     constexpr int BN = 64, WARPS_M = 2, WARPS_N = 2, MT = 2, NTL = 1;
-    constexpr int NPL = NPROD == 1 ? 1 : 2;
+    constexpr bool ONEP = one_product(NPROD), F16P = NPROD == kNprodF16;
+    constexpr int NPL = ONEP ? 1 : 2;
     constexpr int PC = kPatchCols + 6, PRW = kPatchRows + 6, PP = PRW * PC;     // 38 x 10 = 380 patch pixels
     constexpr int REGION = kS32Region, PLANE = kS32Plane;
     constexpr int NSTEPS = 98;                                                  // 49 taps x two 16-channel groups
-    static_assert(NPROD == 1 || NPROD == 3, "one (bf16 operands) or three products");
+    static_assert(ONEP || NPROD == 3, "one (a bf16 or an fp16 plane) or three products");
 
     HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) unsigned char, smem_raw)
     const int tid = threadIdx.x;
@@ -88,9 +89,9 @@ void conv_h2s32_kernel(ConvArgs a) {
             float t[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) t[e] = x[r].v[e] * in_scale;
-            if (NPROD == 1) {
+            if (ONEP) {
                 uint2 w;
-                w.x = TSNET_CVT_PK_BF16(t[0], t[1]); w.y = TSNET_CVT_PK_BF16(t[2], t[3]);
+                w.x = cvt_pk_one<F16P>(t[0], t[1]); w.y = cvt_pk_one<F16P>(t[2], t[3]);
                 *reinterpret_cast<uint2*>(dst) = w;
             } else {
                 unsigned h0, l0, h1, l1;
@@ -143,7 +144,7 @@ void conv_h2s32_kernel(ConvArgs a) {
         load_b((j + 3) & 3, s + 3);
         const int jn = j + 1;                                                     // the next step: tap 2 c + (jn >> 1) (jn = 4: the next chain's first)
         load_a(jn & 1, 2 * c + (jn >> 1), jn & 1);
-        if (NPROD == 1) {
+        if (ONEP) {
             product(j & 1, j, 0, 0, j == 0);
         } else {
             product(j & 1, j, 1, 0, j == 0);                                      // lo * hi; chains of four k-groups counted from k = 0 (conv_h2r's association)

@@ -35,7 +35,9 @@ struct ConvShape {
     int csplit = 0;              // > 0: channels >= csplit come from a second tensor (concat on load)
     int x2_nmod = 1;             // images of that second tensor (image n reads its image n % x2_nmod)
     bool transform = false;      // the producer's InstanceNorm (+ ReLU) applied while the operand is staged
-    int nprod = 3;               // 1 = bf16 operands, 3 or 4 fp16 x 2 products
+    int nprod = 3;               // 1 = one operand plane, 3 or 4 fp16 x 2 products
+    bool f16 = false;            // nprod = 1: the plane holds fp16 of the scaled operand (fp16-operand mode) instead of bf16.  Every rule keyed on
+                                 // nprod == 1 counts MFMA work per staged byte and holds for both kinds: an fp16 layer runs its bf16 twin's plan
     bool fin_counter = false;    // output statistics with arrival counters supplied: the in-kernel finalize is possible
     int ho() const { return (H + 2 * pad - ks) / stride + 1; }
     int wo() const { return (W + 2 * pad - ks) / stride + 1; }
@@ -152,7 +154,7 @@ inline void validate_conv(const ConvShape& s) {
 // eligible_only: what the layer CAN run on (an explicit request, op tests / tools); otherwise what the forward runs it on
 inline ConvFamily conv_class(const ConvShape& s, int rows, bool eligible_only) {
     const int Ho = s.ho(), Wo = s.wo();
-    const bool bf16 = s.nprod == 1;
+    const bool onep = s.nprod == 1;                  // one product: a bf16 plane or (s.f16) an fp16 plane
     const bool s1 = s.ks == 3 && s.stride == 1 && s.pad == 1 && s.cin >= 16 && (s.cin & 15) == 0 && s.H >= 2 && s.W >= 2;
     if (s.csplit || Ho <= 0 || Wo <= 0 || Wo % kPlanTileCols) return ConvFamily::H2R;
     const bool s2 = s.ks == 3 && s.stride == 2 && s.pad == 1 && !s.reflect && s.cin >= (eligible_only ? 16 : 128) && (s.cin & 15) == 0 && s.H == 2 * Ho && s.W == 2 * Wo;
@@ -169,7 +171,7 @@ inline ConvFamily conv_class(const ConvShape& s, int rows, bool eligible_only) {
     // general kernel); with 64 channels the K loop is four slabs long and the general kernel's smaller per-tile prologue wins (147 vs 157 us)
     // bf16 operands: a third of the MFMA work per staged byte -- the patch tiles' five-round staging binds (459 / 378 us on 128 -> 256 /
     // 256 -> 512 at 24 images against 180 us for the general kernel's 128-wide tile: profiles/round4_bf16_layers.txt)
-    if (s2 && (eligible_only || !bf16)) return ConvFamily::H2D;
+    if (s2 && (eligible_only || !onep)) return ConvFamily::H2D;
     return ConvFamily::H2R;
 }
 
@@ -219,12 +221,13 @@ inline void plan_w1_chunk(const ConvShape& s, const ConvRequest& r, int cus, Con
 
 inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
     validate_conv(s);
-    const bool bf16 = s.nprod == 1;
+    const bool onep = s.nprod == 1;                  // one product: a bf16 plane or (s.f16) an fp16 plane
     const int Ho = s.ho(), hw = Ho * s.wo();
     ConvPlan p;
     if (s.form == 1) {
         if (s.csplit || !w1_eligible(s.ks, s.stride, s.pad, s.cin, s.H, s.W))
             throw std::invalid_argument("conv(w1): the layer is packed in the Winograd form, which needs a single source and whole 4 x 32 tiles");
+        if (s.f16) throw std::invalid_argument("conv(w1): the Winograd form is not built for fp16 operands (one fp16 plane); its one-product form takes bf16 operands");
         p.family = ConvFamily::W1;
     } else if (r.kernel == ConvKernel::General) {
         p.family = ConvFamily::H2R;
@@ -233,7 +236,8 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         if (r.kernel == ConvKernel::Patch && p.family == ConvFamily::H2R) throw std::invalid_argument("conv: this layer / frame size has no patch kernel");
     }
     if (s.nprod != 1 && s.nprod != 3 && (s.nprod != 4 || p.family != ConvFamily::H2))
-        throw std::invalid_argument("conv: 1 (bf16 operands) or 3 products; four on the 3x3 / stride-1 patch kernel's plain 4x64 and 4x128 tiles");
+        throw std::invalid_argument("conv: 1 (bf16 operands), 16 (fp16 operands) or 3 products; four on the 3x3 / stride-1 patch kernel's plain 4x64 and 4x128 tiles");
+    if (s.f16 && s.nprod != 1) throw std::invalid_argument("conv: fp16 operands (one fp16 plane) run one product");
     auto set_tiles = [&](int rows_per_tile_m, int bn) {     // rows_per_tile_m: output positions of an M tile (patch: PR * 32; general: 128)
         p.tpi = (hw + rows_per_tile_m - 1) / rows_per_tile_m;
         p.tiles_m = s.N * p.tpi; p.tiles_n = (s.cout + bn - 1) / bn;
@@ -261,7 +265,7 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
             // bf16 operands: one product per step -- the 64-wide tile is latency-bound (mfma_util 0.19, 81 % of the wave cycles
             // waiting at configs[4]); the 128-wide one runs three workgroups per CU as well (no second accumulator level) and wins
             // whenever it still fills the chip
-            if (bf16 && s.npad % 128 == 0 && s.cout > 64 && tm * ((s.cout + 127) / 128) >= cus) bn = 128;
+            if (onep && s.npad % 128 == 0 && s.cout > 64 && tm * ((s.cout + 127) / 128) >= cus) bn = 128;
             // (Round 3 gave a forward of ONE frame two-K-group tiles here -- eight waves, total = P0 + P1: another association of the same
             // chains, so a frame run alone differed from its copy inside a batch in the last bits.  Since round 5 every layer that form
             // paid on runs conv_w1 in every batch (the decoder's second up-convolution included: 29.7 against 34.0 us for one frame, equal
@@ -273,9 +277,9 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         // the A rows double-buffered by tap column: 120.5 -> 107.0 us on the 512 -> 512 layer, 96.1 -> 86.3 us on the decoder's first
         // up-convolution (profiles/round6_h2_1x4.txt).  Same K order and chains: the same bits as the 2 x 2 form (tests).  Tile code 3128
         // forces it, 128 the 2 x 2 form.
-        p.side_by_side = r.alt || (!r.width && bf16 && pr == 4 && bn == 128);
+        p.side_by_side = r.alt || (!r.width && onep && pr == 4 && bn == 128);
         // what conv_h2_launch.cpp instantiates
-        if (p.side_by_side && (!bf16 || bn != 128 || pr != 4)) throw std::invalid_argument("conv(h2): the 1 x 4 wave grid is the bf16 4 x 128 tile's");
+        if (p.side_by_side && (!onep || bn != 128 || pr != 4)) throw std::invalid_argument("conv(h2): the 1 x 4 wave grid is the bf16 4 x 128 tile's (and its fp16-operand twin's: one product)");
         if (!(pr == 4 && (bn == 32 || bn == 64 || bn == 128)) && !(pr == 2 && bn == 128)) throw std::invalid_argument("conv(h2): tile must be 4x32, 4x64, 4x128 or 2x128");
         if (Ho % pr) throw std::invalid_argument("conv(h2): the output height must be a multiple of the tile's rows (2 or 4)");
         if (s.nprod == 4 && (pr != 4 || bn == 32 || r.sched != ConvSched::Plain)) throw std::invalid_argument("conv(h2): four products on the plain 4x64 and 4x128 tiles");
@@ -316,6 +320,7 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         // workgroup's memory round trips (72 -> us on the 64-tile launch).  Same bits: the choice may follow the batch.  Tile code 12128 forces
         // it, 2128 the plain schedule.
         const bool deep = r.width ? r.sched == ConvSched::Deep : (pr == 2 && bn == 128 && s.nprod == 3 && (long)p.tiles_m * p.tiles_n <= 2L * cus);
+        if (deep && s.f16) throw std::invalid_argument("conv(h2d): the deep schedule (12128) is not built for fp16 operands (one fp16 plane): fp16 x 2 operands only");
         if (deep && (pr != 2 || bn != 128 || s.nprod != 3)) throw std::invalid_argument("conv(h2d): the deep schedule is the 2 x 128 tile's, fp16 x 2 operands");
         p.sched = deep ? ConvSched::Deep : ConvSched::Plain;
         break;

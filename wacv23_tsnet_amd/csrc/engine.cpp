@@ -12,7 +12,7 @@
 //   fuse conv1 (per-source half + shared target half) -> conv2 -> residual+mean -> 1x1 conv   [A7, A6]
 //   dec map 1x1 (cat on load) -> ResnetBlocks -> 3x (upsample, conv) -> 7x7+tanh [A8, A9]
 // Every convolution reads the producer's RAW fp32 output and applies that producer's InstanceNorm + ReLU while it stages its operand
-// tile; operands enter the matrix pipe as fp16 x 2 splits (three products) or, with tsnet_cfg.operand_mode = 1, as one bf16 plane.
+// tile; operands enter the matrix pipe as fp16 x 2 splits (three products) or, with tsnet_cfg.operand_mode = 1 / 3, as one bf16 / fp16 plane.
 // Which kernel a layer runs on (the Winograd-along-x kernel of conv_w1.hpp for the ResnetBlock / FuseNet layers and the first two
 // up-convolutions, the patch kernels of conv_h2.hpp where the output splits into 4 x 32 rectangles, the general implicit GEMM of
 // conv_g64.hpp / conv_h2r.hpp elsewhere) and which tile it takes depend on the layer and the frame size only -- never on the batch, never
@@ -191,7 +191,7 @@ struct ConvLayer {
     int form = 0;                     // 0: the filter as it is (ks x ks taps); 1: its Winograd F(2,3)-along-x transform, 3 x 4 "taps" (conv_w1.hpp)
     size_t w_off = 0, b_off = 0;          // offsets into the packed buffer: operand planes (16-bit units from the plane section), bias (floats)
     const unsigned short* wq = nullptr;   // device: operand planes [planes][K/16][Npad][2 octets][8] (conv_common.hpp pack_weights_kernel)
-    const float* w_unscale = nullptr;     // device scalar 2^-sw (in the packed buffer: replicas receive it with the broadcast); null in bf16 mode
+    const float* w_unscale = nullptr;     // device scalar 2^-sw (in the packed buffer: replicas receive it with the broadcast); null in the bf16 modes
     const float* bias = nullptr;          // device (cout)
 };
 
@@ -227,24 +227,27 @@ struct ConvCall {
     float* fin_alpha = nullptr; float* fin_beta = nullptr; int* fin_counter = nullptr;
     unsigned* amax_out = nullptr;   // publish max |y| per image (operand scale of a consumer without an a-priori bound)
     int x_bf16 = 0, y_bf16 = 0; // bf16 storage mode (bf16-operand kernels only): the input / output tensor holds bf16
-    int nprod = 3;              // products per k-group: 3 (4 adds lo*lo), or 1 = bf16 operands
+    int nprod = 3;              // products per k-group: 3 (4 adds lo*lo), 1 = bf16 operands, or TSNET_NPROD_F16 = one product on one fp16 plane
     int tclass = TSNET_T_CONV;
 };
 
-// power-of-two operand scale: |x| <= bound  ->  |x * 2^sa| <= 2^15 < 65504 (fp16 max)
-inline int h2_scale_log2(float bound) {
+// power-of-two operand scale: |x| <= bound  ->  |x * 2^sa| <= 2^15 < 65504 (fp16 max).  lim: the largest |sa|.  24 keeps the residual plane of
+// the fp16 x 2 split meaningful; the one-plane fp16 kind has no residual and takes 64 (2^-(sa + sw) stays a normal fp32), so that its
+// results are covariant with a power-of-two scaling of the input far outside fp16's own range.  A scale derived on the device from a
+// published maximum (h2_device_scale, conv_common.hpp) keeps 24 in every kind.
+inline int h2_scale_log2(float bound, int lim = 24) {
     if (!(bound > 0.f) || !std::isfinite(bound)) throw ArgError("conv: the operand bound must be positive and finite");
     int e = 0;
     (void)std::frexp(bound, &e);          // bound = m * 2^e, m in [0.5, 1)  ->  bound <= 2^e
     int sa = 15 - e;
-    if (sa > 24) sa = 24;
-    if (sa < -24) sa = -24;
+    if (sa > lim) sa = lim;
+    if (sa < -lim) sa = -lim;
     return sa;
 }
 
 // What depends on pointers is checked here; the layer, the geometry and the request by plan_conv (conv_plan.hpp), before anything is launched.
 void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req = {}) {
-    const bool bf16 = c.nprod == 1;
+    const bool bf16 = c.nprod == 1, f16 = c.nprod == TSNET_NPROD_F16;      // the two one-product kinds: unscaled bf16, or fp16 with the split path's scales
     if (!L.wq) throw ArgError("conv: layer has no packed weights");
     if (c.alpha && !c.beta) throw ArgError("conv: alpha without beta");
     if ((c.x_bf16 || c.y_bf16) && !bf16) throw ArgError("conv: bf16 storage goes with bf16 operands");
@@ -256,12 +259,12 @@ void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req =
     ConvShape sh;
     sh.ks = L.ks; sh.stride = L.stride; sh.pad = L.pad; sh.reflect = L.reflect; sh.cin = L.cin_pad; sh.cout = L.cout; sh.npad = L.npad; sh.kpad = L.kpad;
     sh.form = L.form; sh.N = c.N; sh.H = c.H; sh.W = c.W; sh.csplit = c.x2 ? c.csplit : 0; sh.x2_nmod = c.x2_nmod > 0 ? c.x2_nmod : 1;
-    sh.transform = c.alpha != nullptr; sh.nprod = c.nprod; sh.fin_counter = c.stat_part && c.fin_counter;
+    sh.transform = c.alpha != nullptr; sh.nprod = f16 ? 1 : c.nprod; sh.f16 = f16; sh.fin_counter = c.stat_part && c.fin_counter;
     ConvPlan p;
     try { p = plan_conv(sh, req, ctx.cus); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     ConvArgs g{};
     g.x = c.x; g.x2 = c.x2; g.in_alpha = c.alpha; g.in_beta = c.alpha ? c.beta : nullptr; g.in_relu = c.relu;
-    const int sa = (bf16 || c.in_amax) ? 0 : h2_scale_log2(L.form == 1 ? 2.f * c.bound : c.bound);   // Winograd: |V| <= 2 max |x|
+    const int sa = (bf16 || c.in_amax) ? 0 : h2_scale_log2(L.form == 1 ? 2.f * c.bound : c.bound, f16 ? 64 : 24);   // Winograd: |V| <= 2 max |x|
     g.in_scale = std::ldexp(1.0f, sa); g.in_unscale = std::ldexp(1.0f, -sa);
     g.in_amax = bf16 ? nullptr : c.in_amax; g.in_bound_add = c.bound_add; g.amax_out = c.amax_out;
     g.w = L.wq; g.w_unscale = bf16 ? nullptr : L.w_unscale; g.bias = L.bias; g.y = c.y;
@@ -435,7 +438,7 @@ void run_warp(Ctx& ctx, const float* src, const float* flow, float* out, int B, 
 }
 
 // weights of one layer -> operand planes + the un-scale factor; `stage` holds the OIHW parameter on the device (form 1: its transform,
-// kernel 3 x 4)
+// kernel 3 x 4).  planes: 2 = fp16 (hi, lo), 1 = one bf16 plane, -1 = one fp16 plane (hi alone)
 void pack_layer(const float* stage, const ConvLayer& L, unsigned short* planes_out, int planes, float scale, hipStream_t s) {
     hipLaunchKernelGGL(pack_weights_kernel, dim3(ew_grid((size_t)L.kpad * L.npad)), dim3(256), 0, s, stage, planes_out, scale, planes,
                        L.cout, L.cin_real, L.cin_pad, L.ks, L.form == 1 ? 4 : L.ks, L.kpad, L.npad, L.cin_total > 0 ? L.cin_total : L.cin_real, L.cin_off);
@@ -495,7 +498,8 @@ struct tsnet_engine {
     int cus = 256;                        // CUs of the engine's device, read at tsnet_finalize (launch heuristics only: conv_plan.hpp)
     int C = 0, h = 0, w = 0, P = 0, K = 0, Bmax = 0;
     int cp_img = 0, cp_lbl = 0;
-    int np = 3;                           // MFMA products per k-group: 3 (fp16 x 2 operands), or 1 = bf16-operand mode (cfg.operand_mode)
+    int np = 3;                           // MFMA products per k-group: 3 (fp16 x 2 operands), or 1 = the bf16- and fp16-operand modes (cfg.operand_mode)
+    bool f16 = false;                     // np = 1: one fp16 plane of the scaled operand (cfg.operand_mode = 3) instead of one bf16 plane
     bool st16 = false;                    // cfg.operand_mode = 2: bf16 operands AND bf16 storage of the large conv-to-conv activations (the encoder's
                                           // 256^2 .. 64^2 maps, the decoder's up-convolution outputs and upsampled inputs); statistics from fp32 accumulators
 
@@ -585,7 +589,7 @@ struct tsnet_engine {
     }
     float enc_bound() const { return (float)(cfg.enc_blocks + 1) * std::sqrt((float)P); }  // bound of the source features: |relu(IN)| <= sqrt(P), + one IN output per block
     // every convolution of the forward goes through here: the engine's operand mode, the lane's statistics scratch, the finalize
-    void conv(Ctx& ctx, const ConvLayer& L, ConvCall& c) { c.nprod = np; run_conv(ctx, L, c); }
+    void conv(Ctx& ctx, const ConvLayer& L, ConvCall& c) { c.nprod = f16 ? TSNET_NPROD_F16 : np; run_conv(ctx, L, c); }
     void conv_stats(Ctx& ctx, const ConvLayer& L, ConvCall& c, int N, int HW, float* alpha, float* beta) {
         double* pt = ctx.lane ? part_side : part;
         c.stat_part = pt;
@@ -714,18 +718,18 @@ void tsnet_engine::alloc_all(hipStream_t s) {
         float mx = 0.f;
         for (float v : wsrc) { const float av = std::fabs(v); if (av > mx) mx = av; }
         if (!std::isfinite(mx)) throw WeightError("parameter '" + L->wparam + "' holds a non-finite value");
-        const int sw = (np != 1 && mx > 0.f) ? h2_scale_log2(mx) : 0;
+        const int sw = ((np != 1 || f16) && mx > 0.f) ? h2_scale_log2(mx) : 0;
         const float unscale = std::ldexp(1.0f, -sw);
         HIP_TRY(hipMemcpyAsync(stage, wsrc.data(), wsrc.size() * sizeof(float), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(wpack + tab_off + i, &unscale, sizeof(float), hipMemcpyHostToDevice, s));
-        pack_layer(stage, *L, planes_base + L->w_off, planes, std::ldexp(1.0f, sw), s);
+        pack_layer(stage, *L, planes_base + L->w_off, f16 ? -1 : planes, std::ldexp(1.0f, sw), s);
         if (!L->bparam.empty()) {
             const Param& pb = params[pindex[L->bparam]];
             HIP_TRY(hipMemcpyAsync(wpack + L->b_off, pb.host.data(), pb.host.size() * sizeof(float), hipMemcpyHostToDevice, s));
         }
         HIP_TRY(hipStreamSynchronize(s));   // host vectors / staging buffer reused next iteration
         L->wq = planes_base + L->w_off;
-        L->w_unscale = np == 1 ? nullptr : wpack + tab_off + i;
+        L->w_unscale = (np == 1 && !f16) ? nullptr : wpack + tab_off + i;
         L->bias = L->bparam.empty() ? nullptr : wpack + L->b_off;
     }
     {                                      // RGB head: fp32 weights in the vector kernel's order + bias
@@ -1036,7 +1040,7 @@ int tsnet_create(const tsnet_cfg* cfg, tsnet_handle* out) {
     if (cfg->max_batch < 1) return bad("max_batch must be >= 1");
     if (cfg->pose_composite && (cfg->height != 256 || cfg->width != 256))
         return bad("pose composite is defined for 256x256 frames only (TSNet_pose.py:277-280)");
-    if (cfg->operand_mode < 0 || cfg->operand_mode > 2) return bad("operand_mode must be 0 (fp32-class), 1 (bf16 operands) or 2 (bf16 operands + bf16 storage)");
+    if (cfg->operand_mode < 0 || cfg->operand_mode > 3) return bad("operand_mode must be 0 (fp32-class), 1 (bf16 operands), 2 (bf16 operands + bf16 storage) or 3 (fp16 operands)");
     try {
         tsnet_engine* e = new tsnet_engine();
         e->cfg = *cfg;
@@ -1046,6 +1050,7 @@ int tsnet_create(const tsnet_cfg* cfg, tsnet_handle* out) {
         e->h = cfg->height / ds; e->w = cfg->width / ds; e->P = e->h * e->w;
         e->np = cfg->operand_mode != 0 ? 1 : 3;
         e->st16 = cfg->operand_mode == 2;
+        e->f16 = cfg->operand_mode == 3;
         e->build_layers();
         *out = e;
     } catch (const std::exception& ex) { g_create_error = ex.what(); return TSNET_ERR_NOMEM; }
@@ -1354,7 +1359,8 @@ struct OpLayer {
         if (form == 1) { hw = winograd_x_filters(hw); wn = hw.size(); }
         float mx = 0.f;
         for (float v : hw) mx = std::max(mx, std::fabs(v));
-        const int planes = nprod == 1 ? 1 : 2;
+        const bool f16 = nprod == TSNET_NPROD_F16;
+        const int planes = (nprod == 1 || f16) ? 1 : 2;
         const int sw = (nprod != 1 && mx > 0.f) ? h2_scale_log2(mx) : 0;
         wd = mem.alloc<float>(wn * sizeof(float));
         wq = mem.alloc<unsigned short>((size_t)L.kpad * L.npad * 2 * planes);
@@ -1362,7 +1368,7 @@ struct OpLayer {
         HIP_TRY(hipMemcpy(wd, hw.data(), wn * sizeof(float), hipMemcpyHostToDevice));
         const float unscale = std::ldexp(1.0f, -sw);
         HIP_TRY(hipMemcpy(un, &unscale, sizeof(float), hipMemcpyHostToDevice));
-        pack_layer(wd, L, wq, planes, std::ldexp(1.0f, sw), s);
+        pack_layer(wd, L, wq, f16 ? -1 : planes, std::ldexp(1.0f, sw), s);
         if (bias) {
             bd = mem.alloc<float>(Cout * sizeof(float));
             HIP_TRY(hipMemcpy(bd, bias, Cout * sizeof(float), hipMemcpyDefault));
@@ -1379,7 +1385,7 @@ int tsnet_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w
                     float bound, int nprod, int kernel, int tile, float* y, void* stream) {
     OP_BEGIN
     if (!x || !w_oihw || !y) throw ArgError("null tensor");
-    if (nprod != 1 && nprod != 3 && nprod != 4) throw ArgError("conv2d op: 1 (bf16 operands), 3 or 4 products");
+    if (nprod != 1 && nprod != 3 && nprod != 4 && nprod != TSNET_NPROD_F16) throw ArgError("conv2d op: nprod must be 1 (bf16 operands), 16 (fp16 operands: one fp16 plane), 3 or 4 products");
     hipStream_t s = (hipStream_t)stream;
     Ctx ctx(s, current_device_cus());
     ConvRequest req;

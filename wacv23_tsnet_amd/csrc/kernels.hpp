@@ -12,7 +12,7 @@ namespace tsnet {
 
 // The convolution launchers DISPATCH: run_conv fills ConvArgs from the ConvPlan (conv_plan.hpp: plan_conv has validated the layer and plans
 // instantiated kernels only); a family with several tiles takes the plan and runs the instantiation it names -- none is a bug, std::logic_error.
-// nprod: 1 (bf16 operands), 3, or 4 (h2 only); affine = a.in_alpha != null; kernel size from a.taps.  abl / opt: tools build only, outside the plan.
+// nprod: 1 (bf16 operands), 16 (kNprodF16: one fp16 plane; every family but conv_w1), 3, or 4 (h2 only); affine = a.in_alpha != null; kernel size from a.taps.  abl / opt: tools build only, outside the plan.
 // conv_h2.hpp -- patch kernels:
 //   h2  (3x3 / stride 1): rows x width in {4x32, 4x64, 4x128, 2x128}, the bf16 4x128 tile's side-by-side wave grid, two K groups (4x32, 4x64)
 //   h2s (7x7 stem, 8 input channels): 4 x 64

@@ -8,7 +8,8 @@ namespace tsnet {
 // OIHW fp32 (kernel kh x kw) -> operand planes in MFMA fragment order:
 //   out[p][((kc*Npad + n)*2 + o)*8 + e] = part_p( scale * W[k = kc*16 + (o ^ ((n>>3)&1))*8 + e][n] ),  k = tap*cin_pad + c
 // A wave's fragment of 32 columns x 16 k is 1 KiB contiguous; the octet swizzle by bit 3 of the column is the one the A tile uses.
-// planes = 2: fp16 (hi, lo) of w * scale;  planes = 1: one bf16 plane of w (bf16-operand mode, scale ignored)
+// planes = 2: fp16 (hi, lo) of w * scale;  planes = 1: one bf16 plane of w (bf16-operand mode, scale ignored);  planes = -1: the hi plane
+// alone, rne16(w * scale) (fp16-operand mode)
 __global__ void pack_weights_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, float scale, int planes,
                                     int cout, int cin_real, int cin_pad, int kh, int kw, int kpad, int npad, int cin_total, int cin_off) {
     const size_t plane = (size_t)kpad * npad;
@@ -30,7 +31,8 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, unsigned short*
         } else {
             unsigned hi, lo;
             split_h2(v * scale, hi, lo);
-            out[idx] = (unsigned short)hi; out[plane + idx] = (unsigned short)lo;
+            out[idx] = (unsigned short)hi;
+            if (planes == 2) out[plane + idx] = (unsigned short)lo;
         }
     }
 }

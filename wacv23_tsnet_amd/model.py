@@ -114,9 +114,10 @@ class TSNet(nn.Module):
                  addcoords=True, ngf=64, n_downsampling=4, return_flow=False,
                  height=256, width=256, max_batch=None, operands="fp32"):
         super().__init__()
-        if operands not in ("fp32", "bf16", "bf16s"):
+        if operands not in ("fp32", "bf16", "bf16s", "fp16"):
             raise ValueError("operands must be 'fp32' (default, 1e-3 parity with the fp32 reference), 'bf16' (BASELINE.json configs[2]/[4]: bf16 "
-                             "convolution operands) or 'bf16s' (the same + bf16 storage of the large activations)")
+                             "convolution operands), 'bf16s' (the same + bf16 storage of the large activations) or 'fp16' (scaled fp16 "
+                             "convolution operands: the cost of 'bf16', 11 significant bits instead of 8)")
         self.operands = operands
         if is_train:
             raise NotImplementedError("training (GAN/VGG losses, optimisers) is outside the MI355X forward path; "
