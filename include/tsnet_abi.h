@@ -206,6 +206,27 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  * tsnet_op_warp_k     <- the same for K sources per driving frame fused with the mean over sources (TSNet.py:366, 392/400), as the forward
  *   runs it: src_fea / flow hold K*B images (image k*B + b), out (B,h,w,C).  repeat > 1 launches the kernel that many times; ms_out
  *   (nullable) receives the average time of launches 2 .. repeat by HIP events -- the kernel ALONE (tools/warp_bench.py).
+ * tsnet_op_warp_k_shared <- tsnet_op_warp_k with the forward's source-batch extent SB (B, or 1 in clip mode: one source set shared by the
+ *   batch): src_fea holds K*SB images and (source k, driving frame b) reads image k*SB + b % SB; SB must divide B.  No timing arguments.
+ * tsnet_op_add_stats  <- FuseNet's join (TSNet.py:195-197 split at the concat): y[n] = x[n / add_nmod * x_sb + n % add_nmod % x_sb] +
+ *   add[n % add_nmod] (one fp32 addition per element) with the InstanceNorm statistics of y as tsnet_op_instnorm_stats gives them.
+ *   x (N / add_nmod * x_sb, HW, C), add (add_nmod, HW, C), y (N, HW, C), alpha / beta (N*C); add_nmod divides N, x_sb divides add_nmod.
+ * tsnet_op_finalize_stats <- stage 2 of the statistics alone: part (N, S, C, 2) DEVICE doubles, (sum, sum of squares) per (image, partial,
+ *   channel) over HW positions in all -> alpha, beta (N*C) by the kernel the forward picks for S (in_finalize for S <= 8, in_finalize2
+ *   above: what a convolution epilogue's S = tiles per image, up to 1024, goes through).
+ * tsnet_op_fuse_tail  <- FuseNet's tail (TSNet.py:198-200, :400): zbar[b] = mean over k of cat(src_fea[k*SB + b % SB], tar_fea[b]) +
+ *   (y2[k*B + b] * alpha + beta).  src_fea (K*SB, P, C1), tar_fea (B, P, C1), y2 (K*B, P, 2*C1), alpha / beta (K*B * 2*C1), zbar (B, P, 2*C1);
+ *   1 <= K <= 8, SB divides B, C1 a multiple of 4.
+ * tsnet_op_pack_input <- the stems' input assembly (set_test_input's /255 + torch.cat + coord_conv, TSNet.py:286,312,107-125): img / lbl are
+ *   HOST arrays of S device pointers, img[s] (B,3,H,W) and lbl[s] (B,L,H,W) NCHW; out (S*B, H, W, Cp) NHWC holds [img / img_div[s] | lbl |
+ *   xx yy rr (coords != 0: tsnet_coord_table) | zeros], image s*B + b.  nimg = 3, or 0 for the label-only form (img, img_div not read);
+ *   img_div: S HOST floats (255, or 1 for a frame already in [0,1]).  Cp = 8 or a multiple of 16, at least the real channel count.
+ *   amax (S*B): zeroed, then max |out| per image as float bits -- what fixes the stem's operand scale.
+ * tsnet_op_upsample2x_st <- tsnet_op_upsample2x in the bf16 storage mode (tsnet_cfg.operand_mode = 2): x_bf16 / y_bf16 != 0: x / y hold bf16
+ *   (widened exactly on load; the fp32 result rounded to nearest even on store).
+ * The entry points from tsnet_op_warp_k_shared on check their arguments on the host and return TSNET_ERR_ARG, with a message and nothing
+ * launched, for a null tensor, a channel count that is not a multiple of 4, K outside 1..8, an extent that does not divide, a bad Cp, S < 1
+ * or HW < 1; they return after the stream has drained.
  */
 int tsnet_op_conv2d(const float* x, int N, int H, int W, int Cin,
                     const float* w_oihw, const float* bias, int Cout, int ksize, int stride, int pad, int pad_mode,
@@ -231,6 +252,16 @@ int tsnet_op_flow_k(const float* tar_fea, const float* src_fea, const float* tar
 int tsnet_flow_plan(int B, int h, int w, int C);
 int tsnet_op_warp(const float* src_fea, const float* flow, int B, int h, int w, int C, float* out, void* stream);
 int tsnet_op_warp_k(const float* src_fea, const float* flow, int B, int K, int h, int w, int C, float* out, int repeat, float* ms_out, void* stream);
+int tsnet_op_warp_k_shared(const float* src_fea, const float* flow, int B, int K, int SB, int h, int w, int C, float* out, void* stream);
+int tsnet_op_add_stats(const float* x, const float* add, int add_nmod, int x_sb, int N, int HW, int C,
+                       float* y, float* alpha, float* beta, void* stream);
+int tsnet_op_finalize_stats(const double* part, int N, int S, int C, int HW, float* alpha, float* beta, void* stream);
+int tsnet_op_fuse_tail(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
+                       int B, int K, int SB, int P, int C1, float* zbar, void* stream);
+int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S, int B, int H, int W, int L, int nimg, int Cp, int coords,
+                        const float* img_div, float* out, unsigned int* amax, void* stream);
+int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta, int relu,
+                           int N, int H, int W, int C, int x_bf16, int y_bf16, float* y, void* stream);
 const char* tsnet_op_last_error(void);
 
 /* ---- demo post-processing (demo/demo_face.py:96-105,180-198 = demo/demo_pose.py:98-107,

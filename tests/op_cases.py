@@ -864,3 +864,360 @@ def bf16_forward_layer_case(lib, dev, s, kernel, tile, seed=0):
         return conv_cat_case(lib, dev, N, s["H"], s["W"], s["csplit"], s["cin"] - s["csplit"], s["cout"], k=s["ks"], seed=seed, nprod=1, ref="bf16")
     return conv_bf16_case(lib, dev, N, s["H"], s["W"], s["cin"], s["cout"], s["ks"], s["stride"], s["pad"], bool(s["reflect"]),
                           norm=bool(s["transform"]), seed=seed, kernel=kernel, tile=tile)
+
+
+# ---- the kernels between the convolutions, one operator at a time --------------------------------------------------------------------------
+# Each case draws its inputs from the PRNG, evaluates the operation in fp64 torch on the CPU and returns the error (or, where one correctly
+# rounded fp32 operation per element leaves no room, the tensors for torch.equal).  Images that share a launch differ from each other, and
+# per-image coefficients are drawn per (image, channel): a swapped image or channel index moves the result by O(1).
+def _check(lib, rc):
+    assert rc == 0, lib.tsnet_op_last_error().decode()
+
+
+def warp_k_inputs(B, K, h, w, C, SB, seed=0, hand=False):
+    """src (K*SB, C, h, w) and flow (K*B, h, w, 2) of one warp launch.  hand=True: flows placed by hand instead of drawn -- sample positions
+    (pixel units, per axis) on pixel centres, on the outermost sample positions (grid -1 and +1: half a pixel outside the border centres),
+    one and several pixels outside on either side; the product of the two axes' lists holds every corner with all four neighbours outside.
+    Each (source, frame) image walks the list from another start."""
+    src = _rand(seed, "src", (K * SB, C, h, w), -2, 2)
+    flow = _rand(seed, "flow", (K * B, h, w, 2), -1.3, 1.3)
+    if hand:
+        ax = lambda n: [0.0, 1.0, n - 1.0, n - 2.0, -0.5, n - 0.5, -1.0, float(n), -1.5, n + 0.5, -4.0, n + 3.0, 0.25 * n]
+        pts = [((2 * x + 1) / w - 1, (2 * y + 1) / h - 1) for y in ax(h) for x in ax(w)]
+        assert h * w >= len(pts), "the map is too small for every hand-placed position"
+        t = torch.tensor(pts, dtype=torch.float64).float()
+        for n in range(K * B):
+            idx = (torch.arange(h * w) + 37 * n) % len(pts)
+            flow[n] = t[idx].view(h, w, 2)
+    return src, flow
+
+
+def warp_k_ref(src, flow, B, K, SB):
+    """fp64 grid_sample per source, then the mean over sources: (B, C, h, w); (source k, frame b) reads src[k*SB + b % SB], flow[k*B + b]"""
+    acc = 0
+    for k in range(K):
+        sel = [k * SB + b % SB for b in range(B)]
+        acc = acc + F.grid_sample(src[sel].double(), flow[k * B:(k + 1) * B].double(), mode="bilinear", padding_mode="zeros", align_corners=False)
+    return acc / K
+
+
+def run_warp_k(lib, dev, src, flow, B, K, SB, entry="shared"):
+    """the warp through tsnet_op_warp_k_shared ("shared"), tsnet_op_warp_k ("k": SB = B) or tsnet_op_warp ("one": K = 1); NCHW on the CPU"""
+    _, C, h, w = src.shape
+    srcd, fd = nhwc(src).to(dev), flow.contiguous().to(dev)
+    out = torch.full((B, h, w, C), float("nan"), device=dev)
+    if entry == "shared":
+        rc = lib.tsnet_op_warp_k_shared(srcd.data_ptr(), fd.data_ptr(), B, K, SB, h, w, C, out.data_ptr(), None)
+    elif entry == "k":
+        assert SB == B
+        rc = lib.tsnet_op_warp_k(srcd.data_ptr(), fd.data_ptr(), B, K, h, w, C, out.data_ptr(), 1, None, None)
+    else:
+        assert SB == B and K == 1
+        rc = lib.tsnet_op_warp(srcd.data_ptr(), fd.data_ptr(), B, h, w, C, out.data_ptr(), None)
+    _check(lib, rc)
+    _sync(dev)
+    return nchw(out.cpu())
+
+
+def warp_k_case(lib, dev, B, K, h, w, C, seed=0, hand=False, entry="shared"):
+    """warp_mean_kernel with K sources per driving frame against fp64 grid_sample + mean.  Returns max|d|."""
+    src, flow = warp_k_inputs(B, K, h, w, C, B, seed, hand)
+    return (run_warp_k(lib, dev, src, flow, B, K, B, entry).double() - warp_k_ref(src, flow, B, K, B)).abs().max().item()
+
+
+def warp_k_shared_case(lib, dev, B, K, h, w, C, seed=0):
+    """one source set shared by the batch (SB = 1) and the same set replicated per frame (SB = B): (shared output, replicated output,
+    max|shared - fp64 reference|)"""
+    src, flow = warp_k_inputs(B, K, h, w, C, 1, seed)
+    rep = src.repeat_interleave(B, dim=0)                                   # image k*B + b = source k
+    a = run_warp_k(lib, dev, src, flow, B, K, 1)
+    b = run_warp_k(lib, dev, rep, flow, B, K, B)
+    return a, b, (a.double() - warp_k_ref(src, flow, B, K, 1)).abs().max().item()
+
+
+def warp_one_source_entries(lib, dev, B, h, w, C, seed=0):
+    """K = 1 through tsnet_op_warp, tsnet_op_warp_k and tsnet_op_warp_k_shared: the three outputs"""
+    src, flow = warp_k_inputs(B, 1, h, w, C, B, seed)
+    return [run_warp_k(lib, dev, src, flow, B, 1, B, e) for e in ("one", "k", "shared")]
+
+
+def fuse_tail_inputs(B, K, P, C1, SB, seed=0):
+    C = 2 * C1
+    return (_rand(seed, "src", (K * SB, P, C1), -2, 2), _rand(seed, "tar", (B, P, C1), -2, 2), _rand(seed, "y2", (K * B, P, C), -2, 2),
+            _rand(seed, "al", (K * B, C), 0.5, 1.5), _rand(seed, "be", (K * B, C), -0.3, 0.3))
+
+
+def run_fuse_tail(lib, dev, src, tar, y2, al, be, B, K, SB):
+    P, C1 = tar.shape[1:]
+    d = [t.contiguous().to(dev) for t in (src, tar, y2, al, be)]
+    z = torch.full((B, P, 2 * C1), float("nan"), device=dev)
+    _check(lib, lib.tsnet_op_fuse_tail(*[t.data_ptr() for t in d], B, K, SB, P, C1, z.data_ptr(), None))
+    _sync(dev)
+    return z.cpu()
+
+
+def fuse_tail_ref(src, tar, y2, al, be, B, K, SB):
+    """fp64 mean over sources of cat(src[k*SB + b % SB], tar[b]) + (y2[k*B + b] * alpha + beta): (B, P, 2*C1)"""
+    acc = 0
+    for k in range(K):
+        sel = [k * SB + b % SB for b in range(B)]
+        n = slice(k * B, (k + 1) * B)
+        acc = acc + torch.cat([src[sel].double(), tar.double()], dim=2) + (y2[n].double() * al[n].double()[:, None, :] + be[n].double()[:, None, :])
+    return acc / K
+
+
+def fuse_tail_case(lib, dev, B, K, P, C1, seed=0):
+    """fuse_resid_mean_kernel against the fp64 reference; alpha / beta per (image, channel).  Returns max|d|."""
+    t = fuse_tail_inputs(B, K, P, C1, B, seed)
+    return (run_fuse_tail(lib, dev, *t, B, K, B).double() - fuse_tail_ref(*t, B, K, B)).abs().max().item()
+
+
+def fuse_tail_shared_case(lib, dev, B, K, P, C1, seed=0):
+    """SB = 1 and the same sources replicated with SB = B: (shared output, replicated output, max|shared - fp64 reference|)"""
+    src, tar, y2, al, be = fuse_tail_inputs(B, K, P, C1, 1, seed)
+    a = run_fuse_tail(lib, dev, src, tar, y2, al, be, B, K, 1)
+    b = run_fuse_tail(lib, dev, src.repeat_interleave(B, dim=0), tar, y2, al, be, B, K, B)
+    return a, b, (a.double() - fuse_tail_ref(src, tar, y2, al, be, B, K, 1)).abs().max().item()
+
+
+def _instnorm64(y):
+    """InstanceNorm (eps 1e-5, biased variance) of (N, HW, C) in fp64 (F.instance_norm refuses HW = 1)"""
+    y = y.double()
+    mean = y.mean(dim=1, keepdim=True)
+    var = ((y - mean) ** 2).mean(dim=1, keepdim=True)
+    return (y - mean) / torch.sqrt(var + 1e-5)
+
+
+def add_stats_case(lib, dev, K, B, x_sb, HW, C, seed=0, offset=0.0):
+    """add_stats_partial_kernel + its finalize: N = K*B images, add_nmod = B, x of K*x_sb images.  Returns (y, torch's fp32 x + add: one IEEE
+    addition per element, so the bits must agree; max|y*alpha + beta - fp64 instance_norm(y)|)."""
+    N = K * B
+    x = _rand(seed, "x", (K * x_sb, HW, C), -2, 2) + offset
+    add = _rand(seed, "add", (B, HW, C), -2, 2)
+    sel = [n // B * x_sb + n % B % x_sb for n in range(N)]
+    yref = x[sel] + add[[n % B for n in range(N)]]
+    xd, ad = x.to(dev), add.to(dev)
+    y = torch.full((N, HW, C), float("nan"), device=dev)
+    al = torch.full((N * C,), float("nan"), device=dev)
+    be = torch.full((N * C,), float("nan"), device=dev)
+    _check(lib, lib.tsnet_op_add_stats(xd.data_ptr(), ad.data_ptr(), B, x_sb, N, HW, C, y.data_ptr(), al.data_ptr(), be.data_ptr(), None))
+    _sync(dev)
+    y, al, be = y.cpu(), al.cpu().view(N, 1, C), be.cpu().view(N, 1, C)
+    return y, yref, (y * al + be - _instnorm64(yref)).abs().max().item()
+
+
+# tsnet_op_finalize_stats against the same formula in fp64 on the same partials: max relative error of alpha, and of beta relative to
+# |beta| + alpha.  The kernels round var to fp32, add eps, take sqrtf and divide; beta is the product of two rounded fp32 numbers: a handful
+# of half-ulps (2^-24 = 6.0e-8 each).  Worst readings over S in FINALIZE_S x C in (8, 24, 64):
+#   emulated build (sqrtf and / correctly rounded):  in_finalize  alpha 9.85e-8  beta 8.77e-8;   in_finalize2  alpha 1.14e-7  beta 1.39e-7
+#   MI355X:                                          in_finalize  alpha 9.03e-8  beta 1.15e-7;   in_finalize2  alpha 1.05e-7  beta 1.19e-7
+# The gate is twice the worse of the two builds' worst reading (1.39e-7), and not above 1e-6.
+FINALIZE_TOL = 2.8e-7
+FINALIZE_S = (1, 8, 9, 15, 16, 17, 127, 128, 129, 130, 1000, 1024)
+
+
+def finalize_partials(S, C, N=2, rows=2, seed=0):
+    """fp64 partials (N, S, C, 2) of real data (N, S*rows, C) split into S groups of `rows` rows: values in [-2, 2] plus the group's offset
+    3 + 0.3 (g % 5).  Every element then lies in (0, 2 mean), so that a partial lost or counted twice moves the mean AND the variance by about
+    1 / S of themselves, whichever group it is (offsets that grow with g let the group near twice the mean vanish without a trace).
+    Measured on the CPU for S = 1024 (C = 16, 64) and S = 1000 (C = 24): zeroing or doubling any one partial moves alpha by >= 1.7e-3
+    relative and beta by >= 1.7e-3 of |beta| + alpha -- thousands of times FINALIZE_TOL."""
+    off = 3.0 + 0.3 * (torch.arange(S, dtype=torch.float64) % 5)
+    x = _rand(seed, "x", (N, S, rows, C), -2, 2).double() + off.view(1, S, 1, 1)
+    return torch.stack([x.sum(dim=2), (x * x).sum(dim=2)], dim=-1).contiguous(), S * rows
+
+
+def finalize_ref(part, HW):
+    sm, sq = part[..., 0].sum(dim=1), part[..., 1].sum(dim=1)
+    mean = sm / HW
+    var = (sq / HW - mean * mean).clamp(min=0)
+    alpha = 1.0 / torch.sqrt(var + 1e-5)
+    return alpha, -mean * alpha
+
+
+def finalize_case(lib, dev, S, C, N=2, seed=0):
+    """in_finalize (S <= 8) / in_finalize2 (S > 8) on caller-supplied partials.  Returns (alpha error, beta error) as defined above."""
+    part, HW = finalize_partials(S, C, N, seed=seed)
+    pd = part.to(dev)
+    al = torch.full((N, C), float("nan"), device=dev)
+    be = torch.full((N, C), float("nan"), device=dev)
+    _check(lib, lib.tsnet_op_finalize_stats(pd.data_ptr(), N, S, C, HW, al.data_ptr(), be.data_ptr(), None))
+    _sync(dev)
+    ra, rb = finalize_ref(part, HW)
+    ea = ((al.cpu().double() - ra).abs() / ra).max().item()
+    eb = ((be.cpu().double() - rb).abs() / (rb.abs() + ra)).max().item()
+    return ea, eb
+
+
+def finalize_worst(lib, dev):
+    """the worst (alpha, beta) error per kernel over FINALIZE_S x C in (8, 24, 64): {"in_finalize": (ea, eb), "in_finalize2": (ea, eb)}"""
+    worst = {"in_finalize": [0.0, 0.0], "in_finalize2": [0.0, 0.0]}
+    for S in FINALIZE_S:
+        for C in (8, 24, 64):
+            ea, eb = finalize_case(lib, dev, S, C, seed=S + C)
+            wk = worst["in_finalize" if S <= 8 else "in_finalize2"]
+            wk[0], wk[1] = max(wk[0], ea), max(wk[1], eb)
+            assert ea == ea and eb == eb, (S, C)                            # NaN: an entry the kernel did not write
+    return {k: tuple(v) for k, v in worst.items()}
+
+
+def pack_case(lib, dev, S, B, H, W, L, nimg, Cp, coords, divs=None, seed=0):
+    """pack_input_kernel against torch's cat(img / div, lbl, coords, zeros) in NHWC, and its per-image amax against max|out|.  Images in
+    [-120, 150] (a BGR frame minus its mean), labels in [0, 1); image 0's largest magnitude is planted in a label channel, image 1's (where
+    there is one) in a NEGATIVE value -- of the second image channel, or of the first label channel in the label-only form.
+    Returns (out, reference, amax as floats, reference amax)."""
+    import ctypes
+    divs = list(divs) if divs is not None else [255.0] * S
+    imgs = [_rand(seed + s, "img", (B, 3, H, W), -120, 150) for s in range(S)] if nimg else None
+    lbls = [_rand(seed + s, "lbl", (B, L, H, W), 0, 1) for s in range(S)]
+    lbls[0][0, L - 1, H // 2, W // 3] = 7.0
+    if S * B > 1:
+        s1, b1 = divmod(1, B)
+        if nimg:
+            imgs[s1][b1, 1, H // 3, W // 2] = -9.0 * divs[s1]
+        else:
+            lbls[s1][b1, 0, H // 3, W // 2] = -5.0
+    table = torch.empty(H, W, 3)
+    if coords:
+        lib.tsnet_coord_table(H, W, ctypes.cast(table.data_ptr(), ctypes.POINTER(ctypes.c_float)))
+    ref = []
+    for s in range(S):
+        parts = ([imgs[s] / divs[s]] if nimg else []) + [lbls[s]] + ([table.permute(2, 0, 1).expand(B, 3, H, W)] if coords else [])
+        creal = sum(p.shape[1] for p in parts)
+        ref.append(torch.cat(parts + [torch.zeros(B, Cp - creal, H, W)], dim=1))
+    ref = nhwc(torch.cat(ref, dim=0))
+    imgd = [t.to(dev) for t in imgs] if nimg else None
+    lbld = [t.to(dev) for t in lbls]
+    arr = lambda ts: (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts])
+    out = torch.full((S * B, H, W, Cp), float("nan"), device=dev)
+    amax = torch.full((S * B,), -1, dtype=torch.int32, device=dev)
+    _check(lib, lib.tsnet_op_pack_input(arr(imgd) if nimg else None, arr(lbld), S, B, H, W, L, nimg, Cp, int(coords),
+                                        (ctypes.c_float * S)(*divs) if nimg else None, out.data_ptr(), amax.data_ptr(), None))
+    _sync(dev)
+    return out.cpu(), ref, amax.cpu().view(torch.float32), ref.abs().amax(dim=(1, 2, 3))
+
+
+def upsample64_case(lib, dev, N, H, W, C, norm, seed=0):
+    """nn.Upsample(x2, bilinear, align_corners=False) [after IN + ReLU] in fp64 vs tsnet_op_upsample2x_st with fp32 storage, which must also
+    be tsnet_op_upsample2x's bits.  Returns max|d|."""
+    x = _rand(seed, "x", (N, C, H, W), -2, 2)
+    al = _rand(seed, "al", (N, C), 0.5, 1.5) if norm else None
+    be = _rand(seed, "be", (N, C), -0.3, 0.3) if norm else None
+    xin = x.double()
+    if norm:
+        xin = F.relu(xin * al.double()[:, :, None, None] + be.double()[:, :, None, None])
+    ref = F.interpolate(xin, scale_factor=2, mode="bilinear", align_corners=False)
+    y = run_upsample_st(lib, dev, x, al, be, 0, 0)
+    xd = nhwc(x).to(dev)
+    ald, bed = (al.to(dev), be.to(dev)) if norm else (None, None)
+    y0 = torch.full((N, 2 * H, 2 * W, C), float("nan"), device=dev)
+    _check(lib, lib.tsnet_op_upsample2x(xd.data_ptr(), _p(ald), _p(bed), int(norm), N, H, W, C, y0.data_ptr(), None))
+    _sync(dev)
+    assert torch.equal(y0.cpu(), y)
+    return (nchw(y).double() - ref).abs().max().item()
+
+
+def run_upsample_st(lib, dev, x, al, be, x_bf16, y_bf16):
+    """tsnet_op_upsample2x_st on an NCHW fp32 CPU tensor (stored as bf16 on the device when x_bf16: x must be representable); the NHWC output
+    on the CPU, widened to fp32 when y_bf16"""
+    N, C, H, W = x.shape
+    xd = nhwc(x).to(dev)
+    if x_bf16:
+        assert torch.equal(bf16_round(x), x)
+        xd = xd.to(torch.bfloat16)
+    ald = None if al is None else al.contiguous().to(dev)
+    bed = None if be is None else be.contiguous().to(dev)
+    y = torch.full((N, 2 * H, 2 * W, C), float("nan"), device=dev, dtype=torch.bfloat16 if y_bf16 else torch.float32)
+    _check(lib, lib.tsnet_op_upsample2x_st(xd.data_ptr(), _p(ald), _p(bed), int(al is not None), N, H, W, C, int(x_bf16), int(y_bf16), y.data_ptr(), None))
+    _sync(dev)
+    return y.cpu().float()
+
+
+def upsample_storage_case(lib, dev, N, H, W, C, norm, seed=0, ties=False):
+    """bf16 storage of the upsample's input and output.  Data: bf16-representable values in [-2, 2], or (ties=True) fp32 values where a
+    bf16 rounding is decided (bf16_tie_values: a 1 x 1 map hands every one of them to the output unchanged).  Returns the pairs that must be
+    equal bits: (bf16 input, the same values as fp32), (bf16 output, bf16_round of the fp32 output), (both, bf16_round of the fp32 output)."""
+    al = _rand(seed, "al", (N, C), 0.5, 1.5) if norm else None
+    be = _rand(seed, "be", (N, C), -0.3, 0.3) if norm else None
+    x = bf16_tie_values(seed, "xt", (N, C, H, W), -20, 20) if ties else bf16_round(_rand(seed, "x", (N, C, H, W), -2, 2))
+    y32 = run_upsample_st(lib, dev, x, al, be, 0, 0)
+    pairs = [(run_upsample_st(lib, dev, x, al, be, 0, 1), bf16_round(y32))]
+    if not ties:                                                            # (the ties themselves are not bf16 values)
+        pairs += [(run_upsample_st(lib, dev, x, al, be, 1, 0), y32), (run_upsample_st(lib, dev, x, al, be, 1, 1), bf16_round(y32))]
+    return pairs
+
+
+def op_refusals(lib, dev, op):
+    """the bad arguments of one of the new operators: each call must return TSNET_ERR_ARG with a message of its own and leave the
+    NaN-filled outputs untouched (the host code refuses before anything is launched).  Returns the number of refusals walked."""
+    import ctypes
+    z = torch.zeros(4096, device=dev)
+    zd = torch.zeros(4096, dtype=torch.float64, device=dev)
+    outs = [torch.full((4096,), float("nan"), device=dev) for _ in range(3)]
+    p, o = z.data_ptr(), [t.data_ptr() for t in outs]
+    ptrs = lambda *v: (ctypes.c_void_p * 8)(*v)
+    two = ptrs(p, p)
+    div = (ctypes.c_float * 8)(255.0, 255.0)
+    if op == "warp_k_shared":       # (src, flow, B, K, SB, h, w, C, out)
+        fn, good = lib.tsnet_op_warp_k_shared, [p, p, 2, 2, 2, 4, 4, 8, o[0], None]
+        bad = [{0: None}, {1: None}, {8: None}, {7: 6}, {7: 0}, {3: 0}, {3: 9}, {4: 0}, {2: 3, 4: 2}, {2: 0}, {5: 0}]
+    elif op == "add_stats":         # (x, add, add_nmod, x_sb, N, HW, C, y, alpha, beta)
+        fn, good = lib.tsnet_op_add_stats, [p, p, 2, 2, 4, 4, 8, o[0], o[1], o[2], None]
+        bad = [{0: None}, {1: None}, {7: None}, {8: None}, {9: None}, {6: 6}, {6: 0}, {2: 3}, {2: 0}, {3: 0}, {2: 4, 3: 3}, {4: 0}, {5: 0}]
+    elif op == "finalize_stats":    # (part, N, S, C, HW, alpha, beta)
+        fn, good = lib.tsnet_op_finalize_stats, [zd.data_ptr(), 2, 4, 8, 16, o[0], o[1], None]
+        bad = [{0: None}, {5: None}, {6: None}, {3: 6}, {3: 0}, {2: 0}, {4: 0}, {1: 0}]
+    elif op == "fuse_tail":         # (src, tar, y2, alpha, beta, B, K, SB, P, C1, zbar)
+        fn, good = lib.tsnet_op_fuse_tail, [p, p, p, p, p, 2, 2, 2, 4, 8, o[0], None]
+        bad = [{i: None} for i in (0, 1, 2, 3, 4, 10)] + [{9: 6}, {9: 0}, {6: 0}, {6: 9}, {7: 0}, {5: 3, 7: 2}, {8: 0}, {5: 0}]
+    elif op == "pack_input":        # (img, lbl, S, B, H, W, L, nimg, Cp, coords, img_div, out, amax)
+        fn, good = lib.tsnet_op_pack_input, [two, two, 2, 1, 4, 4, 2, 3, 8, 1, div, o[0], o[1], None]
+        bad = [{0: None}, {1: None}, {10: None}, {11: None}, {12: None}, {0: ptrs(p, None)}, {1: ptrs(None, p)}, {2: 0}, {2: 9}, {7: 1}, {8: 7}, {6: 3},
+               {8: 24}, {9: 0, 8: 4}, {3: 0}, {4: 0}, {6: 0}, {10: (ctypes.c_float * 8)(255.0, 0.0)}, {7: 0, 8: 4}, {7: 0, 6: 25, 8: 24}]
+    elif op == "upsample2x_st":     # (x, alpha, beta, relu, N, H, W, C, x_bf16, y_bf16, y)
+        fn, good = lib.tsnet_op_upsample2x_st, [p, None, None, 0, 1, 4, 4, 8, 0, 0, o[0], None]
+        bad = [{0: None}, {10: None}, {1: p}, {7: 6}, {7: 0}, {4: 0}, {5: 0}, {6: 0}]
+    else:
+        raise AssertionError(op)
+    for change in bad:
+        args = list(good)
+        for i, v in change.items():
+            args[i] = v
+        rc = fn(*args)
+        msg = lib.tsnet_op_last_error().decode()
+        _sync(dev)
+        assert rc == TSNET_ERR_ARG and msg, (op, change, rc, msg)
+        assert all(torch.isnan(t).all().item() for t in outs), (op, change)
+    return len(bad)
+
+
+# the shapes both tiers run: the smallest at which each kernel can still go wrong
+WARP_K_SHAPES = [(2, 3, 16, 12, 128), (1, 8, 7, 9, 16), (3, 2, 32, 32, 64),         # (B, K, h, w, C)
+                 (5, 1, 32, 32, 512)]                                               # 2560 blocks of 256 quads: the grid-stride loop (2048 blocks) repeats
+FUSE_TAIL_SHAPES = [(2, 3, 7 * 9, 16), (1, 8, 16, 8), (3, 2, 64, 512),              # (B, K, P, C1)
+                    (2, 2, 1040, 512)]                                              # 2080 blocks: the loop repeats, the last pass ragged
+ADD_STATS_CASES = {                                                                 # (K, B, x_sb, HW, C): N = K*B, add_nmod = B
+    "per_frame_sources": (3, 2, 2, 35, 16),
+    "shared_sources": (3, 2, 1, 35, 16),
+    "c1024_hw64": (2, 2, 2, 64, 1024),          # 8 splits: the last size in_finalize takes
+    "c1024_hw72": (2, 2, 1, 72, 1024),          # 9 splits: in_finalize2 with a ragged first batch
+    "c1024_hw520": (2, 1, 1, 520, 1024),        # the 64-split cap (58 splits of 9 rows): in_finalize2
+    "c24_hw27": (2, 2, 2, 27, 24),
+    "hw1": (3, 2, 1, 1, 16),
+}
+PACK_CASES = {                                                                      # (S, B, H, W, L, nimg, Cp, coords, divisors)
+    "face_coords_s3": (3, 2, 24, 20, 2, 3, 8, True, (255.0, 1.0, 255.0)),           # S*B = 6, no padding channel
+    "face_no_coords": (1, 2, 24, 20, 2, 3, 8, False, None),                         # three padding channels
+    "pose": (2, 1, 24, 20, 25, 3, 32, True, None),
+    "label_only_face": (1, 2, 24, 20, 2, 0, 8, True, None),
+    "label_only_pose": (1, 2, 24, 20, 25, 0, 32, True, None),
+    "frame_192": (1, 2, 192, 192, 2, 3, 8, True, None),                             # 144 blocks of pixels per image: the loop (128 blocks) repeats
+}
+UPSAMPLE_SHAPES = [(1, 1, 1, 8), (1, 1, 9, 8), (2, 5, 1, 16), (1, 3, 72, 512)]      # (N, H, W, C); the last: 72 blocks per output row (64 launched)
+INSTNORM_EDGES = {                                                                  # instnorm_case's (N, H, W, C, relu, resid, seed)
+    "loop_fixed_quad": (64, 32, 32, 128, True, False, 0),       # 128 blocks of quads per image, 64 launched (4096 / N): two passes
+    "loop_moving_quad": (4096, 10, 10, 24, True, False, 1),     # one block per image, three passes, the channel quad advances by 256 % 6 = 4
+    "c2048": (2, 4, 4, 2048, False, False, 2),                  # statistics: blockIdx.z = 0, 1
+    "c1040": (2, 4, 4, 1040, True, False, 3),                   # C / 4 = 260: four columns left to the second block
+}
+OPS_WITH_REFUSALS = ("warp_k_shared", "add_stats", "finalize_stats", "fuse_tail", "pack_input", "upsample2x_st")

@@ -345,3 +345,93 @@ def test_conv_w1_winograd_x_form(emu_lib):
     assert oc.conv_w1_case(emu_lib, "cpu", 1, 8, 32, 64, 128, False, bias=False) < REL
     assert oc.conv_w1_case(emu_lib, "cpu", 1, 4, 32, 32, 64, True, scale=300.0) < REL
     assert oc.conv_w1_case(emu_lib, "cpu", 1, 4, 32, 32, 64, True, norm=True, nprod=1) < 2e-2
+
+
+# ---- the kernels between the convolutions, one operator at a time (op_cases.py: fp64 references; tests/test_gpu_ops.py runs the same cases)
+@pytest.mark.parametrize("B,K,h,w,C", oc.WARP_K_SHAPES)
+def test_warp_k_sources(emu_lib, B, K, h, w, C):
+    """warp_mean_kernel with K sources per frame (image k*B + b), the mean over sources, the grid-stride loop"""
+    assert oc.warp_k_case(emu_lib, "cpu", B, K, h, w, C) < TOL
+
+
+def test_warp_k_hand_placed_flows(emu_lib):
+    """sample positions on pixel centres, on the outermost positions, one and several pixels outside on every side and in the corners"""
+    assert oc.warp_k_case(emu_lib, "cpu", 2, 3, 16, 12, 16, hand=True) < TOL
+
+
+def test_warp_k_shared_sources(emu_lib):
+    """one source set shared by the batch (SB = 1) gives the bits of the replicated set (SB = B), and matches fp64"""
+    a, b, err = oc.warp_k_shared_case(emu_lib, "cpu", 3, 2, 7, 9, 16)
+    assert torch.equal(a, b) and err < TOL
+
+
+def test_warp_entry_points_agree_for_one_source(emu_lib):
+    one, k, shared = oc.warp_one_source_entries(emu_lib, "cpu", 2, 7, 9, 16)
+    assert torch.equal(one, k) and torch.equal(one, shared)
+
+
+@pytest.mark.parametrize("B,K,P,C1", oc.FUSE_TAIL_SHAPES)
+def test_fuse_tail(emu_lib, B, K, P, C1):
+    """fuse_resid_mean_kernel: both halves of the concat, alpha / beta per (source, frame, channel), the division by K, the loop"""
+    assert oc.fuse_tail_case(emu_lib, "cpu", B, K, P, C1) < TOL
+
+
+def test_fuse_tail_shared_sources(emu_lib):
+    a, b, err = oc.fuse_tail_shared_case(emu_lib, "cpu", 3, 2, 7 * 9, 16)
+    assert torch.equal(a, b) and err < TOL
+
+
+@pytest.mark.parametrize("case", list(oc.ADD_STATS_CASES))
+def test_add_stats(emu_lib, case):
+    """add_stats_partial_kernel + finalize: the stored sum is torch's fp32 x + add bit for bit, its statistics normalise it as fp64 does"""
+    y, yref, err = oc.add_stats_case(emu_lib, "cpu", *oc.ADD_STATS_CASES[case])
+    assert torch.equal(y, yref) and err < TOL
+
+
+def test_add_stats_large_mean(emu_lib):
+    y, yref, err = oc.add_stats_case(emu_lib, "cpu", 3, 2, 1, 256, 8, offset=300.0)
+    assert torch.equal(y, yref) and err < 2e-3       # test_instnorm_large_mean's tolerance
+
+
+def test_finalize_stats(emu_lib):
+    """in_finalize / in_finalize2 on partials made on the CPU: S from 1 to 1024 around every batch boundary of the 16 groups x 8 loads,
+    C = 24 leaving a half-used last block"""
+    worst = oc.finalize_worst(emu_lib, "cpu")
+    for k, (ea, eb) in worst.items():
+        print(f"{k}: worst alpha {ea:.2e} relative, beta {eb:.2e} of |beta| + alpha")
+    assert max(max(v) for v in worst.values()) < oc.FINALIZE_TOL
+
+
+@pytest.mark.parametrize("case", list(oc.PACK_CASES))
+def test_pack_input(emu_lib, case):
+    """pack_input_kernel: every channel kind, both forms, per-source divisors, the per-image amax: equal bits"""
+    out, ref, amax, amax_ref = oc.pack_case(emu_lib, "cpu", *oc.PACK_CASES[case])
+    assert torch.equal(out, ref) and torch.equal(amax, amax_ref)
+
+
+@pytest.mark.parametrize("N,H,W,C", oc.UPSAMPLE_SHAPES)
+@pytest.mark.parametrize("norm", [False, True])
+def test_upsample_fp64(emu_lib, N, H, W, C, norm):
+    assert oc.upsample64_case(emu_lib, "cpu", N, H, W, C, norm) < TOL
+
+
+@pytest.mark.parametrize("norm", [False, True])
+def test_upsample_bf16_storage(emu_lib, norm):
+    """bf16 storage of the input (exact widening), of the output (round to nearest even, ties included) and of both: equal bits"""
+    pairs = oc.upsample_storage_case(emu_lib, "cpu", 2, 5, 7, 16, norm) + oc.upsample_storage_case(emu_lib, "cpu", 1, 3, 72, 512, norm, seed=1)
+    pairs += oc.upsample_storage_case(emu_lib, "cpu", 4, 1, 1, 256, False, seed=2, ties=True)
+    assert all(torch.equal(a, b) for a, b in pairs), [torch.equal(a, b) for a, b in pairs]
+
+
+@pytest.mark.parametrize("case", list(oc.INSTNORM_EDGES))
+def test_norm_act_grid_stride_and_stats_edges(emu_lib, case):
+    """norm_act's loop repeating (with a fixed channel quad, and with one that advances per pass) and statistics of more than 1024 channels
+    (op_cases.INSTNORM_EDGES)"""
+    assert oc.instnorm_case(emu_lib, "cpu", *oc.INSTNORM_EDGES[case]) < TOL
+
+
+@pytest.mark.parametrize("op", oc.OPS_WITH_REFUSALS)
+def test_new_operator_refusals(emu_lib, op):
+    """TSNET_ERR_ARG, a message and untouched outputs for null tensors, C not a multiple of 4, K outside 1..8, extents that do not divide,
+    a bad Cp, S < 1 and HW < 1"""
+    assert oc.op_refusals(emu_lib, "cpu", op) >= 8

@@ -140,6 +140,96 @@ def test_warp_out_of_range(lib):
     assert oc.warp_case(lib, DEV, 2, 16, 12, 128) < TOL
 
 
+# ---- the kernels between the convolutions, one operator at a time (op_cases.py: fp64 references; tests/test_emu_ops.py runs the same cases under the emulator)
+@pytest.mark.parametrize("B,K,h,w,C", oc.WARP_K_SHAPES)
+def test_warp_k_sources(lib, B, K, h, w, C):
+    """warp_mean_kernel with K sources per frame (image k*B + b), the mean over sources, the grid-stride loop"""
+    assert oc.warp_k_case(lib, DEV, B, K, h, w, C) < TOL
+
+
+def test_warp_k_hand_placed_flows(lib):
+    """sample positions on pixel centres, on the outermost positions, one and several pixels outside on every side and in the corners"""
+    assert oc.warp_k_case(lib, DEV, 2, 3, 16, 12, 16, hand=True) < TOL
+
+
+def test_warp_k_shared_sources(lib):
+    """one source set shared by the batch (SB = 1) gives the bits of the replicated set (SB = B), and matches fp64"""
+    a, b, err = oc.warp_k_shared_case(lib, DEV, 3, 2, 7, 9, 16)
+    assert torch.equal(a, b) and err < TOL
+
+
+def test_warp_entry_points_agree_for_one_source(lib):
+    one, k, shared = oc.warp_one_source_entries(lib, DEV, 2, 7, 9, 16)
+    assert torch.equal(one, k) and torch.equal(one, shared)
+
+
+@pytest.mark.parametrize("B,K,P,C1", oc.FUSE_TAIL_SHAPES)
+def test_fuse_tail(lib, B, K, P, C1):
+    """fuse_resid_mean_kernel: both halves of the concat, alpha / beta per (source, frame, channel), the division by K, the loop"""
+    assert oc.fuse_tail_case(lib, DEV, B, K, P, C1) < TOL
+
+
+def test_fuse_tail_shared_sources(lib):
+    a, b, err = oc.fuse_tail_shared_case(lib, DEV, 3, 2, 7 * 9, 16)
+    assert torch.equal(a, b) and err < TOL
+
+
+@pytest.mark.parametrize("case", list(oc.ADD_STATS_CASES))
+def test_add_stats(lib, case):
+    """add_stats_partial_kernel + finalize: the stored sum is torch's fp32 x + add bit for bit, its statistics normalise it as fp64 does"""
+    y, yref, err = oc.add_stats_case(lib, DEV, *oc.ADD_STATS_CASES[case])
+    assert torch.equal(y, yref) and err < TOL
+
+
+def test_add_stats_large_mean(lib):
+    y, yref, err = oc.add_stats_case(lib, DEV, 3, 2, 1, 256, 8, offset=300.0)
+    assert torch.equal(y, yref) and err < 2e-3       # test_instnorm_large_mean's tolerance
+
+
+def test_finalize_stats(lib):
+    """in_finalize / in_finalize2 on partials made on the CPU: S from 1 to 1024 around every batch boundary of the 16 groups x 8 loads,
+    C = 24 leaving a half-used last block"""
+    worst = oc.finalize_worst(lib, DEV)
+    for k, (ea, eb) in worst.items():
+        print(f"{k}: worst alpha {ea:.2e} relative, beta {eb:.2e} of |beta| + alpha")
+    assert max(max(v) for v in worst.values()) < oc.FINALIZE_TOL
+
+
+@pytest.mark.parametrize("case", list(oc.PACK_CASES))
+def test_pack_input(lib, case):
+    """pack_input_kernel: every channel kind, both forms, per-source divisors, the per-image amax: equal bits"""
+    out, ref, amax, amax_ref = oc.pack_case(lib, DEV, *oc.PACK_CASES[case])
+    assert torch.equal(out, ref) and torch.equal(amax, amax_ref)
+
+
+@pytest.mark.parametrize("N,H,W,C", oc.UPSAMPLE_SHAPES)
+@pytest.mark.parametrize("norm", [False, True])
+def test_upsample_fp64(lib, N, H, W, C, norm):
+    assert oc.upsample64_case(lib, DEV, N, H, W, C, norm) < TOL
+
+
+@pytest.mark.parametrize("norm", [False, True])
+def test_upsample_bf16_storage(lib, norm):
+    """bf16 storage of the input (exact widening), of the output (round to nearest even, ties included) and of both: equal bits"""
+    pairs = oc.upsample_storage_case(lib, DEV, 2, 5, 7, 16, norm) + oc.upsample_storage_case(lib, DEV, 1, 3, 72, 512, norm, seed=1)
+    pairs += oc.upsample_storage_case(lib, DEV, 4, 1, 1, 256, False, seed=2, ties=True)
+    assert all(torch.equal(a, b) for a, b in pairs), [torch.equal(a, b) for a, b in pairs]
+
+
+@pytest.mark.parametrize("case", list(oc.INSTNORM_EDGES))
+def test_norm_act_grid_stride_and_stats_edges(lib, case):
+    """norm_act's loop repeating (with a fixed channel quad, and with one that advances per pass) and statistics of more than 1024 channels
+    (op_cases.INSTNORM_EDGES)"""
+    assert oc.instnorm_case(lib, DEV, *oc.INSTNORM_EDGES[case]) < TOL
+
+
+@pytest.mark.parametrize("op", oc.OPS_WITH_REFUSALS)
+def test_new_operator_refusals(lib, op):
+    """TSNET_ERR_ARG, a message and untouched outputs for null tensors, C not a multiple of 4, K outside 1..8, extents that do not divide,
+    a bad Cp, S < 1 and HW < 1"""
+    assert oc.op_refusals(lib, DEV, op) >= 8
+
+
 # ---- fp16x2 patch kernel with the producer's IN + ReLU fused into the staging (conv_h2.hpp); error relative to max|fp64 reference|
 @pytest.mark.parametrize("norm", [False, True])
 def test_conv_h2_layers(lib, norm):

@@ -28,7 +28,7 @@ ABI_SYMBOLS = (
     "tsnet_forward", "tsnet_set_source_divisors", "tsnet_set_sources", "tsnet_set_sources_shared", "tsnet_forward_target", "tsnet_train_extras", "tsnet_stage_ptr",
     "tsnet_forward_macs", "tsnet_timing_enable", "tsnet_timing_read",
     "tsnet_op_conv2d", "tsnet_op_conv2d_cat", "tsnet_op_head", "tsnet_op_instnorm_stats", "tsnet_op_norm_act", "tsnet_op_upsample2x",
-    "tsnet_op_flow", "tsnet_op_flow_k", "tsnet_flow_plan", "tsnet_op_warp", "tsnet_op_warp_k", "tsnet_op_last_error", "tsnet_frame_stats", "tsnet_demo_postprocess", "tsnet_fit_face_curves", "tsnet_raster_face", "tsnet_vl2ch", "tsnet_fit_pose_curves", "tsnet_raster_pose", "tsnet_label_bbox", "tsnet_resize_pad", "tsnet_resize_label", "tsnet_bench_conv", "tsnet_debug_counters", "tsnet_linspace", "tsnet_coord_table",
+    "tsnet_op_flow", "tsnet_op_flow_k", "tsnet_flow_plan", "tsnet_op_warp", "tsnet_op_warp_k", "tsnet_op_warp_k_shared", "tsnet_op_add_stats", "tsnet_op_finalize_stats", "tsnet_op_fuse_tail", "tsnet_op_pack_input", "tsnet_op_upsample2x_st", "tsnet_op_last_error", "tsnet_frame_stats", "tsnet_demo_postprocess", "tsnet_fit_face_curves", "tsnet_raster_face", "tsnet_vl2ch", "tsnet_fit_pose_curves", "tsnet_raster_pose", "tsnet_label_bbox", "tsnet_resize_pad", "tsnet_resize_label", "tsnet_bench_conv", "tsnet_debug_counters", "tsnet_linspace", "tsnet_coord_table",
     "tsnet_bicubic_taps", "tsnet_bicubic_table", "tsnet_prepare_frames",
     "tsnet_face_adapt_stats", "tsnet_face_adapt_apply", "tsnet_smooth_keypoints",
 )
@@ -87,6 +87,13 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.tsnet_op_warp.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]
     if hasattr(lib, "tsnet_op_warp_k"):          # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
         lib.tsnet_op_warp_k.argtypes = [_vp, _vp] + [C.c_int] * 5 + [_vp, C.c_int, _fp, _vp]
+    if hasattr(lib, "tsnet_op_fuse_tail"):       # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_op_warp_k_shared.argtypes = [_vp, _vp] + [C.c_int] * 6 + [_vp, _vp]
+        lib.tsnet_op_add_stats.argtypes = [_vp, _vp] + [C.c_int] * 5 + [_vp, _vp, _vp, _vp]
+        lib.tsnet_op_finalize_stats.argtypes = [_vp] + [C.c_int] * 4 + [_vp, _vp, _vp]
+        lib.tsnet_op_fuse_tail.argtypes = [_vp] * 5 + [C.c_int] * 5 + [_vp, _vp]
+        lib.tsnet_op_pack_input.argtypes = [pp, pp] + [C.c_int] * 8 + [_fp, _vp, _vp, _vp]
+        lib.tsnet_op_upsample2x_st.argtypes = [_vp, _vp, _vp] + [C.c_int] * 7 + [_vp, _vp]
     lib.tsnet_op_last_error.restype = C.c_char_p
     lib.tsnet_frame_stats.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp]
     lib.tsnet_demo_postprocess.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _fp, _vp, _vp]

@@ -437,6 +437,21 @@ void run_warp(Ctx& ctx, const float* src, const float* flow, float* out, int B, 
     check_launch("warp_mean");
 }
 
+// Stem input assembly (pack_input_kernel) of p.S * p.B images.  `amax_clear` maxima from p.amax_out on are zeroed first: the images' own,
+// or more where the caller resets neighbouring maxima of the same forward in the one memset.  The caller opens the timing scope.
+void run_pack_input(Ctx& ctx, const PackArgs& p, size_t amax_clear) {
+    if (p.amax_out) HIP_TRY(hipMemsetAsync(p.amax_out, 0, amax_clear * sizeof(unsigned), ctx.stream));
+    hipLaunchKernelGGL(pack_input_kernel, dim3(pack_grid(p.H * p.W), p.S * p.B), dim3(256), 0, ctx.stream, p);
+    check_launch(p.nimg ? "pack_input(img)" : "pack_input(lbl)");
+}
+
+// FuseNet tail: zbar = mean over sources of cat(src_fea, tar_fea) + (y2 * alpha + beta)   (FuseTailArgs)
+void run_fuse_tail(Ctx& ctx, const FuseTailArgs& t) {
+    TimeScope ts(ctx, TSNET_T_ELEMWISE);
+    hipLaunchKernelGGL(fuse_resid_mean_kernel, dim3(ew_grid((size_t)t.B * t.P * 2 * t.C1 / 4)), dim3(256), 0, ctx.stream, t);
+    check_launch("fuse_resid_mean");
+}
+
 // weights of one layer -> operand planes + the un-scale factor; `stage` holds the OIHW parameter on the device (form 1: its transform,
 // kernel 3 x 4).  planes: 2 = fp16 (hi, lo), 1 = one bf16 plane, -1 = one fp16 plane (hi alone)
 void pack_layer(const float* stage, const ConvLayer& L, unsigned short* planes_out, int planes, float scale, hipStream_t s) {
@@ -876,10 +891,8 @@ void tsnet_engine::set_sources(Ctx& ctx, const float* const* src_img, const floa
         for (int s = 0; s < K; ++s) { p.img[s] = src_img[s]; p.lbl[s] = src_lbl[s]; p.img_div[s] = src_div[s]; }
         p.coords = cfg.addcoords ? d_coords : nullptr;
         p.out = x_img; p.S = K; p.B = B; p.H = H; p.W = W; p.L = cfg.label_nc; p.nimg = 3; p.Cp = cp_img;
-        HIP_TRY(hipMemsetAsync(amax_src(), 0, (size_t)K * B * sizeof(unsigned), ctx.stream));
         p.amax_out = amax_src();
-        hipLaunchKernelGGL(pack_input_kernel, dim3(pack_grid(H * W), K * B), dim3(256), 0, ctx.stream, p);
-        check_launch("pack_input(img)");
+        run_pack_input(ctx, p, (size_t)K * B);
         for (int s = 0; s < K; ++s)
             HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)s * Bmax * H * W, src_bbox[s], (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice,
                                    bbox_stream ? bbox_stream : ctx.stream));
@@ -905,10 +918,8 @@ void tsnet_engine::target_chain(Ctx& ctx, const float* tar_lbl, int B) {
         p.coords = cfg.addcoords ? d_coords : nullptr;
         p.out = x_lbl; p.S = 1; p.B = B; p.H = H; p.W = W; p.L = cfg.label_nc; p.nimg = 0; p.Cp = cp_lbl;
         // one reset for the three per-image maxima of this forward (target input, sg, decoder stream: contiguous)
-        HIP_TRY(hipMemsetAsync(amax_tar(), 0, (size_t)3 * Bmax * sizeof(unsigned), ctx.stream));
         p.amax_out = amax_tar();
-        hipLaunchKernelGGL(pack_input_kernel, dim3(pack_grid(H * W), B), dim3(256), 0, ctx.stream, p);
-        check_launch("pack_input(lbl)");
+        run_pack_input(ctx, p, (size_t)3 * Bmax);
     }
     encode(ctx, lbl_enc, x_lbl, amax_tar(), B, raw_lbl, tar_fea, 0);
     run_l2norm_split(ctx, tar_fea, reinterpret_cast<unsigned short*>(that), B, P, C);
@@ -952,12 +963,7 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
         ConvCall b; b.x = F1; b.alpha = s1.first; b.beta = s1.second; b.relu = 1; b.bound = sqP;
         b.N = NB; b.H = h; b.W = w; b.y = F2;
         conv_stats(ctx, fuse_c2, b, NB, P, s2.first, s2.second);
-        {
-            TimeScope ts(ctx, TSNET_T_ELEMWISE);
-            FuseTailArgs t2{X, tar_fea, F2, s2.first, s2.second, zbar, B, K, P, C, SB};
-            hipLaunchKernelGGL(fuse_resid_mean_kernel, dim3(ew_grid((size_t)B * P * 2 * C / 4)), dim3(256), 0, ctx.stream, t2);
-            check_launch("fuse_resid_mean");
-        }
+        run_fuse_tail(ctx, FuseTailArgs{X, tar_fea, F2, s2.first, s2.second, zbar, B, K, P, C, SB});
         // zbar = mean over sources of cat(src_fea, tar_fea) + IN(.): bounded by enc_bound + sqrt(P).  fuse_net.conv has no norm behind it:
         // it publishes max |sg| per image for dec.map_conv's operand scale
         ConvCall c; c.x = zbar; c.bound = enc_bound() + sqP; c.N = B; c.H = h; c.W = w; c.y = sg;
@@ -1546,6 +1552,102 @@ int tsnet_op_warp_k(const float* src_fea, const float* flow, int B, int K, int h
         const float t = ev.ms();
         if (ms_out) *ms_out = t / (float)(repeat - 1);
     }
+    OP_END
+}
+
+int tsnet_op_warp_k_shared(const float* src_fea, const float* flow, int B, int K, int SB, int h, int w, int C, float* out, void* stream) {
+    OP_BEGIN
+    if (!src_fea || !flow || !out) throw ArgError("warp op: null tensor");
+    if (C < 4 || (C & 3)) throw ArgError("warp op: C must be a multiple of 4");
+    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape (1 <= K <= 8 sources, B, h, w >= 1)");
+    if (SB < 1 || B % SB) throw ArgError("warp op: the source-batch extent must divide the batch");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    run_warp(ctx, src_fea, flow, out, B, K, h, w, C, SB);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    OP_END
+}
+
+int tsnet_op_add_stats(const float* x, const float* add, int add_nmod, int x_sb, int N, int HW, int C, float* y, float* alpha, float* beta, void* stream) {
+    OP_BEGIN
+    if (!x || !add || !y || !alpha || !beta) throw ArgError("add_stats op: null tensor");
+    if (C < 4 || (C & 3)) throw ArgError("add_stats op: C must be a multiple of 4");
+    if (N < 1 || N > 65535 || HW < 1) throw ArgError("add_stats op: bad shape (1 <= N <= 65535, HW >= 1)");
+    if (add_nmod < 1 || N % add_nmod) throw ArgError("add_stats op: add_nmod must divide N");
+    if (x_sb < 1 || add_nmod % x_sb) throw ArgError("add_stats op: the source-batch extent must divide add_nmod");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    DevBufs mem;
+    double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
+    run_add_stats(ctx, x, add, add_nmod, y, N, HW, C, part, alpha, beta, x_sb);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    OP_END
+}
+
+int tsnet_op_finalize_stats(const double* part, int N, int S, int C, int HW, float* alpha, float* beta, void* stream) {
+    OP_BEGIN
+    if (!part || !alpha || !beta) throw ArgError("finalize op: null tensor");
+    if (C < 4 || (C & 3)) throw ArgError("finalize op: C must be a multiple of 4");
+    if (N < 1 || N > 65535 || S < 1 || HW < 1) throw ArgError("finalize op: bad shape (1 <= N <= 65535, S >= 1, HW >= 1)");
+    launch_finalize(part, alpha, beta, N, C, S, HW, (hipStream_t)stream);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    OP_END
+}
+
+int tsnet_op_fuse_tail(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
+                       int B, int K, int SB, int P, int C1, float* zbar, void* stream) {
+    OP_BEGIN
+    if (!src_fea || !tar_fea || !y2 || !alpha || !beta || !zbar) throw ArgError("fuse_tail op: null tensor");
+    if (C1 < 4 || (C1 & 3)) throw ArgError("fuse_tail op: C1 must be a multiple of 4");
+    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || P < 1) throw ArgError("fuse_tail op: bad shape (1 <= K <= 8 sources, B, P >= 1)");
+    if (SB < 1 || B % SB) throw ArgError("fuse_tail op: the source-batch extent must divide the batch");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    run_fuse_tail(ctx, FuseTailArgs{src_fea, tar_fea, y2, alpha, beta, zbar, B, K, P, C1, SB});
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    OP_END
+}
+
+int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S, int B, int H, int W, int L, int nimg, int Cp, int coords,
+                        const float* img_div, float* out, unsigned int* amax, void* stream) {
+    OP_BEGIN
+    if (S < 1 || S > TSNET_MAX_SOURCES) throw ArgError("pack op: 1 <= S <= 8 sources");
+    if (!lbl || !out || !amax) throw ArgError("pack op: null tensor");
+    if (nimg != 0 && nimg != 3) throw ArgError("pack op: nimg is 3 (image + label) or 0 (label only)");
+    if (nimg && (!img || !img_div)) throw ArgError("pack op: null tensor");
+    for (int s = 0; s < S; ++s) {
+        if (!lbl[s] || (nimg && !img[s])) throw ArgError("pack op: null tensor");
+        if (nimg && !(img_div[s] > 0.f)) throw ArgError("pack op: the image divisors must be positive");
+    }
+    if (B < 1 || (size_t)S * B > 65535 || H < 1 || W < 1 || L < 1) throw ArgError("pack op: bad shape (B, H, W, L >= 1, S * B <= 65535)");
+    if (coords && (H < 2 || W < 2)) throw ArgError("pack op: the coordinate table needs H, W >= 2");
+    const int creal = nimg + L + (coords ? 3 : 0);
+    if (Cp < creal) throw ArgError("pack op: Cp is smaller than the real channel count");
+    if (Cp != conv_cin_pad(Cp)) throw ArgError("pack op: Cp must be 8 or a multiple of 16");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    DevBufs mem;
+    PackArgs p{};
+    for (int s = 0; s < S; ++s) { p.img[s] = nimg ? img[s] : nullptr; p.lbl[s] = lbl[s]; p.img_div[s] = nimg ? img_div[s] : 1.f; }
+    if (coords) {                                   // as tsnet_finalize builds d_coords
+        std::vector<float> t((size_t)H * W * 3);
+        coord_table(H, W, t.data());
+        float* d = mem.alloc<float>(t.size() * sizeof(float));
+        HIP_TRY(hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+        p.coords = d;
+    }
+    p.out = out; p.S = S; p.B = B; p.H = H; p.W = W; p.L = L; p.nimg = nimg; p.Cp = Cp; p.amax_out = amax;
+    run_pack_input(ctx, p, (size_t)S * B);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    OP_END
+}
+
+int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta, int relu, int N, int H, int W, int C, int x_bf16, int y_bf16,
+                           float* y, void* stream) {
+    OP_BEGIN
+    if (!x || !y) throw ArgError("upsample op: null tensor");
+    if (alpha && !beta) throw ArgError("upsample op: alpha without beta");
+    if (C < 4 || (C & 3)) throw ArgError("upsample op: C must be a multiple of 4");
+    if (N < 1 || H < 1 || W < 1) throw ArgError("upsample op: bad shape (N, H, W >= 1)");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    run_upsample(ctx, x, alpha, beta, relu, N, H, W, C, y, x_bf16 != 0, y_bf16 != 0);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
     OP_END
 }
 
