@@ -14,7 +14,9 @@
  *         (tsnet_last_error(NULL) returns the message of the last failed tsnet_create).
  *
  * Additions within TSNET_ABI_VERSION 5 (new entry points only; nothing that existed changed): tsnet_face_adapt_stats,
- * tsnet_face_adapt_apply, tsnet_smooth_keypoints -- the face loader's key-point preparation of a cross-identity pair.
+ * tsnet_face_adapt_apply, tsnet_smooth_keypoints -- the face loader's key-point preparation of a cross-identity pair; tsnet_bank_capacity,
+ * tsnet_bank_put, tsnet_forward_bank -- the source bank; tsnet_op_flow_k_slots, tsnet_op_warp_k_slots, tsnet_op_add_stats_slots,
+ * tsnet_op_fuse_tail_slots -- its kernels one at a time.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -26,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
+#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots); 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
 #define TSNET_MAX_SOURCES 8
 
 enum {
@@ -130,6 +132,25 @@ int tsnet_forward_target(tsnet_handle h, const float* tar_lbl, const float* tar_
 int tsnet_set_sources_shared(tsnet_handle h, const float* const* src_img, const float* const* src_lbl,
                              const float* const* src_bbox, void* stream);
 
+/* Source bank: the layout both clip modes are special cases of.  The source-side cache is seen as tsnet_bank_capacity(h) = n_source *
+ * max_batch SLOTS of one encoded source each; every driving frame of a forward names the slots it reads.
+ * tsnet_bank_put encodes `count` sources of batch 1 -- src_img[i] (1,3,H,W), src_lbl[i] (1,L,H,W), src_bbox[i] (1,H,W), i < count; div: `count`
+ *   HOST floats, the image divisors (what tsnet_set_source_divisors is to the caches above), NULL = 255 -- into slots first_slot ..
+ *   first_slot + count - 1, at 1 / n_source of a tsnet_set_sources per slot.  The first put after tsnet_forward, tsnet_set_sources*,
+ *   tsnet_set_source_divisors (they write the same buffers and drop the bank), or after none, starts an empty bank; later puts add or
+ *   replace slots and leave the others as they are.  tsnet_forward_target after a put is refused: the bank is no per-batch cache.
+ * tsnet_forward_bank runs B driving frames, each on Kc sources (1 <= Kc <= n_source, the means divide by Kc): slots = Kc*B HOST ints, entry
+ *   s*B + b the slot of source s of frame b, read before the call returns.  A slot may repeat within a frame and across frames.  Frame b of
+ *   the result has the bits of tsnet_forward at B = 1 on (the sources it names, in that order; frame b); out_flow (Kc,B,H/8,W/8,2).
+ *   TSNET_ERR_ARG, with a message naming the cause: a slot outside the bank or not filled (the slot is named), Kc or B out of range, no bank.
+ *   Both are stream-ordered like the calls above; a put enqueued behind a forward cannot overtake its reads.  tsnet_train_extras after
+ *   a bank forward returns TSNET_ERR_ARG; tsnet_stage_ptr("src_fea") then exposes every slot (capacity images, unfilled ones undefined). */
+int tsnet_bank_capacity(tsnet_handle h);
+int tsnet_bank_put(tsnet_handle h, int first_slot, int count, const float* const* src_img, const float* const* src_lbl,
+                   const float* const* src_bbox, const float* div, void* stream);
+int tsnet_forward_bank(tsnet_handle h, const int* slots, int Kc, const float* tar_lbl, const float* tar_bbox,
+                       float* out_rgb, float* out_flow, int B, void* stream);
+
 /* Training-mode extras of the forward (model/TSNet.py:327-331, 372-390, 402-405), computed
  * from the flows and features the LAST tsnet_forward / tsnet_forward_target left in the engine -- call it right after that
  * forward, same B, same source images.  src_img: n_source x (B,3,H,W) raw (the /255 of set_train_input is applied inside);
@@ -141,7 +162,7 @@ int tsnet_train_extras(tsnet_handle h, const float* const* src_img, const float*
                        float* warp_src_img, float* losses, void* stream);
 
 /* Device copies of the stage tensors of the last forward, for stage-wise parity tests
- * (NHWC fp32).  name: "src_fea" (K*B,h,w,c; n = i*B+b -- K images after a forward on a shared source set), "tar_fea" (B,h,w,c), "pg", "sg" (B,h,w,c),
+ * (NHWC fp32).  name: "src_fea" (K*B,h,w,c; n = i*B+b -- K images after a forward on a shared source set, every slot after one on a source bank), "tar_fea" (B,h,w,c), "pg", "sg" (B,h,w,c),
  * "dec_map" (B,h,w,c), "dec_up<i>" (B, h<<(i+1), w<<(i+1), c>>(i+1)): RAW output of the i-th decoder
  * up-convolution, before its InstanceNorm + ReLU.  Returns the element count through *count. */
 int tsnet_stage_ptr(tsnet_handle h, const char* name, const float** dev_ptr, size_t* count);
@@ -224,6 +245,11 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  *   amax (S*B): zeroed, then max |out| per image as float bits -- what fixes the stem's operand scale.
  * tsnet_op_upsample2x_st <- tsnet_op_upsample2x in the bf16 storage mode (tsnet_cfg.operand_mode = 2): x_bf16 / y_bf16 != 0: x / y hold bf16
  *   (widened exactly on load; the fp32 result rounded to nearest even on store).
+ * tsnet_op_flow_k_slots, tsnet_op_warp_k_slots, tsnet_op_add_stats_slots, tsnet_op_fuse_tail_slots <- tsnet_op_flow_k, tsnet_op_warp_k_shared,
+ *   tsnet_op_add_stats, tsnet_op_fuse_tail as a source-bank forward runs them: the source-side tensor (src_fea and, for the flow, src_bbox; x of
+ *   add_stats) holds n_src images, and slots -- HOST ints, one per (source k, frame b) pair, entry k*B + b (add_stats: one per image n) -- names
+ *   the image each pair reads, in place of the siblings' SB / x_sb expression.  Everything else as the sibling; a slot outside 0 .. n_src - 1
+ *   returns TSNET_ERR_ARG.
  * The entry points from tsnet_op_warp_k_shared on check their arguments on the host and return TSNET_ERR_ARG, with a message and nothing
  * launched, for a null tensor, a channel count that is not a multiple of 4, K outside 1..8, an extent that does not divide, a bad Cp, S < 1
  * or HW < 1; they return after the stream has drained.
@@ -258,6 +284,15 @@ int tsnet_op_add_stats(const float* x, const float* add, int add_nmod, int x_sb,
 int tsnet_op_finalize_stats(const double* part, int N, int S, int C, int HW, float* alpha, float* beta, void* stream);
 int tsnet_op_fuse_tail(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
                        int B, int K, int SB, int P, int C1, float* zbar, void* stream);
+int tsnet_op_flow_k_slots(const float* tar_fea, const float* src_fea, const float* tar_bbox, const float* src_bbox,
+                          int B, int K, int h, int w, int C, int H, int W, float* flow, int variant, int repeat, float* ms_out,
+                          const int* slots, int n_src, void* stream);
+int tsnet_op_warp_k_slots(const float* src_fea, const float* flow, int B, int K, int h, int w, int C, float* out,
+                          const int* slots, int n_src, void* stream);
+int tsnet_op_add_stats_slots(const float* x, const float* add, int add_nmod, int N, int HW, int C,
+                             float* y, float* alpha, float* beta, const int* slots, int n_src, void* stream);
+int tsnet_op_fuse_tail_slots(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
+                             int B, int K, int P, int C1, float* zbar, const int* slots, int n_src, void* stream);
 int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S, int B, int H, int W, int L, int nimg, int Cp, int coords,
                         const float* img_div, float* out, unsigned int* amax, void* stream);
 int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta, int relu,

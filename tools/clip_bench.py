@@ -3,7 +3,14 @@
 
     --shared            ONE source set of batch 1 for the B driving frames (tsnet_set_sources_shared): K encoded images instead of K * B
     --compare ROUNDS    one process, interleaved rounds of (a) the per-batch cache on replicated sources, (b) the shared cache, (c) a B = 1
-                        loop over the same B frames; one JSON line with the per-round figures, their medians and the spread of (a)"""
+                        loop over the same B frames; one JSON line with the per-round figures, their medians and the spread of (a)
+    --bank [--lib2 SO [--lib2-first]] [--rounds R]
+                        the source bank (tsnet_bank_put / tsnet_forward_bank), one process, interleaved rounds, one JSON line:
+                        (1) with --lib2 (another build of the same ABI, e.g. the parent commit's): the one-shot forward and the shared cache's
+                            forward_target at B = 4 on both libraries, with each library's own spread over the rounds;
+                        (2) forward_bank with the identity table against forward_target on the shared cache;
+                        (3) bank_put of ONE slot against a full set_sources (K = 3 images), and four source sets x one driving frame as one
+                            forward_bank(B = 4) against four forward_bank(B = 1) calls"""
 import os, sys, time, json, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,6 +20,93 @@ B, H, W = 4, 256, 256
 NB = int(sys.argv[sys.argv.index("--n-blocks") + 1]) if "--n-blocks" in sys.argv else 0
 if "--batch" in sys.argv:
     B = int(sys.argv[sys.argv.index("--batch") + 1])
+
+
+def bank_bench():
+    import ctypes
+    from wacv23_tsnet_amd import _lib
+    rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5
+    lib2 = sys.argv[sys.argv.index("--lib2") + 1] if "--lib2" in sys.argv else None
+    K = 3
+
+    def engine(lib=None):
+        e = TSNetEngine(label_nc=2, n_blocks=NB, n_downsampling=3, n_source=K, height=H, width=W, max_batch=B, lib=lib)
+        e.load_state_dict(synth.state_dict(e.param_shapes(), seed=0)); e.finalize("cuda")
+        return e
+
+    dev = lambda x: [t.cuda() for t in x] if isinstance(x, list) else x.cuda()
+    si, sl, sb, tl, tb = [dev(x) for x in synth.inputs(K, 2, B, H, W, seed=1)]                 # per-batch sources + B driving frames
+    one = lambda ts, b=0: [t[b:b + 1] for t in ts]                                              # source set b, batch 1
+    sets = [(one(si, b), one(sl, b), one(sb, b)) for b in range(B)]                             # B source sets ("identities") of K images
+
+    def ms(step, N=20, warm=3):
+        for _ in range(warm): step()
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(N): step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / N * 1e3
+
+    def table(runs):
+        """{name: [ms per round]} -> {name: {median, spread (max - min over the rounds)}}"""
+        return {k: {"median_ms": round(statistics.median(v), 4), "spread_ms": round(max(v) - min(v), 4), "per_round_ms": [round(x, 4) for x in v]} for k, v in runs.items()}
+
+    out = {"batch": B, "n_blocks": NB, "rounds": rounds, "lib2_first": "--lib2-first" in sys.argv}
+    eng = engine()
+    # (1) legacy paths, this library against --lib2
+    if lib2:
+        engs = {"this": eng, "lib2": engine(_lib.bind(ctypes.CDLL(lib2)))}
+        if "--lib2-first" in sys.argv:                       # which library goes first in a round: an order effect shows as a sign change
+            engs = dict(reversed(list(engs.items())))
+        runs = {f"{w} {k}": [] for w in ("forward", "shared forward_target") for k in engs}
+        for r in range(rounds + 1):
+            for k, e in engs.items():
+                t = ms(lambda: e.forward(si, sl, sb, tl, tb))
+                if r: runs[f"forward {k}"].append(t)
+            for k, e in engs.items():
+                e.set_sources(*sets[0], shared=True)
+                t = ms(lambda: e.forward_target(tl, tb))
+                if r: runs[f"shared forward_target {k}"].append(t)
+        out["legacy_this_vs_lib2"] = table(runs)
+        for w in ("forward", "shared forward_target"):
+            a, b = out["legacy_this_vs_lib2"][f"{w} this"], out["legacy_this_vs_lib2"][f"{w} lib2"]
+            out["legacy_this_vs_lib2"][f"{w}: this - lib2, % of lib2"] = round((a["median_ms"] - b["median_ms"]) / b["median_ms"] * 100, 3)
+            out["legacy_this_vs_lib2"][f"{w}: lib2 spread, % of its median"] = round(b["spread_ms"] / b["median_ms"] * 100, 3)
+        engs["lib2"].close()
+    # (2) identity table against the shared cache, (3) the use cases
+    ident = [list(range(K))] * B
+    mixed = [[K * b + s for s in range(K)] for b in range(B)]                                   # frame b on source set b
+    runs = {n: [] for n in ("shared forward_target", "forward_bank identity", "set_sources shared (K images)", "bank_put one slot",
+                            "forward_bank B=4, 4 source sets", "4 x forward_bank B=1")}
+    same = True
+    for r in range(rounds + 1):
+        eng.set_sources(*sets[0], shared=True)
+        t = {"shared forward_target": ms(lambda: eng.forward_target(tl, tb))}
+        want = eng.forward_target(tl, tb)[0].clone()
+        t["set_sources shared (K images)"] = ms(lambda: eng.set_sources(*sets[0], shared=True))
+        for b in range(B):
+            eng.bank_put(K * b, *sets[b])
+        t["forward_bank identity"] = ms(lambda: eng.forward_bank(ident, tl, tb))
+        same = same and bool(torch.equal(eng.forward_bank(ident, tl, tb)[0], want))
+        t["bank_put one slot"] = ms(lambda: eng.bank_put(1, *[x[1:2] for x in sets[0]]))
+        t["forward_bank B=4, 4 source sets"] = ms(lambda: eng.forward_bank(mixed, tl, tb))
+        t["4 x forward_bank B=1"] = ms(lambda: [eng.forward_bank(mixed[b:b + 1], tl[b:b + 1], tb[b:b + 1]) for b in range(B)])
+        a = eng.forward_bank(mixed, tl, tb)[0]
+        same = same and all(bool(torch.equal(a[b:b + 1], eng.forward_bank(mixed[b:b + 1], tl[b:b + 1], tb[b:b + 1])[0])) for b in range(B))
+        if r:
+            for n, v in t.items(): runs[n].append(v)
+    out["bank"] = table(runs)
+    m = lambda n: out["bank"][n]["median_ms"]
+    out["bank"]["identity - shared, % of shared"] = round((m("forward_bank identity") - m("shared forward_target")) / m("shared forward_target") * 100, 3)
+    out["bank"]["shared spread, % of its median"] = round(out["bank"]["shared forward_target"]["spread_ms"] / m("shared forward_target") * 100, 3)
+    out["bank"]["set_sources / bank_put one slot"] = round(m("set_sources shared (K images)") / m("bank_put one slot"), 3)
+    out["bank"]["4 x B=1 / one B=4"] = round(m("4 x forward_bank B=1") / m("forward_bank B=4, 4 source sets"), 3)
+    out["bit_identical"] = same
+    print(json.dumps(out))
+
+
+if "--bank" in sys.argv:
+    bank_bench()
+    sys.exit(0)
 SHARED = "--shared" in sys.argv
 ROUNDS = int(sys.argv[sys.argv.index("--compare") + 1]) if "--compare" in sys.argv else 0
 eng = TSNetEngine(label_nc=2, n_blocks=NB, n_downsampling=3, n_source=3, height=H, width=W, max_batch=B)

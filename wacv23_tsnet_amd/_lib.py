@@ -31,6 +31,8 @@ ABI_SYMBOLS = (
     "tsnet_op_flow", "tsnet_op_flow_k", "tsnet_flow_plan", "tsnet_op_warp", "tsnet_op_warp_k", "tsnet_op_warp_k_shared", "tsnet_op_add_stats", "tsnet_op_finalize_stats", "tsnet_op_fuse_tail", "tsnet_op_pack_input", "tsnet_op_upsample2x_st", "tsnet_op_last_error", "tsnet_frame_stats", "tsnet_demo_postprocess", "tsnet_fit_face_curves", "tsnet_raster_face", "tsnet_vl2ch", "tsnet_fit_pose_curves", "tsnet_raster_pose", "tsnet_label_bbox", "tsnet_resize_pad", "tsnet_resize_label", "tsnet_bench_conv", "tsnet_debug_counters", "tsnet_linspace", "tsnet_coord_table",
     "tsnet_bicubic_taps", "tsnet_bicubic_table", "tsnet_prepare_frames",
     "tsnet_face_adapt_stats", "tsnet_face_adapt_apply", "tsnet_smooth_keypoints",
+    "tsnet_bank_capacity", "tsnet_bank_put", "tsnet_forward_bank",
+    "tsnet_op_flow_k_slots", "tsnet_op_warp_k_slots", "tsnet_op_add_stats_slots", "tsnet_op_fuse_tail_slots",
 )
 
 
@@ -119,6 +121,15 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.tsnet_face_adapt_stats.argtypes = [_vp, C.c_int, _vp]
         lib.tsnet_face_adapt_apply.argtypes = [_vp, _vp, C.c_int]
         lib.tsnet_smooth_keypoints.argtypes = [_vp, C.c_int, C.c_int, _vp]
+    if hasattr(lib, "tsnet_forward_bank"):       # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        _ip = C.POINTER(C.c_int)
+        lib.tsnet_bank_capacity.argtypes = [_vp]
+        lib.tsnet_bank_put.argtypes = [_vp, C.c_int, C.c_int, pp, pp, pp, _fp, _vp]
+        lib.tsnet_forward_bank.argtypes = [_vp, _ip, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]
+        lib.tsnet_op_flow_k_slots.argtypes = [_vp, _vp, _vp, _vp] + [C.c_int] * 7 + [_vp, C.c_int, C.c_int, _fp, _ip, C.c_int, _vp]
+        lib.tsnet_op_warp_k_slots.argtypes = [_vp, _vp] + [C.c_int] * 5 + [_vp, _ip, C.c_int, _vp]
+        lib.tsnet_op_add_stats_slots.argtypes = [_vp, _vp] + [C.c_int] * 4 + [_vp, _vp, _vp, _ip, C.c_int, _vp]
+        lib.tsnet_op_fuse_tail_slots.argtypes = [_vp] * 5 + [C.c_int] * 4 + [_vp, _ip, C.c_int, _vp]
     return lib
 
 

@@ -327,7 +327,9 @@ void launch_finalize_impl(const double* part, float* alpha, float* beta, int N, 
 
 // y = x + add[n % add_nmod] with the InstanceNorm statistics of y -> (alpha, beta); `part` must hold N*64*C*2 doubles.  x_sb: source-batch
 // extent of x (AddStatsArgs; 0 = add_nmod: x holds N images)
-void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, float* y, int N, int HW, int C, double* part, float* alpha, float* beta, int x_sb = 0) {
+// slot (device, N ints; source bank): image n reads x[slot[n]] instead
+void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, float* y, int N, int HW, int C, double* part, float* alpha, float* beta, int x_sb = 0,
+                   const int* slot = nullptr) {
     if (C & 3) throw ArgError("add_stats: C must be a multiple of 4");
     TimeScope ts(ctx, TSNET_T_STATS);
     const int cq = C / 4, cols = cq < 256 ? cq : 256, R = 256 / cols;
@@ -339,7 +341,8 @@ void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, flo
     const int nmod = add_nmod > 0 ? add_nmod : 1;
     if (x_sb < 0 || x_sb > nmod || (x_sb && nmod % x_sb)) throw ArgError("add_stats: the source-batch extent must divide add_nmod");
     AddStatsArgs sa{x, add, y, part, HW, C, S, rps, nmod, x_sb ? x_sb : nmod};
-    hipLaunchKernelGGL(add_stats_partial_kernel, dim3(S, N, (cq + 255) / 256), dim3(256), 0, ctx.stream, sa);
+    if (slot) hipLaunchKernelGGL(add_stats_slots_kernel, dim3(S, N, (cq + 255) / 256), dim3(256), 0, ctx.stream, AddStatsSlotArgs{sa, slot});
+    else hipLaunchKernelGGL(add_stats_partial_kernel, dim3(S, N, (cq + 255) / 256), dim3(256), 0, ctx.stream, sa);
     check_launch("add_stats_partial");
     // (its finalize stays a launch: 64 splits x 1024 channels per image are a megabyte of partials -- one last-arriving workgroup per image
     // would read them at a single block's rate, in_finalize2 spreads them over 64 x N)
@@ -403,7 +406,8 @@ void run_l2norm_split(Ctx& ctx, const float* x, unsigned short* q, int N, int P,
 }
 
 // variant (tsnet_op_flow_k; the forward passes 0): 1 = flow_kernel whatever the plan says; 2 = flow_kernel_p without the exp pass (tools build)
-void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0) {
+// slot (device, NB ints; source bank): the kernels' slot forms
+void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0, const int* slot = nullptr) {
     if (a.C & 7) throw ArgError("flow: C must be a multiple of 8");
     if (a.SB == 0) a.SB = a.B;
     if (a.SB < 1 || a.B % a.SB) throw ArgError("flow: the source-batch extent must divide the batch");
@@ -415,7 +419,7 @@ void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0) {
     if (G) {
         a.K = NB / a.B; a.G = G; a.S = flowp_slices(a.h, a.w);
         try {
-            launch_flow_p(a, variant, ctx.stream);
+            launch_flow_p(a, variant, ctx.stream, slot);
         } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
         check_launch("flow_p");
         return;
@@ -425,15 +429,16 @@ void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0) {
     const size_t lds = flow_lds_bytes(NT, a.h, a.w, a.C);
     if (lds > budget) throw ArgError("flow: feature width / position count exceed the LDS budget");
     try {
-        launch_flow(a, NT, lds, (unsigned)(flow_ppad(a.P) / (32 * NT) * NB), ctx.stream);
+        launch_flow(a, NT, lds, (unsigned)(flow_ppad(a.P) / (32 * NT) * NB), ctx.stream, slot);
     } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     check_launch("flow");
 }
 
-void run_warp(Ctx& ctx, const float* src, const float* flow, float* out, int B, int K, int h, int w, int C, int SB = 0) {
+void run_warp(Ctx& ctx, const float* src, const float* flow, float* out, int B, int K, int h, int w, int C, int SB = 0, const int* slot = nullptr) {
     TimeScope ts(ctx, TSNET_T_WARP);
     WarpArgs a{src, flow, out, B, K, h, w, C, SB > 0 ? SB : B};
-    hipLaunchKernelGGL(warp_mean_kernel, dim3(ew_grid((size_t)B * h * w * C / 4)), dim3(256), 0, ctx.stream, a);
+    if (slot) hipLaunchKernelGGL(warp_mean_slots_kernel, dim3(ew_grid((size_t)B * h * w * C / 4)), dim3(256), 0, ctx.stream, WarpSlotArgs{a, slot});
+    else hipLaunchKernelGGL(warp_mean_kernel, dim3(ew_grid((size_t)B * h * w * C / 4)), dim3(256), 0, ctx.stream, a);
     check_launch("warp_mean");
 }
 
@@ -446,10 +451,23 @@ void run_pack_input(Ctx& ctx, const PackArgs& p, size_t amax_clear) {
 }
 
 // FuseNet tail: zbar = mean over sources of cat(src_fea, tar_fea) + (y2 * alpha + beta)   (FuseTailArgs)
-void run_fuse_tail(Ctx& ctx, const FuseTailArgs& t) {
+void run_fuse_tail(Ctx& ctx, const FuseTailArgs& t, const int* slot = nullptr) {
     TimeScope ts(ctx, TSNET_T_ELEMWISE);
-    hipLaunchKernelGGL(fuse_resid_mean_kernel, dim3(ew_grid((size_t)t.B * t.P * 2 * t.C1 / 4)), dim3(256), 0, ctx.stream, t);
+    if (slot) hipLaunchKernelGGL(fuse_resid_mean_slots_kernel, dim3(ew_grid((size_t)t.B * t.P * 2 * t.C1 / 4)), dim3(256), 0, ctx.stream, FuseTailSlotArgs{t, slot});
+    else hipLaunchKernelGGL(fuse_resid_mean_kernel, dim3(ew_grid((size_t)t.B * t.P * 2 * t.C1 / 4)), dim3(256), 0, ctx.stream, t);
     check_launch("fuse_resid_mean");
+}
+
+// n slot-table entries, host -> device on the stream: by value in the kernel arguments (slot_fill_kernel), so that nothing of the caller's
+// is read after this returns and two tables enqueued back to back cannot meet
+void run_slot_fill(hipStream_t s, int* dst, const int* host, int n) {
+    for (int i0 = 0; i0 < n; i0 += kSlotFill) {
+        SlotFillArgs a{};
+        a.dst = dst + i0; a.n = std::min(kSlotFill, n - i0);
+        for (int i = 0; i < a.n; ++i) a.v[i] = host[i0 + i];
+        hipLaunchKernelGGL(slot_fill_kernel, dim3(1), dim3(kSlotFill), 0, s, a);
+        check_launch("slot_fill");
+    }
 }
 
 // weights of one layer -> operand planes + the un-scale factor; `stage` holds the OIHW parameter on the device (form 1: its transform,
@@ -576,6 +594,14 @@ struct tsnet_engine {
     int last_B = 0;
     int last_SB = 0;                // source-batch extent of the last forward (what "src_fea" holds per source)
     bool last_shared = false;       // ... and whether it ran on a shared source set (tsnet_train_extras refuses: its src_img is per batch element)
+    // source bank (tsnet_bank_put / tsnet_forward_bank): the same five buffers seen as K * Bmax SLOTS of one image each -- slot j is image j of
+    // x_img / X / shat / F1s and mask j of bbox_copy, read densely ((K*Bmax, H, W); the two caches above keep their (K, Bmax, H, W) stride).  A
+    // forward names the slot of every (source, driving frame) pair in a table, entry s*B + b; both caches above are the tables s*SB + b % SB.
+    // The bank and the caches overwrite each other: whichever was written last is the one that can be read.
+    bool bank = false;              // the source-side buffers hold a bank (cached_B = 0 then)
+    std::vector<char> bank_filled;  // per slot: put since the bank was started
+    int* slot_tab = nullptr;        // device (arena): K * Bmax ints, the table of the bank forward being enqueued (written by slot_fill_kernel)
+    bool last_bank = false;         // the last forward ran on the bank ("src_fea" holds K * Bmax images; tsnet_train_extras refuses)
     int cur_B = 0;                        // batch of the forward being enqueued
     float src_div[TSNET_MAX_SOURCES];  // per-source image divisor (255; 1 for use_prev sources), tsnet_set_source_divisors
 
@@ -622,7 +648,8 @@ struct tsnet_engine {
                   float* y1, float* y2, int N, int hh, int ww);
     void set_sources(Ctx& ctx, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, int B, hipStream_t bbox_stream = nullptr);
     void target_chain(Ctx& ctx, const float* tar_lbl, int B);
-    void forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB);
+    void bank_put(Ctx& ctx, int first, int count, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, const float* div);
+    void forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB, int Kc = 0, const int* slot = nullptr);
     void forward_target(Ctx& ctx, const float* tar_lbl, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB) {
         target_chain(ctx, tar_lbl, B);
         forward_rest(ctx, tar_bbox, out_rgb, out_flow, B, SB);
@@ -803,6 +830,8 @@ void tsnet_engine::alloc_all(hipStream_t s) {
     for (int i = 0; i < 4; ++i) { want(&ab[i][0], NB * 2 * C); want(&ab[i][1], NB * 2 * C); }
     for (int i = 0; i < 2; ++i) { want(&ab_side[i][0], NB * 2 * C); want(&ab_side[i][1], NB * 2 * C); }
     want(&bbox_copy, NB * H * W);
+    float* slot_f = nullptr;
+    want(&slot_f, NB);                                                       // the source bank's slot table (ints)
     if (P >= 2048 && P % 64 == 0) want(&flow_part, 2 * flowp_part_words((int)NB, P, flowp_slices(h, w)));   // flow_kernel_p: one softmax state per (image, target tile, slice, column), 8-byte words
     // InstanceNorm partials (doubles = 2 floats each): the stand-alone pass N*64*C*2, a conv epilogue N * tiles-per-image * Cout * 2
     // with tiles of at least 64 positions (ceil for ragged images), per lane
@@ -821,6 +850,8 @@ void tsnet_engine::alloc_all(hipStream_t s) {
     for (auto& r : req) { *r.first = arena + o; o += r.second; }
     part = reinterpret_cast<double*>(part_f);
     part_side = reinterpret_cast<double*>(part_side_f);
+    slot_tab = reinterpret_cast<int*>(slot_f);
+    bank_filled.assign(NB, 0);
     HIP_TRY(hipMalloc((void**)&amax, (size_t)(K + 3) * Bmax * sizeof(unsigned)));
     HIP_TRY(hipMemsetAsync(amax, 0, (size_t)(K + 3) * Bmax * sizeof(unsigned), s));
     // arrival counters: one per (image, 32-channel group) of a launch; launches with more (image, group) pairs than kFinCounterInts
@@ -903,7 +934,36 @@ void tsnet_engine::set_sources(Ctx& ctx, const float* const* src_img, const floa
     // depends on the sources only: computed here, so a driving frame of a clip does not pay for it
     ConvCall a; a.x = X; a.bound = enc_bound(); a.N = K * B; a.H = h; a.W = w; a.y = F1s;
     conv(ctx, fuse_c1_src, a);
-    cached_B = B; cached_shared = false;
+    cached_B = B; cached_shared = false; bank = false;
+}
+
+// `count` sources of batch 1 -> slots first .. first + count - 1 of the bank: set_sources' chain on count images, its outputs at the slot
+// offset.  x_img, raw_img, the ResnetBlock scratch and the first `count` source maxima are staging; the other slots are not touched.
+void tsnet_engine::bank_put(Ctx& ctx, int first, int count, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, const float* div) {
+    cur_B = 1;
+    const int H = cfg.height, W = cfg.width;
+    if (!bank) { std::fill(bank_filled.begin(), bank_filled.end(), 0); bank = true; cached_B = 0; cached_shared = false; }
+    for (int i = 0; i < count; ++i) bank_filled[first + i] = 0;     // until everything below is enqueued
+    {
+        TimeScope ts(ctx, TSNET_T_PACK);
+        for (int i0 = 0; i0 < count; i0 += TSNET_MAX_SOURCES) {     // the packing kernel takes up to eight plane pointers by value
+            const int n = std::min(TSNET_MAX_SOURCES, count - i0);
+            PackArgs p{};
+            for (int s = 0; s < n; ++s) { p.img[s] = src_img[i0 + s]; p.lbl[s] = src_lbl[i0 + s]; p.img_div[s] = div ? div[i0 + s] : 255.0f; }
+            p.coords = cfg.addcoords ? d_coords : nullptr;
+            p.out = x_img + (size_t)i0 * H * W * cp_img; p.S = n; p.B = 1; p.H = H; p.W = W; p.L = cfg.label_nc; p.nimg = 3; p.Cp = cp_img;
+            p.amax_out = amax_src() + i0;
+            run_pack_input(ctx, p, (size_t)n);
+        }
+        for (int i = 0; i < count; ++i)
+            HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)(first + i) * H * W, src_bbox[i], (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx.stream));
+    }
+    float* fea = X + (size_t)first * P * C;
+    encode(ctx, img_enc, x_img, amax_src(), count, raw_img, fea, cfg.enc_blocks);
+    run_l2norm_split(ctx, fea, reinterpret_cast<unsigned short*>(shat) + (size_t)first * flow_plane_halves(1, P, C), count, P, C);
+    ConvCall a; a.x = fea; a.bound = enc_bound(); a.N = count; a.H = h; a.W = w; a.y = F1s + (size_t)first * P * C * 2;
+    conv(ctx, fuse_c1_src, a);
+    for (int i = 0; i < count; ++i) bank_filled[first + i] = 1;
 }
 
 // Everything that depends on the driving frame only: label encoder, its L2-normalised features and the target half of
@@ -928,8 +988,10 @@ void tsnet_engine::target_chain(Ctx& ctx, const float* tar_lbl, int B) {
 }
 
 // SB: source-batch extent of what set_sources left behind (B, or 1 for the shared cache)
-void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB) {
+// slot (device table, entry s*B + b) and Kc sources per frame: a forward on the source bank
+void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB, int Kc, const int* slot) {
     cur_B = B;
+    const int K = Kc > 0 ? Kc : this->K;                   // sources per driving frame of THIS forward
     const int H = cfg.height, W = cfg.width, NB = K * B;
     // ---- transformation branch.  Its result (pg) is first needed by the decoder, and its kernels are latency-bound (384 workgroups):
     // with the side stream available it runs there, concurrently with the MFMA-bound synthesis branch below, and joins before dec_map.
@@ -947,10 +1009,10 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
     fa.gx = d_gx; fa.gy = d_gy; fa.flow = flow;
     fa.part = reinterpret_cast<unsigned long long*>(flow_part); fa.cnt = flow_cnt;
     fa.B = B; fa.SB = SB; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
-    run_flow(cx, fa, NB);
+    run_flow(cx, fa, NB, 0, slot);                          // (with a table the kernels read the masks densely from src_bbox[0] = bbox_copy)
     if (out_flow)
         HIP_TRY(hipMemcpyAsync(out_flow, flow, (size_t)NB * P * 2 * sizeof(float), hipMemcpyDeviceToDevice, cx.stream));
-    run_warp(cx, X, flow, pg, B, K, h, w, C, SB);
+    run_warp(cx, X, flow, pg, B, K, h, w, C, SB, slot);
     if (fork) HIP_TRY(hipEventRecord(ev_join2, side_stream));
 
     // ---- synthesis branch
@@ -959,11 +1021,11 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
         auto s1 = next_ab(ctx);
         auto s2 = next_ab(ctx);
         // F1 = conv_src(src) [from set_sources] + conv_tar(tar) [target chain], and its InstanceNorm statistics
-        run_add_stats(ctx, F1s, FT, B, F1, NB, P, 2 * C, part, s1.first, s1.second, SB);
+        run_add_stats(ctx, F1s, FT, B, F1, NB, P, 2 * C, part, s1.first, s1.second, SB, slot);
         ConvCall b; b.x = F1; b.alpha = s1.first; b.beta = s1.second; b.relu = 1; b.bound = sqP;
         b.N = NB; b.H = h; b.W = w; b.y = F2;
         conv_stats(ctx, fuse_c2, b, NB, P, s2.first, s2.second);
-        run_fuse_tail(ctx, FuseTailArgs{X, tar_fea, F2, s2.first, s2.second, zbar, B, K, P, C, SB});
+        run_fuse_tail(ctx, FuseTailArgs{X, tar_fea, F2, s2.first, s2.second, zbar, B, K, P, C, SB}, slot);
         // zbar = mean over sources of cat(src_fea, tar_fea) + IN(.): bounded by enc_bound + sqrt(P).  fuse_net.conv has no norm behind it:
         // it publishes max |sg| per image for dec.map_conv's operand scale
         ConvCall c; c.x = zbar; c.bound = enc_bound() + sqP; c.N = B; c.H = h; c.W = w; c.y = sg;
@@ -1011,7 +1073,7 @@ void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb,
         for (int c = 0; c < 3; ++c) ha.bg[c] = (-cfg.pose_mean[c]) / 255.0f;             // TSNet_pose.py:276
         launch_head(ha, hh, ww, B, ctx.stream, ctx.cus);
     }
-    last_B = B; last_SB = SB; last_shared = cached_shared;
+    last_B = B; last_SB = SB; last_shared = cached_shared; last_bank = slot != nullptr;
     HIP_TRY(hipEventRecord(ev_done, ctx.stream));       // what tsnet_stage_ptr orders its widening pass behind
 }
 
@@ -1146,7 +1208,7 @@ int tsnet_set_source_divisors(tsnet_handle h, const float* div, int n) {
         if (!(d > 0.f) || !std::isfinite(d)) throw ArgError("set_source_divisors: divisors must be positive and finite");
         h->src_div[s] = d;
     }
-    h->cached_B = 0; h->cached_shared = false;      // cached source features were encoded with the previous divisors
+    h->cached_B = 0; h->cached_shared = false; h->bank = false;     // cached source features were encoded with the previous divisors
     API_END(h)
 }
 
@@ -1183,6 +1245,44 @@ int tsnet_forward_target(tsnet_handle h, const float* tar_lbl, const float* tar_
     if (!h->cached_shared && h->cached_B != B) throw ArgError("forward_target: batch differs from the cached sources (call tsnet_set_sources first)");
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
     h->forward_target(ctx, tar_lbl, tar_bbox, out_rgb, out_flow, B, h->cached_B);
+    API_END(h)
+}
+
+int tsnet_bank_capacity(tsnet_handle h) { return h ? h->K * h->Bmax : TSNET_ERR_ARG; }
+
+int tsnet_bank_put(tsnet_handle h, int first_slot, int count, const float* const* src_img, const float* const* src_lbl,
+                   const float* const* src_bbox, const float* div, void* stream) {
+    API_BEGIN(h)
+    if (!h->finalized) throw ArgError("bank_put before finalize");
+    const int cap = h->K * h->Bmax;
+    if (count < 1 || first_slot < 0 || first_slot > cap - count)
+        throw ArgError("bank_put: slots " + std::to_string(first_slot) + " .. " + std::to_string((long long)first_slot + count - 1) + " are outside the bank (capacity " + std::to_string(cap) + ")");
+    if (!src_img || !src_lbl || !src_bbox) throw ArgError("bank_put: null source list");
+    for (int i = 0; i < count; ++i) {
+        if (!src_img[i] || !src_lbl[i] || !src_bbox[i]) throw ArgError("bank_put: null source tensor (need `count` entries)");
+        if (div && (!(div[i] > 0.f) || !std::isfinite(div[i]))) throw ArgError("bank_put: divisors must be positive and finite");
+    }
+    Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
+    h->bank_put(ctx, first_slot, count, src_img, src_lbl, src_bbox, div);
+    API_END(h)
+}
+
+int tsnet_forward_bank(tsnet_handle h, const int* slots, int Kc, const float* tar_lbl, const float* tar_bbox,
+                       float* out_rgb, float* out_flow, int B, void* stream) {
+    API_BEGIN(h)
+    check_forward_args(h, B);
+    if (Kc < 1 || Kc > h->K) throw ArgError("forward_bank: sources per frame outside 1..n_source");
+    if (!h->bank) throw ArgError("forward_bank: no source bank (call tsnet_bank_put first)");
+    if (!slots || !tar_lbl || !tar_bbox || !out_rgb) throw ArgError("forward_bank: null slot table / target / output tensor");
+    const int cap = h->K * h->Bmax;
+    for (int i = 0; i < Kc * B; ++i) {
+        if (slots[i] < 0 || slots[i] >= cap) throw ArgError("forward_bank: slot " + std::to_string(slots[i]) + " is outside the bank (capacity " + std::to_string(cap) + ")");
+        if (!h->bank_filled[slots[i]]) throw ArgError("forward_bank: slot " + std::to_string(slots[i]) + " is not filled");
+    }
+    Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
+    run_slot_fill(ctx.stream, h->slot_tab, slots, Kc * B);
+    h->target_chain(ctx, tar_lbl, B);
+    h->forward_rest(ctx, tar_bbox, out_rgb, out_flow, B, 1, Kc, h->slot_tab);
     API_END(h)
 }
 
@@ -1226,6 +1326,7 @@ int tsnet_train_extras(tsnet_handle h, const float* const* src_img, const float*
     check_forward_args(h, B);
     if (h->last_B != B) throw ArgError("train_extras: call tsnet_forward with the same batch first (uses its flows and features)");
     if (h->last_shared) throw ArgError("train_extras: the last forward ran on a shared source set (tsnet_set_sources_shared); src_img is per batch element here");
+    if (h->last_bank) throw ArgError("train_extras: the last forward ran on a source bank (tsnet_forward_bank); src_img is per batch element here");
     if (!src_img || !tar_img || !warp_src_img || !losses) throw ArgError("train_extras: null tensor");
     const int K = h->K, H = h->cfg.height, W = h->cfg.width, hh = h->h, ww = h->w, P = h->P, C = h->C;
     for (int s = 0; s < K; ++s) if (!src_img[s]) throw ArgError("train_extras: null source image (need n_source entries)");
@@ -1270,7 +1371,7 @@ int tsnet_stage_ptr(tsnet_handle h, const char* name, const float** dev_ptr, siz
     const size_t fe = (size_t)h->P * h->C, B = h->last_B;
     std::string n = name ? name : "";
     const float* p = nullptr; size_t c = 0;
-    if (n == "src_fea") { p = h->X; c = (size_t)h->K * h->last_SB * fe; }       // K * SB images (K after a forward on a shared source set)
+    if (n == "src_fea") { p = h->X; c = (size_t)h->K * (h->last_bank ? h->Bmax : h->last_SB) * fe; }   // K * SB images (K after a forward on a shared source set; every slot after one on a bank)
     else if (n == "tar_fea") { p = h->tar_fea; c = B * fe; }
     else if (n == "pg") { p = h->pg; c = B * fe; }
     else if (n == "sg") { p = h->sg; c = B * fe; }
@@ -1474,16 +1575,31 @@ int tsnet_op_upsample2x(const float* x, const float* alpha, const float* beta, i
 }
 
 // tar_fea (B), src_fea / src_bbox / flow (K*B, image k*B + b).  repeat > 1 re-launches the flow kernel (identical results) for timing.
+// a host slot table of n entries in 0 .. n_src - 1 -> a device copy (operator entry points: they return after the stream has drained)
+static int* op_slot_table(DevBufs& bufs, const char* op, const int* slots, int n, int n_src) {
+    if (!slots) throw ArgError(std::string(op) + ": null slot table");
+    if (n_src < 1) throw ArgError(std::string(op) + ": the number of source images must be >= 1");
+    for (int i = 0; i < n; ++i)
+        if (slots[i] < 0 || slots[i] >= n_src) throw ArgError(std::string(op) + ": slot " + std::to_string(slots[i]) + " is outside the " + std::to_string(n_src) + " source images");
+    int* d = bufs.alloc<int>((size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpy(d, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    return d;
+}
+
+// slots (host, K*B entries, or null) + n_src: src_fea / src_bbox hold n_src images and (source k, frame b) reads image slots[k*B + b]
 static void op_flow_impl(const float* tar_fea, const float* src_fea, const float* tar_bbox, const float* src_bbox,
-                         int B, int K, int h, int w, int C, int H, int W, float* flow, int variant, int repeat, float* ms_out, hipStream_t stream) {
+                         int B, int K, int h, int w, int C, int H, int W, float* flow, int variant, int repeat, float* ms_out, hipStream_t stream,
+                         const int* slots = nullptr, int n_src = 0) {
     if (!tar_fea || !src_fea || !tar_bbox || !src_bbox || !flow) throw ArgError("null tensor");
     if (B < 1 || K < 1 || K > 8) throw ArgError("flow op: 1 <= K <= 8 sources, B >= 1");
     if (H % h || W % w) throw ArgError("flow op: bbox size must be a multiple of the feature size");
     Ctx ctx(stream, current_device_cus());
     const int P = h * w, NB = K * B;
     DevBufs bufs;
+    const int* dslot = slots ? op_slot_table(bufs, "flow op", slots, NB, n_src) : nullptr;
+    const int NS = slots ? n_src : NB;                      // source images
     auto* that = bufs.alloc<unsigned short>(flow_plane_halves(B, P, C) * 2);
-    auto* shat = bufs.alloc<unsigned short>(flow_plane_halves(NB, P, C) * 2);
+    auto* shat = bufs.alloc<unsigned short>(flow_plane_halves(NS, P, C) * 2);
     auto* gx = bufs.alloc<float>(w * sizeof(float));
     auto* gy = bufs.alloc<float>(h * sizeof(float));
     std::vector<float> hx(w), hy(h);
@@ -1498,14 +1614,14 @@ static void op_flow_impl(const float* tar_fea, const float* src_fea, const float
         HIP_TRY(hipMemsetAsync(fa.cnt, 0, (size_t)B * (P / 64) * sizeof(int), ctx.stream));
     }
     run_l2norm_split(ctx, tar_fea, that, B, P, C);
-    run_l2norm_split(ctx, src_fea, shat, NB, P, C);
+    run_l2norm_split(ctx, src_fea, shat, NS, P, C);
     fa.tq = that; fa.sq = shat; fa.tar_bbox = tar_bbox; fa.gx = gx; fa.gy = gy; fa.flow = flow;
     for (int k = 0; k < K; ++k) fa.src_bbox[k] = src_bbox + (size_t)k * B * H * W;
     fa.B = B; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
     std::unique_ptr<EventPair> ev(ms_out ? new EventPair : nullptr);
-    run_flow(ctx, fa, NB, variant);
+    run_flow(ctx, fa, NB, variant, dslot);
     if (ev) HIP_TRY(hipEventRecord(ev->a, ctx.stream));
-    for (int r = 1; r < repeat; ++r) run_flow(ctx, fa, NB, variant);
+    for (int r = 1; r < repeat; ++r) run_flow(ctx, fa, NB, variant, dslot);
     if (ev) HIP_TRY(hipEventRecord(ev->b, ctx.stream));
     HIP_TRY(hipStreamSynchronize(ctx.stream));
     if (ms_out) *ms_out = repeat > 1 ? ev->ms() / (float)(repeat - 1) : 0.f;
@@ -1522,6 +1638,15 @@ int tsnet_op_flow_k(const float* tar_fea, const float* src_fea, const float* tar
                     int B, int K, int h, int w, int C, int H, int W, float* flow, int variant, int repeat, float* ms_out, void* stream) {
     OP_BEGIN
     op_flow_impl(tar_fea, src_fea, tar_bbox, src_bbox, B, K, h, w, C, H, W, flow, variant, repeat, ms_out, (hipStream_t)stream);
+    OP_END
+}
+
+int tsnet_op_flow_k_slots(const float* tar_fea, const float* src_fea, const float* tar_bbox, const float* src_bbox,
+                          int B, int K, int h, int w, int C, int H, int W, float* flow, int variant, int repeat, float* ms_out,
+                          const int* slots, int n_src, void* stream) {
+    OP_BEGIN
+    if (!slots) throw ArgError("flow op: null slot table");
+    op_flow_impl(tar_fea, src_fea, tar_bbox, src_bbox, B, K, h, w, C, H, W, flow, variant, repeat, ms_out, (hipStream_t)stream, slots, n_src);
     OP_END
 }
 
@@ -1563,6 +1688,49 @@ int tsnet_op_warp_k_shared(const float* src_fea, const float* flow, int B, int K
     if (SB < 1 || B % SB) throw ArgError("warp op: the source-batch extent must divide the batch");
     Ctx ctx((hipStream_t)stream, current_device_cus());
     run_warp(ctx, src_fea, flow, out, B, K, h, w, C, SB);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    OP_END
+}
+
+int tsnet_op_warp_k_slots(const float* src_fea, const float* flow, int B, int K, int h, int w, int C, float* out, const int* slots, int n_src, void* stream) {
+    OP_BEGIN
+    if (!src_fea || !flow || !out) throw ArgError("warp op: null tensor");
+    if (C < 4 || (C & 3)) throw ArgError("warp op: C must be a multiple of 4");
+    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape (1 <= K <= 8 sources, B, h, w >= 1)");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    DevBufs mem;
+    const int* d = op_slot_table(mem, "warp op", slots, K * B, n_src);
+    run_warp(ctx, src_fea, flow, out, B, K, h, w, C, 1, d);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    OP_END
+}
+
+int tsnet_op_add_stats_slots(const float* x, const float* add, int add_nmod, int N, int HW, int C, float* y, float* alpha, float* beta,
+                             const int* slots, int n_src, void* stream) {
+    OP_BEGIN
+    if (!x || !add || !y || !alpha || !beta) throw ArgError("add_stats op: null tensor");
+    if (C < 4 || (C & 3)) throw ArgError("add_stats op: C must be a multiple of 4");
+    if (N < 1 || N > 65535 || HW < 1) throw ArgError("add_stats op: bad shape (1 <= N <= 65535, HW >= 1)");
+    if (add_nmod < 1 || N % add_nmod) throw ArgError("add_stats op: add_nmod must divide N");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    DevBufs mem;
+    const int* d = op_slot_table(mem, "add_stats op", slots, N, n_src);
+    double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
+    run_add_stats(ctx, x, add, add_nmod, y, N, HW, C, part, alpha, beta, 0, d);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    OP_END
+}
+
+int tsnet_op_fuse_tail_slots(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
+                             int B, int K, int P, int C1, float* zbar, const int* slots, int n_src, void* stream) {
+    OP_BEGIN
+    if (!src_fea || !tar_fea || !y2 || !alpha || !beta || !zbar) throw ArgError("fuse_tail op: null tensor");
+    if (C1 < 4 || (C1 & 3)) throw ArgError("fuse_tail op: C1 must be a multiple of 4");
+    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || P < 1) throw ArgError("fuse_tail op: bad shape (1 <= K <= 8 sources, B, P >= 1)");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    DevBufs mem;
+    const int* d = op_slot_table(mem, "fuse_tail op", slots, K * B, n_src);
+    run_fuse_tail(ctx, FuseTailArgs{src_fea, tar_fea, y2, alpha, beta, zbar, B, K, P, C1, 1}, d);
     HIP_TRY(hipStreamSynchronize(ctx.stream));
     OP_END
 }

@@ -34,6 +34,12 @@ struct FlowArgs {
     int* cnt;                 // [B][tiles] arrival counters, zero between launches
     int K, G, S;              // sources per batch element; workgroups per target tile; slices per source image (flowp_slices: S % G == 0)
 };
+// source bank: the argument block of the kernels' slot forms (flow_slots_kernel, flow_kernel_p_slots).  Its own block, so that the kernels of
+// the two cache modes keep their argument layout -- and with it their ISA -- to the instruction.
+struct FlowSlotArgs {
+    FlowArgs a;               // a.SB is not read; a.src_bbox[0] alone: one (H, W) mask per source image
+    const int* slot;          // [NB] device: (source s, driving frame b) reads image slot[s*B + b] of a.sq and the mask a.src_bbox[0] + slot[s*B + b]*H*W
+};
 
 // LDS bytes of flow_kernel_p (64 targets per workgroup): target planes, two merge buffers [kFlowWaves][64][4] floats, a 64-float mask row
 // per wave, gx, gy

@@ -44,8 +44,9 @@ __device__ __forceinline__ void flow_unpack2(unsigned long long v, float& a, flo
 }
 
 // grid = B * (P / 64) * G (1-D), block = 512.  OPT (tools): bit 1 = skip the exp / accumulate pass (ablation: computes garbage).
-template <int OPT>
-__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
+// SL: the source image of a (source, frame) pair comes from the slot table (FlowSlotArgs: a source bank), one scalar load per source of the sweep.
+template <int OPT, bool SL>
+__device__ __forceinline__ void flow_persist_body(const FlowArgs& a, const int* slot) {
     constexpr int NT = 2, NTH = 64 * kFlowWaves;
     HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) unsigned char, smem_raw)
     const int KC = (a.C + 31) / 32 * 2;
@@ -100,11 +101,12 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
         const int n = s_idx * a.B + b;
         const int buf = it & 1;
         const int sp_base = slice * nps;
-        const float* sb = a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
+        const int img = SL ? slot[n] : s_idx * a.SB + bs;
+        const float* sb = SL ? a.src_bbox[0] + (size_t)img * a.H * a.W : a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
         float m_run[NT], l_run[NT], ax[NT], ay[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) { m_run[j] = -3.0e38f; l_run[j] = 0.f; ax[j] = 0.f; ay[j] = 0.f; }
-        const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)(s_idx * a.SB + bs) * (a.P >> 5) * KC) * 2048 + lane * 16;
+        const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)img * (a.P >> 5) * KC) * 2048 + lane * 16;
         for (int sp = sp_base + wave; sp < sp_base + nps; sp += kFlowWaves) {
             // this lane's share of the pair's source mask (F.interpolate(nearest)): source sp * 64 + lane; lands under the MFMA sweep
             float msl;
@@ -301,5 +303,9 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
         }
     }
 }
+
+template <int OPT>
+__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) { flow_persist_body<OPT, false>(a, nullptr); }
+__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p_slots(FlowSlotArgs s) { flow_persist_body<0, true>(s.a, s.slot); }
 
 }  // namespace tsnet

@@ -13,8 +13,9 @@ namespace tsnet {
 
 // grid = Ppad / (32 NT) * NB (1-D), block = 512.  dyn LDS: target planes NT * KC * 2 KiB, then ms[Ppad], gx[w], gy[h]; the merge buffer
 // [16][NT * 32][4] floats aliases the target planes after the sweep.
-template <int NT>
-__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
+// SL: the source image comes from the slot table (FlowSlotArgs) -- one scalar load per workgroup, (s, b) being fixed per workgroup.
+template <int NT, bool SL>
+__device__ __forceinline__ void flow_sweep_body(const FlowArgs& a, const int* slot) {
     constexpr int NTH = 64 * kFlowWaves;
     HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) unsigned char, smem_raw)
     const int Ppad = (a.P + 63) / 64 * 64, KC = (a.C + 31) / 32 * 2;
@@ -48,7 +49,8 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
             for (int u = 0; u < 8; ++u) { const int i = i0 + u * NTH + tid; if (i < cnt) d[i] = v[u]; }
         }
     }
-    const float* sb = a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
+    const int img = SL ? slot[n] : s_idx * a.SB + bs;                 // the (source, frame) pair's image of the source planes
+    const float* sb = SL ? a.src_bbox[0] + (size_t)img * a.H * a.W : a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
     for (int p = tid; p < Ppad; p += NTH) {
         float v = 0.f;
         if (p < a.P) {
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
     float m_run[NT], l_run[NT], ax[NT], ay[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) { m_run[j] = -3.0e38f; l_run[j] = 0.f; ax[j] = 0.f; ay[j] = 0.f; }
-    const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)(s_idx * a.SB + bs) * (Ppad >> 5) * KC) * 2048 + lane * 16;
+    const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)img * (Ppad >> 5) * KC) * 2048 + lane * 16;
     const unsigned char* tbase = smem_raw + lane * 16;
     const int npair = Ppad >> 6;
     for (int sp = wave; sp < npair; sp += kFlowWaves) {
@@ -203,5 +205,11 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
         f[1] = Y / L;
     }
 }
+
+template <int NT>
+__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) { flow_sweep_body<NT, false>(a, nullptr); }
+// the same sweep on a source bank (its own name: tests/test_isa.py counts the instantiations of flow_kernel)
+template <int NT>
+__global__ __launch_bounds__(64 * kFlowWaves) void flow_slots_kernel(FlowSlotArgs s) { flow_sweep_body<NT, true>(s.a, s.slot); }
 
 }  // namespace tsnet

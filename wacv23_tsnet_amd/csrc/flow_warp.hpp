@@ -79,12 +79,18 @@ struct WarpArgs {
     int B, K, h, w, C;
     int SB;              // source-batch extent: B, or 1 for one source set shared by the batch
 };
+// source bank (warp_mean_slots_kernel): (source s, driving frame b) reads image slot[s*B + b] of a.src; a.SB is not read.  Its own block:
+// warp_mean_kernel keeps its argument layout, and its ISA, to the instruction.
+struct WarpSlotArgs { WarpArgs a; const int* slot; };
 
-__global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
+// i0, stride: the thread's first element and the grid's stride, read from blockIdx / blockDim / gridDim by the KERNEL (where the compiler
+// knows the workgroup size is uniform: read here, warp_mean_kernel's prologue grows by the partial-workgroup case)
+template <bool SL>
+__device__ __forceinline__ void warp_mean_body(const WarpArgs& a, const int* slot, size_t i0, size_t stride) {
     const int P = a.h * a.w;
     const int c4n = a.C >> 2;
     const size_t total = (size_t)a.B * P * c4n;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    for (size_t i = i0; i < total; i += stride) {
         const int c = (int)(i % c4n) * 4;
         const size_t bp = i / c4n;
         const int b = (int)(bp / P), p = (int)(bp - (size_t)b * P);
@@ -100,7 +106,7 @@ __global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
             const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
             const float wnw = (x1 - ix) * (y1 - iy), wne = (ix - x0) * (y1 - iy);
             const float wsw = (x1 - ix) * (iy - y0), wse = (ix - x0) * (iy - y0);
-            const float* base = a.src + ((size_t)(s * a.SB + bs) * P) * a.C + c;
+            const float* base = a.src + ((size_t)(SL ? slot[n] : s * a.SB + bs) * P) * a.C + c;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             const bool xin0 = x0 >= 0 && x0 < a.w, xin1 = x1 >= 0 && x1 < a.w;
             const bool yin0 = y0 >= 0 && y0 < a.h, yin1 = y1 >= 0 && y1 < a.h;
@@ -118,6 +124,13 @@ __global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
         sum.x /= kf; sum.y /= kf; sum.z /= kf; sum.w /= kf;
         *reinterpret_cast<float4*>(a.out + ((size_t)b * P + p) * a.C + c) = sum;
     }
+}
+
+__global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
+    warp_mean_body<false>(a, nullptr, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+}
+__global__ __launch_bounds__(256) void warp_mean_slots_kernel(WarpSlotArgs s) {
+    warp_mean_body<true>(s.a, s.slot, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 }  // namespace tsnet

@@ -135,6 +135,8 @@ class ClipRunner:
         into RGB bytes on the device (`DemoPostprocessor`); only the bytes cross PCIe;
       * with batch > 1 the one source set is cached for the whole batch (`tsnet_set_sources_shared`: K encoded images, not K * batch) and
         `run()` walks the clip in groups of `batch` driving frames with a ragged last group -- the same bytes as batch 1, at the batch rate;
+      * `replace_source(i, ...)` swaps one source for another at 1 / K of the encoding work: from the first call on the runner keeps its sources
+        in slots 0 .. K-1 of the engine's source bank (`tsnet_bank_put`, `tsnet_forward_bank`) and re-encodes slot i alone;
       * the three-panel strips and the GIF are written with PIL.
     model: a wacv23_tsnet_amd.model.TSNet on the GPU.
 
@@ -154,8 +156,28 @@ class ClipRunner:
         dev = model._device()
         mv = lambda t: t.to(dev, dtype=torch.float32).contiguous()
         self.src_img = [mv(x) for x in src_img[:K]]
-        self.eng.set_sources(self.src_img, [mv(x) for x in src_lbl[:K]], [mv(x) for x in src_bbox[:K]], shared=batch > 1)
+        self.src_lbl, self.src_bbox = [mv(x) for x in src_lbl[:K]], [mv(x) for x in src_bbox[:K]]
+        self.eng.set_sources(self.src_img, self.src_lbl, self.src_bbox, shared=batch > 1)
+        self._bank = False                                          # replace_source moves the sources into the engine's source bank
         self.post = DemoPostprocessor(self.src_img[0])              # ref_img_list[0] (:180)
+
+    def replace_source(self, i: int, img: torch.Tensor, lbl: torch.Tensor, bbox: torch.Tensor):
+        """Source i <- (img (1,3,H,W), lbl (1,L,H,W), bbox (1,H,W)); the frames produced afterwards are those of a fresh runner built
+        with the new set.  Only source i is encoded -- except in the first call, which moves all K sources from the clip cache into
+        slots 0 .. K-1 of the source bank (the two lay the bounding boxes out differently)."""
+        K = len(self.src_img)
+        if not 0 <= i < K:
+            raise ValueError(f"source {i} of {K}")
+        dev = self.src_img[0].device
+        mv = lambda t: t.to(dev, dtype=torch.float32).contiguous()
+        self.src_img[i], self.src_lbl[i], self.src_bbox[i] = mv(img), mv(lbl), mv(bbox)
+        if self._bank:
+            self.eng.bank_put(i, self.src_img[i:i + 1], self.src_lbl[i:i + 1], self.src_bbox[i:i + 1])
+        else:
+            self.eng.bank_put(0, self.src_img, self.src_lbl, self.src_bbox)
+            self._bank = True
+        if i == 0:
+            self.post = DemoPostprocessor(self.src_img[0])
 
     def close(self):
         if self.eng is not None:
@@ -180,7 +202,11 @@ class ClipRunner:
         if tar_lbl.shape[0] > self.batch:
             raise ValueError(f"{tar_lbl.shape[0]} driving frames, runner built for batch {self.batch}")
         dev = self.src_img[0].device
-        rec, _ = self.eng.forward_target(tar_lbl.to(dev, dtype=torch.float32), tar_bbox.to(dev, dtype=torch.float32))
+        tl, tb = tar_lbl.to(dev, dtype=torch.float32), tar_bbox.to(dev, dtype=torch.float32)
+        if self._bank:
+            rec, _ = self.eng.forward_bank([list(range(len(self.src_img)))] * tl.shape[0], tl, tb)
+        else:
+            rec, _ = self.eng.forward_target(tl, tb)
         return self.post(rec)
 
     def frame(self, tar_lbl: torch.Tensor, tar_bbox: torch.Tensor) -> torch.Tensor:

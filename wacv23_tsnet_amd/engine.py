@@ -226,6 +226,76 @@ class TSNetEngine:
         self._keep = (tl, tb)
         return out, ([flow[i] for i in range(K)] if return_flow else None)
 
+    # ------------------------------------------------------------------ source bank
+    @property
+    def bank_capacity(self) -> int:
+        """tsnet_bank_capacity: slots of the source bank, n_source * max_batch."""
+        return int(self.lib.tsnet_bank_capacity(self._h))
+
+    def bank_put(self, slots, src_img, src_lbl, src_bbox, divisors: Optional[Sequence[float]] = None):
+        """tsnet_bank_put: encode sources of batch 1 into slots of the bank, one tsnet_set_sources' worth of work per n_source slots.
+        slots: an int (the first slot: source i goes to slot slots + i) or one slot per source, in any order; a list is split into
+        contiguous runs, one call each.  divisors: per source, 255 (default) or 1 for a frame already in [0,1]."""
+        n = len(src_img)
+        sl = list(range(slots, slots + n)) if isinstance(slots, int) else [int(x) for x in slots]
+        if n < 1 or len(sl) != n or len(src_lbl) != n or len(src_bbox) != n or (divisors is not None and len(divisors) != n):
+            raise ValueError(f"bank_put: {len(sl)} slots, {n} images, {len(src_lbl)} label maps, {len(src_bbox)} bboxes"
+                             + ("" if divisors is None else f", {len(divisors)} divisors") + ": need one of each per source")
+        if len(set(sl)) != n:
+            raise ValueError("bank_put: a slot is named twice")
+        H, W, L = self.cfg.height, self.cfg.width, self.cfg.label_nc
+        si = [self._prep(src_img[i], (1, 3, H, W), f"src_img[{i}]") for i in range(n)]
+        sb_ = [self._prep(src_bbox[i], (1, H, W), f"src_bbox[{i}]") for i in range(n)]
+        sl_ = [self._prep(src_lbl[i], (1, L, H, W), f"src_lbl[{i}]") for i in range(n)]
+        self._same_device(*si, *sl_, *sb_)
+        lo = 0
+        while lo < n:                                           # contiguous ascending runs
+            hi = lo + 1
+            while hi < n and sl[hi] == sl[hi - 1] + 1:
+                hi += 1
+            c = hi - lo
+            arr = lambda ts: (C.c_void_p * c)(*[t.data_ptr() for t in ts[lo:hi]])
+            div = None if divisors is None else (C.c_float * c)(*[float(x) for x in divisors[lo:hi]])
+            with self._on_device():
+                rc = self.lib.tsnet_bank_put(self._h, sl[lo], c, arr(si), arr(sl_), arr(sb_), div, _stream_of(si[0]))
+            self._check(rc, "tsnet_bank_put")
+            lo = hi
+        self._keep_bank = (si, sl_, sb_)
+
+    def forward_bank(self, index, tar_lbl, tar_bbox, return_flow: bool = False):
+        """tsnet_forward_bank.  index: (B, Kc) integers on the host (nested lists, numpy, a CPU tensor) -- row b lists the slots of
+        driving frame b's sources, in order.  Returns (rec (B,3,H,W), flows Kc x (B,h,w,2) | None); frame b has the bits of forward()
+        at B = 1 on (those sources, frame b)."""
+        if isinstance(index, torch.Tensor):
+            if index.is_cuda:
+                raise ValueError("forward_bank: index must be on the host")
+            if index.dtype.is_floating_point or index.dtype in (torch.bool, torch.complex64, torch.complex128):
+                raise ValueError(f"forward_bank: index must hold integers, got {index.dtype}")
+            rows = index.tolist()
+        else:
+            import numpy as np
+            a = np.asarray(index)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"forward_bank: index must hold integers, got dtype {a.dtype}")
+            rows = a.tolist()
+        B = tar_lbl.shape[0]
+        if not isinstance(rows, list) or len(rows) != B or not all(isinstance(r, list) and r and len(r) == len(rows[0])
+                                                                   and all(isinstance(v, int) for v in r) for r in rows):
+            raise ValueError(f"forward_bank: index must have shape (B, Kc) with B = {B} driving frames")
+        Kc = len(rows[0])
+        H, W, L = self.cfg.height, self.cfg.width, self.cfg.label_nc
+        tl = self._prep(tar_lbl, (B, L, H, W), "tar_lbl")
+        tb = self._prep(tar_bbox, (B, H, W), "tar_bbox")
+        table = (C.c_int * (Kc * B))(*[rows[b][s] for s in range(Kc) for b in range(B)])     # the ABI's layout: entry s*B + b
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=tl.device)
+        flow = torch.empty((Kc, B, self.h, self.w, 2), dtype=torch.float32, device=tl.device) if return_flow else None
+        self._same_device(tl, tb)
+        with self._on_device():
+            rc = self.lib.tsnet_forward_bank(self._h, table, Kc, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
+        self._check(rc, "tsnet_forward_bank")
+        self._keep = (tl, tb)
+        return out, ([flow[i] for i in range(Kc)] if return_flow else None)
+
     def train_extras(self, src_img: List[torch.Tensor], tar_img: torch.Tensor):
         """tsnet_train_extras: the is_train branches of the reference forward (TSNet.py:327-331, 372-390, 402-405) for the
         forward that was just run.  Returns (warp_src_img_list: K x (B,3,H,W), loss_warp, loss_align) -- the losses as 0-d

@@ -181,7 +181,10 @@ class TSNet(nn.Module):
         self._use_prev = None if use_prev is None else [bool(x) for x in use_prev]
 
     def set_source_num(self, n_source):
-        """TSNet.set_source_num (TSNet.py:296)."""
+        """TSNet.set_source_num (TSNet.py:296).  A number up to the one the engine was created for keeps the engine (no re-packing of the
+        weights): test-mode forward() then runs the first n_source sources through the engine's source bank (bank_put + forward_bank),
+        with the bits of a model built with that n_source.  A larger number, or a training-mode input (its extras are per batch
+        element, not per slot), builds a new engine at the next forward()."""
         self.n_source = n_source
 
     def forward(self):
@@ -191,6 +194,15 @@ class TSNet(nn.Module):
             raise RuntimeError("call set_test_input() before forward()")
         eng = self._get_engine(self.tar_lbl.shape[0])
         K = self.n_source
+        if K < eng.K:                          # fewer sources than the engine holds (set_source_num): slot s*B + b = source s of frame b
+            B = self.tar_lbl.shape[0]
+            part = lambda ts: [ts[s][b:b + 1] for s in range(K) for b in range(B)]
+            eng.bank_put(0, part(self.src_img_list), part(self.src_lbl_list), part(self.src_bbox_list))
+            rec, flows = eng.forward_bank([[s * B + b for s in range(K)] for b in range(B)], self.tar_lbl, self.tar_bbox, return_flow=self.return_flow)
+            self.rec_tar_img = rec
+            if self.return_flow:
+                self.warp_grid2d_list = flows
+            return
         use_prev = getattr(self, "_use_prev", None)
         if use_prev != getattr(eng, "_use_prev_applied", None):
             eng.set_source_divisors(None if use_prev is None else [1.0 if p else 255.0 for p in use_prev[:K]])
@@ -243,8 +255,10 @@ class TSNet(nn.Module):
         return eng
 
     def _get_engine(self, B: int) -> TSNetEngine:
-        key = (self.n_source, self._weights_version())
-        if self._engine is None or self._engine_key != key or B > self._engine.cfg.max_batch:
+        key = self._weights_version()
+        eng = self._engine
+        # fewer sources than the engine's run on its source bank (forward()); more, or fewer in training mode, need an engine of their own
+        if eng is None or self._engine_key != key or B > eng.cfg.max_batch or self.n_source > eng.K or (self.n_source < eng.K and self.tar_img is not None):
             if self._device().type != "cuda":
                 raise RuntimeError("TSNet.forward() runs on an MI355X only: move the model with .cuda() first "
                                    "(there is no CPU execution path)")
