@@ -16,7 +16,8 @@
  * Additions within TSNET_ABI_VERSION 5 (new entry points only; nothing that existed changed): tsnet_face_adapt_stats,
  * tsnet_face_adapt_apply, tsnet_smooth_keypoints -- the face loader's key-point preparation of a cross-identity pair; tsnet_bank_capacity,
  * tsnet_bank_put, tsnet_forward_bank -- the source bank; tsnet_op_flow_k_slots, tsnet_op_warp_k_slots, tsnet_op_add_stats_slots,
- * tsnet_op_fuse_tail_slots -- its kernels one at a time.
+ * tsnet_op_fuse_tail_slots -- its kernels one at a time; tsnet_forward_u8, tsnet_set_sources_u8, tsnet_forward_target_u8, tsnet_bank_put_u8,
+ * tsnet_forward_bank_u8, tsnet_op_pack_input_u8, tsnet_prepare_frames_u8 -- compact (byte) inputs.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -28,7 +29,7 @@
 extern "C" {
 #endif
 
-#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots); 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
+#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8); 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
 #define TSNET_MAX_SOURCES 8
 
 enum {
@@ -151,6 +152,29 @@ int tsnet_bank_put(tsnet_handle h, int first_slot, int count, const float* const
 int tsnet_forward_bank(tsnet_handle h, const int* slots, int Kc, const float* tar_lbl, const float* tar_bbox,
                        float* out_rgb, float* out_flow, int B, void* stream);
 
+/* Compact inputs: the same five calls on the BYTES the wide tensors are made from, one byte per value instead of four.
+ *   image  (B,3,H,W) bytes, planes B, G, R: the loader's resized frame BEFORE its `- IMG_MEAN` (tsnet_prepare_frames_u8 writes it);
+ *   label  (B,H,W)   bytes, class indices (what the rasterisers emit; an index >= label_nc gives an all-zero pixel, as vl2ch's comparison does);
+ *   bbox   (B,H,W)   bytes, widened as (float)byte: pass 0 / 1 for the masks the wide entries take.
+ * mean_bgr: 3 HOST floats, required wherever images are passed.  The stems' packing kernel widens on load with the operations the wide form went
+ * through -- (float)byte is exact, `- mean` and `/ div` are the loader's and the packing kernel's own two fp32 operations, one-hot is a comparison
+ * -- so every result has the BITS of the sibling call on the widened tensors.  Everything else is the sibling's: the source divisors (`div` of
+ * tsnet_bank_put_u8, tsnet_set_source_divisors for the others), the cache and bank state machine, stream ordering, error codes and messages
+ * (plus: null mean_bgr; label_nc > 255).  The two forms mix freely across calls: sources put as floats and driving frames as bytes share one
+ * cache, and vice versa.  tsnet_set_sources_u8: shared != 0 is tsnet_set_sources_shared (B must be 1).  The masks of compact driving frames are
+ * widened into an arena buffer of max_batch*H*W floats sized at tsnet_finalize: still no allocation after it.  tsnet_train_extras is unchanged. */
+int tsnet_forward_u8(tsnet_handle h, const uint8_t* const* src_img, const uint8_t* const* src_lbl, const uint8_t* const* src_bbox,
+                     const uint8_t* tar_lbl, const uint8_t* tar_bbox, const float* mean_bgr,
+                     float* out_rgb, float* out_flow, int B, void* stream);
+int tsnet_set_sources_u8(tsnet_handle h, const uint8_t* const* src_img, const uint8_t* const* src_lbl, const uint8_t* const* src_bbox,
+                         const float* mean_bgr, int B, int shared, void* stream);
+int tsnet_forward_target_u8(tsnet_handle h, const uint8_t* tar_lbl, const uint8_t* tar_bbox,
+                            float* out_rgb, float* out_flow, int B, void* stream);
+int tsnet_bank_put_u8(tsnet_handle h, int first_slot, int count, const uint8_t* const* src_img, const uint8_t* const* src_lbl,
+                      const uint8_t* const* src_bbox, const float* mean_bgr, const float* div, void* stream);
+int tsnet_forward_bank_u8(tsnet_handle h, const int* slots, int Kc, const uint8_t* tar_lbl, const uint8_t* tar_bbox,
+                          float* out_rgb, float* out_flow, int B, void* stream);
+
 /* Training-mode extras of the forward (model/TSNet.py:327-331, 372-390, 402-405), computed
  * from the flows and features the LAST tsnet_forward / tsnet_forward_target left in the engine -- call it right after that
  * forward, same B, same source images.  src_img: n_source x (B,3,H,W) raw (the /255 of set_train_input is applied inside);
@@ -243,6 +267,10 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  *   xx yy rr (coords != 0: tsnet_coord_table) | zeros], image s*B + b.  nimg = 3, or 0 for the label-only form (img, img_div not read);
  *   img_div: S HOST floats (255, or 1 for a frame already in [0,1]).  Cp = 8 or a multiple of 16, at least the real channel count.
  *   amax (S*B): zeroed, then max |out| per image as float bits -- what fixes the stem's operand scale.
+ * tsnet_op_pack_input_u8 <- the same assembly from compact inputs, as the tsnet_*_u8 forward entries run it: img[s] (B,3,H,W) bytes, lbl[s] (B,H,W)
+ *   class-index bytes, out[.., c] = (float(byte) - mean_bgr[c]) / img_div[s] for the image channels and byte == j ? 1 : 0 for label channel j;
+ *   mean_bgr: 3 HOST floats (nimg = 3).  bbox: NULL, or S device pointers to (B,H,W) mask bytes, widened to bbox_out (S*B,H,W) floats by the same
+ *   launch.  The checks of tsnet_op_pack_input, and L <= 255.  out and amax carry the bits tsnet_op_pack_input gives on the widened tensors.
  * tsnet_op_upsample2x_st <- tsnet_op_upsample2x in the bf16 storage mode (tsnet_cfg.operand_mode = 2): x_bf16 / y_bf16 != 0: x / y hold bf16
  *   (widened exactly on load; the fp32 result rounded to nearest even on store).
  * tsnet_op_flow_k_slots, tsnet_op_warp_k_slots, tsnet_op_add_stats_slots, tsnet_op_fuse_tail_slots <- tsnet_op_flow_k, tsnet_op_warp_k_shared,
@@ -295,6 +323,9 @@ int tsnet_op_fuse_tail_slots(const float* src_fea, const float* tar_fea, const f
                              int B, int K, int P, int C1, float* zbar, const int* slots, int n_src, void* stream);
 int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S, int B, int H, int W, int L, int nimg, int Cp, int coords,
                         const float* img_div, float* out, unsigned int* amax, void* stream);
+int tsnet_op_pack_input_u8(const uint8_t* const* img, const uint8_t* const* lbl, const uint8_t* const* bbox, int S, int B, int H, int W, int L,
+                           int nimg, int Cp, int coords, const float* img_div, const float* mean_bgr, float* out, float* bbox_out,
+                           unsigned int* amax, void* stream);
 int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta, int relu,
                            int N, int H, int W, int C, int x_bf16, int y_bf16, float* y, void* stream);
 const char* tsnet_op_last_error(void);
@@ -406,13 +437,19 @@ void tsnet_coord_table(int H, int W, float* out);
  *                          (Image.crop: those pixels read 0).  The x tables are those of (x1 - x0 -> ow), the y tables of (y1 - y0 -> oh): DEVICE
  *                          ints; an axis that keeps its size is skipped and its tables are not read (may be NULL).  mean_bgr: 3 HOST floats.
  *                          out: (F,3,OH,OW) device floats, planes B, G, R.  One kernel on `stream`: no allocation, no synchronisation.
- *                          TSNET_ERR_ARG (nothing written): empty box, taps that are not those of the size ratio, padding that does not fit. */
+ *                          TSNET_ERR_ARG (nothing written): empty box, taps that are not those of the size ratio, padding that does not fit.
+ * tsnet_prepare_frames_u8 <- the same kernel storing the resized BYTE: out (F,3,OH,OW) device bytes, no mean -- the compact image the tsnet_*_u8 entries
+ *                          take; (float)out - mean_bgr is tsnet_prepare_frames' output, bit for bit. */
 int tsnet_bicubic_taps(int n_in, int n_out);
 int tsnet_bicubic_table(int n_in, int n_out, int* first, int* count, int* coef);
 int tsnet_prepare_frames(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
                          const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
                          const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
                          int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream);
+int tsnet_prepare_frames_u8(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
+                            const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                            const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                            int oh, int ow, int pad_top, int pad_left, int OH, int OW, unsigned char* out, void* stream);
 
 #ifdef __cplusplus
 }

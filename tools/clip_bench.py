@@ -10,7 +10,12 @@
                             forward_target at B = 4 on both libraries, with each library's own spread over the rounds;
                         (2) forward_bank with the identity table against forward_target on the shared cache;
                         (3) bank_put of ONE slot against a full set_sources (K = 3 images), and four source sets x one driving frame as one
-                            forward_bank(B = 4) against four forward_bank(B = 1) calls"""
+                            forward_bank(B = 4) against four forward_bank(B = 1) calls
+    --compact [--rounds R]
+                        the input hand-off of a driving frame in both forms -- float32 (one-hot labels, float masks) and compact (class-map and mask
+                        bytes, tsnet_forward_target_u8) -- at the face shape (L = 2) and the pose shape (L = 25, composite), B = 1 and B = 4, one
+                        process, interleaved rounds, one JSON line: (a) the host -> device copy of the frames' inputs from pinned memory alone,
+                        (b) that copy + forward_target on the shared cache; per driving frame, median and spread (max - min) over the rounds"""
 import os, sys, time, json, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -104,8 +109,56 @@ def bank_bench():
     print(json.dumps(out))
 
 
+def compact_bench():
+    rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5
+    K, mean = 3, [101.84807705937696, 112.10832843463207, 111.65973036298041]
+    out = {"n_blocks": NB, "rounds": rounds, "unit": "us per driving frame", "shapes": {}}
+    g = torch.Generator().manual_seed(1)
+    for shape, L, pose in (("face", 2, False), ("pose", 25, True)):
+        eng = TSNetEngine(label_nc=L, n_blocks=NB, n_downsampling=3, n_source=K, height=H, width=W, max_batch=4, pose_composite=pose)
+        eng.load_state_dict(synth.state_dict(eng.param_shapes(), seed=0)); eng.finalize("cuda")
+        rnd8 = lambda shp, hi: torch.randint(0, hi, shp, generator=g, dtype=torch.uint8)
+        onehot = lambda c: torch.stack([(c == j) for j in range(L)], dim=1).float()
+        si, sl, sb = [rnd8((1, 3, H, W), 256) for _ in range(K)], [rnd8((1, H, W), L) for _ in range(K)], [rnd8((1, H, W), 2) for _ in range(K)]
+        eng.set_sources([t.cuda() for t in si], [t.cuda() for t in sl], [t.cuda() for t in sb], shared=True, mean=mean)
+        res = {}
+        for B in (1, 4):
+            tl8, tb8 = rnd8((B, H, W), L), rnd8((B, H, W), 2)
+            host = {"compact": (tl8.pin_memory(), tb8.pin_memory()), "float32": (onehot(tl8).pin_memory(), tb8.float().pin_memory())}
+            devt = {k: tuple(torch.empty(t.shape, dtype=t.dtype, device="cuda") for t in v) for k, v in host.items()}
+            nbytes = {k: sum(t.numel() * t.element_size() for t in v) // B for k, v in host.items()}
+
+            def upload(k):
+                for d, h_ in zip(devt[k], host[k]):
+                    d.copy_(h_, non_blocking=True)
+
+            def timed(step, N=200, warm=20):
+                for _ in range(warm): step()
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                for _ in range(N): step()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / N / B * 1e6
+            legs = {(k, w): [] for k in host for w in ("upload", "upload + forward_target")}
+            for r in range(rounds + 1):
+                for k in host:
+                    a_ = timed(lambda: upload(k))
+                    b_ = timed(lambda: (upload(k), eng.forward_target(*devt[k])))
+                    if r:
+                        legs[(k, "upload")].append(a_); legs[(k, "upload + forward_target")].append(b_)
+            upload("compact"); upload("float32")
+            same = bool(torch.equal(eng.forward_target(*devt["compact"])[0], eng.forward_target(*devt["float32"])[0]))
+            res[f"B={B}"] = {"bytes_per_frame": nbytes, "bit_identical": same,
+                             **{f"{k}: {w}": {"median_us": round(statistics.median(v), 2), "spread_us": round(max(v) - min(v), 2)} for (k, w), v in legs.items()}}
+        out["shapes"][shape] = res
+        eng.close()
+    print(json.dumps(out))
+
+
 if "--bank" in sys.argv:
     bank_bench()
+    sys.exit(0)
+if "--compact" in sys.argv:
+    compact_bench()
     sys.exit(0)
 SHARED = "--shared" in sys.argv
 ROUNDS = int(sys.argv[sys.argv.index("--compare") + 1]) if "--compare" in sys.argv else 0

@@ -14,6 +14,9 @@ from SUBJECT and the driving labels from DRIVER's key points as the reference's 
 and smoothed over the clip (raster.face_driving_keypoints), then drawn from the fractional points (rasterise(relative=True)).
 
     python tools/demo_clip.py --out demo_out --clip test114 --drive val024 --frames 16
+
+`--compact` hands the runner the compact form of every input -- image bytes before the mean subtraction, class maps, byte masks (a quarter of the
+bytes and less) -- and must write the same files, byte for byte.
 """
 import argparse
 import os
@@ -67,14 +70,17 @@ def clip_keypoints(clip: str):
     return kp, meta
 
 
-def crossid_labels(rs, subject_kps, driving_kps, size=(256, 256)):
+def crossid_labels(rs, subject_kps, driving_kps, size=(256, 256), compact=False):
     """Driving labels of a cross-identity pair, the reference loader's way (dataset/dataset_video_face.py:335-398): the driving clip's key points
     adapted to the subject's face and smoothed (host code of the library), drawn at the driving crop's resolution from the fractional points,
     resized, one-hot.  rs: a raster.FaceRasteriser (its device and library are used throughout).  Key points in frame coordinates.
-    Returns (labels (F,2,H,W), bbox (F,H,W), driving crop, bw)."""
+    Returns (labels (F,2,H,W), bbox (F,H,W), driving crop, bw); compact: the class map (F,H,W) and the mask as uint8."""
     pts, crop, bw = raster.face_driving_keypoints(subject_kps, driving_kps, lib=rs.lib)
     edges, bbox, _, _ = rs.rasterise(list(pts), crop, relative=True)
-    return rs.vl2ch(demo.resize_label(edges, size, lib=rs.lib), 2), demo.resize_label(bbox, size, lib=rs.lib), crop, bw
+    cls, box = demo.resize_label(edges, size, lib=rs.lib), demo.resize_label(bbox, size, lib=rs.lib)
+    if compact:
+        return cls.to(torch.uint8), box.to(torch.uint8), crop, bw
+    return rs.vl2ch(cls, 2), box, crop, bw
 
 
 def main():
@@ -90,6 +96,8 @@ def main():
                     "(tests/golden/g11_frames_<clip>.npz through the device frame loader)")
     ap.add_argument("--drive", default=None, help="with --clip: a second demo clip whose key points drive the subject given by --clip (cross-identity); "
                     "the driving labels are adapted to the subject's face proportions and smoothed as the reference's loader does")
+    ap.add_argument("--compact", action="store_true", help="compact inputs: image bytes, class maps and byte masks, widened by the engine on load "
+                    "(tsnet_*_u8); the files written equal those of a run without the flag")
     args = ap.parse_args()
     if args.drive and not args.clip:
         ap.error("--drive needs --clip (the subject)")
@@ -124,8 +132,10 @@ def main():
     edges, bbox, crop, bw = rs.rasterise(list(kp), crop_in)
     if args.clip:
         assert list(crop) == meta["crop"] and bw == meta["bw"]      # the crop arithmetic reproduces the reference's on the real clip
-    lbl = rs.vl2ch(demo.resize_label(edges), 2)                  # vl2ch(label map, "face") (demo_face.py:158,164)
-    box = demo.resize_label(bbox)
+    onehot = (lambda m: m.to(torch.uint8)) if args.compact else (lambda m: rs.vl2ch(m, 2))      # compact: the class map itself, no one-hot planes
+    mask = (lambda m: m.to(torch.uint8)) if args.compact else (lambda m: m)
+    lbl = onehot(demo.resize_label(edges))                       # vl2ch(label map, "face") (demo_face.py:158,164)
+    box = mask(demo.resize_label(bbox))
     torch.cuda.synchronize()
     t_raster = time.perf_counter() - t0
     # the first call pays one-off costs (the library's first kernel launches, the caching allocator's first blocks, torch's first
@@ -146,19 +156,21 @@ def main():
         fmeta = json.loads(str(zf["meta"]))
         x0, y0, x1, y1 = fmeta["box"]
         assert [y0, y1, x0, x1] == list(crop)
-        img = frames_mod.FrameLoader(dev).face(zf["crops"], [0, y1 - y0, 0, x1 - x0])
+        img = frames_mod.FrameLoader(dev).face(zf["crops"], [0, y1 - y0, 0, x1 - x0], as_bytes=args.compact)
         src_img = [img[i:i + 1] for i in range(K)]
         se, sb, _, _ = rs.rasterise(list(kp_all[[int(i) for i in fmeta["frames"]][:K]]), crop)
-        src_lbl, src_box = rs.vl2ch(demo.resize_label(se), 2), demo.resize_label(sb)
+        src_lbl, src_box = onehot(demo.resize_label(se)), mask(demo.resize_label(sb))
     else:
+        # noise frames of BYTE values, as every decoded frame is: the float form is byte - IMG_MEAN, the compact form the byte
         g = torch.Generator().manual_seed(1)
-        src_img = [(torch.rand((1, 3, 256, 256), generator=g) * 255.0 - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1)) for _ in range(K)]
+        src_byte = [(torch.rand((1, 3, 256, 256), generator=g) * 256.0).floor().clamp(max=255.0) for _ in range(K)]
+        src_img = [b.to(torch.uint8) if args.compact else b - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1) for b in src_byte]
         src_lbl, src_box = lbl[:K], box[:K]
     tar_lbl, tar_box, name = lbl[K:], box[K:], args.clip or "synthetic_face"
     if args.drive:
         # the whole driving clip is prepared (the moving average runs over the clip), then the first F frames drive
         t0 = time.perf_counter()
-        tar_lbl, tar_box, dcrop, dbw = crossid_labels(rs, kp_all, clip_keypoints(args.drive)[0])
+        tar_lbl, tar_box, dcrop, dbw = crossid_labels(rs, kp_all, clip_keypoints(args.drive)[0], compact=args.compact)
         torch.cuda.synchronize()
         F = min(F, tar_lbl.shape[0])
         print(f"[demo_clip] driving labels of {args.drive} adapted to {args.clip}: {tar_lbl.shape[0]} frames (crop {dcrop}, brush {dbw}) in {(time.perf_counter() - t0) * 1e3:.2f} ms")

@@ -82,6 +82,8 @@ def main():
                     "batch (tsnet_set_sources_shared) and the clip runs in groups of this many frames")
     ap.add_argument("--clip", default=None, help="OpenPose points of a real demo clip (demo/dance_example/labels/<clip>, stored with the raster golden "
                     "tests/golden/g9_raster_pose.npz: 00110 or 00164) instead of the synthetic dancer; the frames' pixels stay synthetic")
+    ap.add_argument("--compact", action="store_true", help="compact inputs: image bytes, class maps (one byte per pixel instead of 25 floats) and "
+                    "byte masks, widened by the engine on load (tsnet_*_u8); the files written equal those of a run without the flag")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -110,15 +112,17 @@ def main():
         pts = synthetic_dancer(F + K)
     pr, fr = raster.PoseRasteriser(dev), raster.FaceRasteriser(dev)
     t0 = time.perf_counter()
-    cls, box, crop = pr.clip_labels(list(pts), size=size)                   # (F+K,256,256) class indices / 0-1 masks on the device
+    cls, box, crop = pr.clip_labels(list(pts), size=size, compact=args.compact)   # (F+K,256,256) class indices / 0-1 masks on the device
     if args.clip:
         assert list(crop) == meta["crop"]                                   # the crop arithmetic reproduces the reference's on the real clip
-    lbl = fr.vl2ch(cls, 25)                                                # vl2ch(label map, "pose") (demo_pose.py:164,170)
+    lbl = cls if args.compact else fr.vl2ch(cls, 25)                       # vl2ch(label map, "pose") (demo_pose.py:164,170); compact: the class map itself
     torch.cuda.synchronize()
     t_raster = time.perf_counter() - t0
     present = sorted(int(c) for c in torch.unique(cls).tolist())
     g = torch.Generator().manual_seed(1)
-    src_img = [(torch.rand((1, 3, 256, 256), generator=g) * 255.0 - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1)) for _ in range(K)]
+    # noise frames of BYTE values, as every decoded frame is: the float form is byte - IMG_MEAN, the compact form the byte
+    src_byte = [(torch.rand((1, 3, 256, 256), generator=g) * 256.0).floor().clamp(max=255.0) for _ in range(K)]
+    src_img = [b.to(torch.uint8) if args.compact else b - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1) for b in src_byte]
     runner = demo.ClipRunner(model, src_img, [lbl[i:i + 1] for i in range(K)], [box[i:i + 1] for i in range(K)], batch=args.batch)
     frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_pose")
     print(f"[demo_pose_clip] {frames.shape[0]} frames written to {args.out} (crop {tuple(crop)}, classes present {present}); "

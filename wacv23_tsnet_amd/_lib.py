@@ -33,6 +33,8 @@ ABI_SYMBOLS = (
     "tsnet_face_adapt_stats", "tsnet_face_adapt_apply", "tsnet_smooth_keypoints",
     "tsnet_bank_capacity", "tsnet_bank_put", "tsnet_forward_bank",
     "tsnet_op_flow_k_slots", "tsnet_op_warp_k_slots", "tsnet_op_add_stats_slots", "tsnet_op_fuse_tail_slots",
+    "tsnet_forward_u8", "tsnet_set_sources_u8", "tsnet_forward_target_u8", "tsnet_bank_put_u8", "tsnet_forward_bank_u8",
+    "tsnet_op_pack_input_u8", "tsnet_prepare_frames_u8",
 )
 
 
@@ -130,6 +132,15 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.tsnet_op_warp_k_slots.argtypes = [_vp, _vp] + [C.c_int] * 5 + [_vp, _ip, C.c_int, _vp]
         lib.tsnet_op_add_stats_slots.argtypes = [_vp, _vp] + [C.c_int] * 4 + [_vp, _vp, _vp, _ip, C.c_int, _vp]
         lib.tsnet_op_fuse_tail_slots.argtypes = [_vp] * 5 + [C.c_int] * 4 + [_vp, _ip, C.c_int, _vp]
+    if hasattr(lib, "tsnet_forward_u8"):         # absent from an older build opened beside this one (tools/clip_bench.py --lib2)
+        _ip = C.POINTER(C.c_int)
+        lib.tsnet_forward_u8.argtypes = [_vp, pp, pp, pp, _vp, _vp, _fp, _vp, _vp, C.c_int, _vp]
+        lib.tsnet_set_sources_u8.argtypes = [_vp, pp, pp, pp, _fp, C.c_int, C.c_int, _vp]
+        lib.tsnet_forward_target_u8.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
+        lib.tsnet_bank_put_u8.argtypes = [_vp, C.c_int, C.c_int, pp, pp, pp, _fp, _fp, _vp]
+        lib.tsnet_forward_bank_u8.argtypes = [_vp, _ip, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]
+        lib.tsnet_op_pack_input_u8.argtypes = [pp, pp, pp] + [C.c_int] * 8 + [_fp, _fp, _vp, _vp, _vp, _vp]
+        lib.tsnet_prepare_frames_u8.argtypes = [_vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_vp, _vp]
     return lib
 
 

@@ -450,6 +450,43 @@ void run_pack_input(Ctx& ctx, const PackArgs& p, size_t amax_clear) {
     check_launch(p.nimg ? "pack_input(img)" : "pack_input(lbl)");
 }
 
+// One call's inputs in either form.  wide: fp32 tensors as the reference's loaders leave them (img = byte - IMG_MEAN (B,3,H,W), lbl one-hot
+// (B,L,H,W), bbox 0/1 floats (B,H,W)); compact (u8): the bytes they were made from (img (B,3,H,W), lbl class indices (B,H,W), bbox (B,H,W)) and
+// the image mean, widened on load by pack_input_u8_kernel.
+struct SrcIn {
+    bool u8 = false;
+    const void* const* img = nullptr;     // per source
+    const void* const* lbl = nullptr;
+    const void* const* bbox = nullptr;
+    const float* mean = nullptr;          // u8: 3 HOST floats (B, G, R)
+};
+struct TarIn { bool u8 = false; const void* lbl = nullptr; const void* bbox = nullptr; };
+
+// Stem input assembly from either form: p holds everything but the planes (p.img / p.lbl are filled here from S entries of img / lbl; img
+// null: the label-only form).  Compact inputs also leave their masks widened at bbox_out (+ s * bbox_sstride + b * H*W) when bbox is given;
+// wide masks are the caller's to copy.
+void run_pack_any(Ctx& ctx, PackArgs p, size_t amax_clear, bool u8, const void* const* img, const void* const* lbl, const void* const* bbox,
+                  const float* mean, float* bbox_out, size_t bbox_sstride) {
+    if (!u8) {
+        for (int s = 0; s < p.S; ++s) { p.img[s] = img ? static_cast<const float*>(img[s]) : nullptr; p.lbl[s] = static_cast<const float*>(lbl[s]); }
+        run_pack_input(ctx, p, amax_clear);
+        return;
+    }
+    PackU8Args q{};
+    for (int s = 0; s < p.S; ++s) {
+        q.img[s] = img ? static_cast<const unsigned char*>(img[s]) : nullptr;
+        q.lbl[s] = static_cast<const unsigned char*>(lbl[s]);
+        q.bbox[s] = bbox ? static_cast<const unsigned char*>(bbox[s]) : nullptr;
+        q.img_div[s] = p.img_div[s];
+    }
+    q.coords = p.coords; q.out = p.out; q.bbox_out = bbox_out; q.bbox_sstride = bbox_sstride;
+    q.S = p.S; q.B = p.B; q.H = p.H; q.W = p.W; q.L = p.L; q.nimg = p.nimg; q.Cp = p.Cp; q.amax_out = p.amax_out;
+    for (int c = 0; c < 3; ++c) q.mean[c] = mean ? mean[c] : 0.f;
+    if (q.amax_out) HIP_TRY(hipMemsetAsync(q.amax_out, 0, amax_clear * sizeof(unsigned), ctx.stream));
+    hipLaunchKernelGGL(pack_input_u8_kernel, dim3(pack_grid((p.H * p.W + kPackU8Px - 1) / kPackU8Px), p.S * p.B), dim3(256), 0, ctx.stream, q);
+    check_launch(p.nimg ? "pack_input_u8(img)" : "pack_input_u8(lbl)");
+}
+
 // FuseNet tail: zbar = mean over sources of cat(src_fea, tar_fea) + (y2 * alpha + beta)   (FuseTailArgs)
 void run_fuse_tail(Ctx& ctx, const FuseTailArgs& t, const int* slot = nullptr) {
     TimeScope ts(ctx, TSNET_T_ELEMWISE);
@@ -591,6 +628,7 @@ struct tsnet_engine {
     int cached_B = 0;               // SB of the cached sources: the batch of tsnet_set_sources, 1 for tsnet_set_sources_shared; 0 = no cache
     bool cached_shared = false;     // one source set for every driving frame: tsnet_forward_target takes any batch
     float* bbox_copy = nullptr;     // (K, Bmax, H, W) device copies of the source bboxes (the first SB of every source's Bmax slots)
+    float* tbox = nullptr;          // (Bmax, H, W): the driving frames' masks widened from a compact call (wide calls pass their own tensor on)
     int last_B = 0;
     int last_SB = 0;                // source-batch extent of the last forward (what "src_fea" holds per source)
     bool last_shared = false;       // ... and whether it ran on a shared source set (tsnet_train_extras refuses: its src_img is per batch element)
@@ -646,13 +684,13 @@ struct tsnet_engine {
     // else its bound is measured: max |first value| published by the producer + amax_add (decoder: the stream starts at a raw conv output)
     void resblock(Ctx& ctx, const ConvLayer& c1, const ConvLayer& c2, float* Xs, float stream_bound, const unsigned* stream_amax, float amax_add,
                   float* y1, float* y2, int N, int hh, int ww);
-    void set_sources(Ctx& ctx, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, int B, hipStream_t bbox_stream = nullptr);
-    void target_chain(Ctx& ctx, const float* tar_lbl, int B);
-    void bank_put(Ctx& ctx, int first, int count, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, const float* div);
-    void forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB, int Kc = 0, const int* slot = nullptr);
-    void forward_target(Ctx& ctx, const float* tar_lbl, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB) {
-        target_chain(ctx, tar_lbl, B);
-        forward_rest(ctx, tar_bbox, out_rgb, out_flow, B, SB);
+    void set_sources(Ctx& ctx, const SrcIn& in, int B, hipStream_t bbox_stream = nullptr);
+    void target_chain(Ctx& ctx, const TarIn& tar, int B);
+    void bank_put(Ctx& ctx, int first, int count, const SrcIn& in, const float* div);
+    void forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int SB, int Kc = 0, const int* slot = nullptr);
+    void forward_target(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int SB) {
+        target_chain(ctx, tar, B);
+        forward_rest(ctx, tar, out_rgb, out_flow, B, SB);
     }
 };
 
@@ -842,6 +880,7 @@ void tsnet_engine::alloc_all(hipStream_t s) {
     }
     float *part_f = nullptr, *part_side_f = nullptr;
     want(&part_f, 2 * part_doubles); want(&part_side_f, 2 * part_doubles);
+    want(&tbox, B * H * W);                                                  // (last: every buffer above keeps its offset)
     size_t total = 0;
     for (auto& r : req) total += r.second;
     arena_floats = total;
@@ -913,19 +952,20 @@ void tsnet_engine::encode(Ctx& ctx, std::vector<ConvLayer>& L, const float* xin,
 // bbox_stream: where the K bounding-box copies of the clip cache are enqueued.  Their only reader is the flow kernel; the one-shot forward
 // passes its side stream (the flow kernel's own lane: the copies are ordered ahead of it there and cost the caller's lane nothing --
 // three 4.7 us copy kernels + their boundaries sat in front of the stem until round 5); null = the caller's stream (clip mode).
-void tsnet_engine::set_sources(Ctx& ctx, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, int B, hipStream_t bbox_stream) {
+// Compact sources: the packing kernel widens the masks into bbox_copy itself, on the caller's lane (ordered ahead of the flow kernel by the join).
+void tsnet_engine::set_sources(Ctx& ctx, const SrcIn& in, int B, hipStream_t bbox_stream) {
     cur_B = B;
     const int H = cfg.height, W = cfg.width;
     {
         TimeScope ts(ctx, TSNET_T_PACK);
         PackArgs p{};
-        for (int s = 0; s < K; ++s) { p.img[s] = src_img[s]; p.lbl[s] = src_lbl[s]; p.img_div[s] = src_div[s]; }
+        for (int s = 0; s < K; ++s) p.img_div[s] = src_div[s];
         p.coords = cfg.addcoords ? d_coords : nullptr;
         p.out = x_img; p.S = K; p.B = B; p.H = H; p.W = W; p.L = cfg.label_nc; p.nimg = 3; p.Cp = cp_img;
         p.amax_out = amax_src();
-        run_pack_input(ctx, p, (size_t)K * B);
-        for (int s = 0; s < K; ++s)
-            HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)s * Bmax * H * W, src_bbox[s], (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice,
+        run_pack_any(ctx, p, (size_t)K * B, in.u8, in.img, in.lbl, in.bbox, in.mean, bbox_copy, (size_t)Bmax * H * W);
+        for (int s = 0; s < K && !in.u8; ++s)
+            HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)s * Bmax * H * W, in.bbox[s], (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice,
                                    bbox_stream ? bbox_stream : ctx.stream));
     }
     encode(ctx, img_enc, x_img, amax_src(), K * B, raw_img, X, cfg.enc_blocks);
@@ -939,7 +979,7 @@ void tsnet_engine::set_sources(Ctx& ctx, const float* const* src_img, const floa
 
 // `count` sources of batch 1 -> slots first .. first + count - 1 of the bank: set_sources' chain on count images, its outputs at the slot
 // offset.  x_img, raw_img, the ResnetBlock scratch and the first `count` source maxima are staging; the other slots are not touched.
-void tsnet_engine::bank_put(Ctx& ctx, int first, int count, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox, const float* div) {
+void tsnet_engine::bank_put(Ctx& ctx, int first, int count, const SrcIn& in, const float* div) {
     cur_B = 1;
     const int H = cfg.height, W = cfg.width;
     if (!bank) { std::fill(bank_filled.begin(), bank_filled.end(), 0); bank = true; cached_B = 0; cached_shared = false; }
@@ -949,14 +989,14 @@ void tsnet_engine::bank_put(Ctx& ctx, int first, int count, const float* const* 
         for (int i0 = 0; i0 < count; i0 += TSNET_MAX_SOURCES) {     // the packing kernel takes up to eight plane pointers by value
             const int n = std::min(TSNET_MAX_SOURCES, count - i0);
             PackArgs p{};
-            for (int s = 0; s < n; ++s) { p.img[s] = src_img[i0 + s]; p.lbl[s] = src_lbl[i0 + s]; p.img_div[s] = div ? div[i0 + s] : 255.0f; }
+            for (int s = 0; s < n; ++s) p.img_div[s] = div ? div[i0 + s] : 255.0f;
             p.coords = cfg.addcoords ? d_coords : nullptr;
             p.out = x_img + (size_t)i0 * H * W * cp_img; p.S = n; p.B = 1; p.H = H; p.W = W; p.L = cfg.label_nc; p.nimg = 3; p.Cp = cp_img;
             p.amax_out = amax_src() + i0;
-            run_pack_input(ctx, p, (size_t)n);
+            run_pack_any(ctx, p, (size_t)n, in.u8, in.img + i0, in.lbl + i0, in.bbox + i0, in.mean, bbox_copy + (size_t)(first + i0) * H * W, (size_t)H * W);
         }
-        for (int i = 0; i < count; ++i)
-            HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)(first + i) * H * W, src_bbox[i], (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx.stream));
+        for (int i = 0; i < count && !in.u8; ++i)
+            HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)(first + i) * H * W, in.bbox[i], (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx.stream));
     }
     float* fea = X + (size_t)first * P * C;
     encode(ctx, img_enc, x_img, amax_src(), count, raw_img, fea, cfg.enc_blocks);
@@ -968,18 +1008,17 @@ void tsnet_engine::bank_put(Ctx& ctx, int first, int count, const float* const* 
 
 // Everything that depends on the driving frame only: label encoder, its L2-normalised features and the target half of
 // FuseNet's first convolution.  Independent of the source encoder, so a full forward runs it on the side stream.
-void tsnet_engine::target_chain(Ctx& ctx, const float* tar_lbl, int B) {
+void tsnet_engine::target_chain(Ctx& ctx, const TarIn& tar, int B) {
     cur_B = B;
     const int H = cfg.height, W = cfg.width;
     {
         TimeScope ts(ctx, TSNET_T_PACK);
         PackArgs p{};
-        p.img[0] = nullptr; p.lbl[0] = tar_lbl;
         p.coords = cfg.addcoords ? d_coords : nullptr;
         p.out = x_lbl; p.S = 1; p.B = B; p.H = H; p.W = W; p.L = cfg.label_nc; p.nimg = 0; p.Cp = cp_lbl;
         // one reset for the three per-image maxima of this forward (target input, sg, decoder stream: contiguous)
         p.amax_out = amax_tar();
-        run_pack_input(ctx, p, (size_t)3 * Bmax);
+        run_pack_any(ctx, p, (size_t)3 * Bmax, tar.u8, nullptr, &tar.lbl, &tar.bbox, nullptr, tbox, 0);    // compact: the masks -> tbox
     }
     encode(ctx, lbl_enc, x_lbl, amax_tar(), B, raw_lbl, tar_fea, 0);
     run_l2norm_split(ctx, tar_fea, reinterpret_cast<unsigned short*>(that), B, P, C);
@@ -989,8 +1028,9 @@ void tsnet_engine::target_chain(Ctx& ctx, const float* tar_lbl, int B) {
 
 // SB: source-batch extent of what set_sources left behind (B, or 1 for the shared cache)
 // slot (device table, entry s*B + b) and Kc sources per frame: a forward on the source bank
-void tsnet_engine::forward_rest(Ctx& ctx, const float* tar_bbox, float* out_rgb, float* out_flow, int B, int SB, int Kc, const int* slot) {
+void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int SB, int Kc, const int* slot) {
     cur_B = B;
+    const float* tar_bbox = tar.u8 ? tbox : static_cast<const float*>(tar.bbox);      // compact: widened by target_chain's packing kernel
     const int K = Kc > 0 ? Kc : this->K;                   // sources per driving frame of THIS forward
     const int H = cfg.height, W = cfg.width, NB = K * B;
     // ---- transformation branch.  Its result (pg) is first needed by the decoder, and its kernels are latency-bound (384 workgroups):
@@ -1212,83 +1252,133 @@ int tsnet_set_source_divisors(tsnet_handle h, const float* div, int n) {
     API_END(h)
 }
 
-int tsnet_set_sources(tsnet_handle h, const float* const* src_img, const float* const* src_lbl,
-                      const float* const* src_bbox, int B, void* stream) {
+// The forward entry points take their inputs in either form (SrcIn / TarIn): the wide entries and their _u8 siblings differ in the descriptor only.
+static const void* const* vlist(const float* const* p) { return reinterpret_cast<const void* const*>(p); }
+static const void* const* vlist(const uint8_t* const* p) { return reinterpret_cast<const void* const*>(p); }
+static SrcIn src_in(const float* const* img, const float* const* lbl, const float* const* bbox) {
+    SrcIn in; in.img = vlist(img); in.lbl = vlist(lbl); in.bbox = vlist(bbox); return in;
+}
+static SrcIn src_in(const uint8_t* const* img, const uint8_t* const* lbl, const uint8_t* const* bbox, const float* mean) {
+    SrcIn in; in.u8 = true; in.img = vlist(img); in.lbl = vlist(lbl); in.bbox = vlist(bbox); in.mean = mean; return in;
+}
+static TarIn tar_in(const float* lbl, const float* bbox) { TarIn t; t.lbl = lbl; t.bbox = bbox; return t; }
+static TarIn tar_in(const uint8_t* lbl, const uint8_t* bbox) { TarIn t; t.u8 = true; t.lbl = lbl; t.bbox = bbox; return t; }
+// what a compact call needs beyond its wide sibling's checks (after them: the sibling's messages come first)
+static void check_compact(tsnet_handle h, const SrcIn* in) {
+    if (h->cfg.label_nc > 255) throw ArgError("compact inputs: class indices are bytes (label_nc <= 255)");
+    if (in && in->u8 && !in->mean) throw ArgError("compact inputs: null mean_bgr");
+}
+
+static int set_sources_any(tsnet_handle h, const SrcIn& in, int B, bool shared, void* stream) {
     API_BEGIN(h)
     check_forward_args(h, B);
-    if (!src_img || !src_lbl || !src_bbox) throw ArgError("null source list");
+    if (!in.img || !in.lbl || !in.bbox) throw ArgError("null source list");
     for (int s = 0; s < h->K; ++s)
-        if (!src_img[s] || !src_lbl[s] || !src_bbox[s]) throw ArgError("null source tensor (need n_source entries)");
+        if (!in.img[s] || !in.lbl[s] || !in.bbox[s]) throw ArgError("null source tensor (need n_source entries)");
+    if (in.u8) check_compact(h, &in);
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
-    h->set_sources(ctx, src_img, src_lbl, src_bbox, B);
+    h->set_sources(ctx, in, B);                                 // shared: K images, source-batch extent 1
+    h->cached_shared = shared;
     API_END(h)
+}
+
+int tsnet_set_sources(tsnet_handle h, const float* const* src_img, const float* const* src_lbl,
+                      const float* const* src_bbox, int B, void* stream) {
+    return set_sources_any(h, src_in(src_img, src_lbl, src_bbox), B, false, stream);
 }
 
 int tsnet_set_sources_shared(tsnet_handle h, const float* const* src_img, const float* const* src_lbl,
                              const float* const* src_bbox, void* stream) {
+    return set_sources_any(h, src_in(src_img, src_lbl, src_bbox), 1, true, stream);
+}
+
+int tsnet_set_sources_u8(tsnet_handle h, const uint8_t* const* src_img, const uint8_t* const* src_lbl, const uint8_t* const* src_bbox,
+                         const float* mean_bgr, int B, int shared, void* stream) {
+    if (h && shared && B != 1) { h->err = "set_sources_u8: a shared source set has batch 1"; return TSNET_ERR_ARG; }
+    return set_sources_any(h, src_in(src_img, src_lbl, src_bbox, mean_bgr), B, shared != 0, stream);
+}
+
+static int forward_target_any(tsnet_handle h, const TarIn& tar, float* out_rgb, float* out_flow, int B, void* stream) {
     API_BEGIN(h)
-    check_forward_args(h, 1);
-    if (!src_img || !src_lbl || !src_bbox) throw ArgError("null source list");
-    for (int s = 0; s < h->K; ++s)
-        if (!src_img[s] || !src_lbl[s] || !src_bbox[s]) throw ArgError("null source tensor (need n_source entries)");
+    check_forward_args(h, B);
+    if (!tar.lbl || !tar.bbox || !out_rgb) throw ArgError("null target/output tensor");
+    if (!h->cached_shared && h->cached_B != B) throw ArgError("forward_target: batch differs from the cached sources (call tsnet_set_sources first)");
+    if (tar.u8) check_compact(h, nullptr);
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
-    h->set_sources(ctx, src_img, src_lbl, src_bbox, 1);         // K images: source-batch extent 1
-    h->cached_shared = true;
+    h->forward_target(ctx, tar, out_rgb, out_flow, B, h->cached_B);
     API_END(h)
 }
 
 int tsnet_forward_target(tsnet_handle h, const float* tar_lbl, const float* tar_bbox,
                          float* out_rgb, float* out_flow, int B, void* stream) {
-    API_BEGIN(h)
-    check_forward_args(h, B);
-    if (!tar_lbl || !tar_bbox || !out_rgb) throw ArgError("null target/output tensor");
-    if (!h->cached_shared && h->cached_B != B) throw ArgError("forward_target: batch differs from the cached sources (call tsnet_set_sources first)");
-    Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
-    h->forward_target(ctx, tar_lbl, tar_bbox, out_rgb, out_flow, B, h->cached_B);
-    API_END(h)
+    return forward_target_any(h, tar_in(tar_lbl, tar_bbox), out_rgb, out_flow, B, stream);
+}
+
+int tsnet_forward_target_u8(tsnet_handle h, const uint8_t* tar_lbl, const uint8_t* tar_bbox,
+                            float* out_rgb, float* out_flow, int B, void* stream) {
+    return forward_target_any(h, tar_in(tar_lbl, tar_bbox), out_rgb, out_flow, B, stream);
 }
 
 int tsnet_bank_capacity(tsnet_handle h) { return h ? h->K * h->Bmax : TSNET_ERR_ARG; }
 
-int tsnet_bank_put(tsnet_handle h, int first_slot, int count, const float* const* src_img, const float* const* src_lbl,
-                   const float* const* src_bbox, const float* div, void* stream) {
+static int bank_put_any(tsnet_handle h, int first_slot, int count, const SrcIn& in, const float* div, void* stream) {
     API_BEGIN(h)
     if (!h->finalized) throw ArgError("bank_put before finalize");
     const int cap = h->K * h->Bmax;
     if (count < 1 || first_slot < 0 || first_slot > cap - count)
         throw ArgError("bank_put: slots " + std::to_string(first_slot) + " .. " + std::to_string((long long)first_slot + count - 1) + " are outside the bank (capacity " + std::to_string(cap) + ")");
-    if (!src_img || !src_lbl || !src_bbox) throw ArgError("bank_put: null source list");
+    if (!in.img || !in.lbl || !in.bbox) throw ArgError("bank_put: null source list");
     for (int i = 0; i < count; ++i) {
-        if (!src_img[i] || !src_lbl[i] || !src_bbox[i]) throw ArgError("bank_put: null source tensor (need `count` entries)");
+        if (!in.img[i] || !in.lbl[i] || !in.bbox[i]) throw ArgError("bank_put: null source tensor (need `count` entries)");
         if (div && (!(div[i] > 0.f) || !std::isfinite(div[i]))) throw ArgError("bank_put: divisors must be positive and finite");
     }
+    if (in.u8) check_compact(h, &in);
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
-    h->bank_put(ctx, first_slot, count, src_img, src_lbl, src_bbox, div);
+    h->bank_put(ctx, first_slot, count, in, div);
     API_END(h)
 }
 
-int tsnet_forward_bank(tsnet_handle h, const int* slots, int Kc, const float* tar_lbl, const float* tar_bbox,
-                       float* out_rgb, float* out_flow, int B, void* stream) {
+int tsnet_bank_put(tsnet_handle h, int first_slot, int count, const float* const* src_img, const float* const* src_lbl,
+                   const float* const* src_bbox, const float* div, void* stream) {
+    return bank_put_any(h, first_slot, count, src_in(src_img, src_lbl, src_bbox), div, stream);
+}
+
+int tsnet_bank_put_u8(tsnet_handle h, int first_slot, int count, const uint8_t* const* src_img, const uint8_t* const* src_lbl,
+                      const uint8_t* const* src_bbox, const float* mean_bgr, const float* div, void* stream) {
+    return bank_put_any(h, first_slot, count, src_in(src_img, src_lbl, src_bbox, mean_bgr), div, stream);
+}
+
+static int forward_bank_any(tsnet_handle h, const int* slots, int Kc, const TarIn& tar, float* out_rgb, float* out_flow, int B, void* stream) {
     API_BEGIN(h)
     check_forward_args(h, B);
     if (Kc < 1 || Kc > h->K) throw ArgError("forward_bank: sources per frame outside 1..n_source");
     if (!h->bank) throw ArgError("forward_bank: no source bank (call tsnet_bank_put first)");
-    if (!slots || !tar_lbl || !tar_bbox || !out_rgb) throw ArgError("forward_bank: null slot table / target / output tensor");
+    if (!slots || !tar.lbl || !tar.bbox || !out_rgb) throw ArgError("forward_bank: null slot table / target / output tensor");
     const int cap = h->K * h->Bmax;
     for (int i = 0; i < Kc * B; ++i) {
         if (slots[i] < 0 || slots[i] >= cap) throw ArgError("forward_bank: slot " + std::to_string(slots[i]) + " is outside the bank (capacity " + std::to_string(cap) + ")");
         if (!h->bank_filled[slots[i]]) throw ArgError("forward_bank: slot " + std::to_string(slots[i]) + " is not filled");
     }
+    if (tar.u8) check_compact(h, nullptr);
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
     run_slot_fill(ctx.stream, h->slot_tab, slots, Kc * B);
-    h->target_chain(ctx, tar_lbl, B);
-    h->forward_rest(ctx, tar_bbox, out_rgb, out_flow, B, 1, Kc, h->slot_tab);
+    h->target_chain(ctx, tar, B);
+    h->forward_rest(ctx, tar, out_rgb, out_flow, B, 1, Kc, h->slot_tab);
     API_END(h)
 }
 
-int tsnet_forward(tsnet_handle h, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox,
-                  const float* tar_lbl, const float* tar_bbox, float* out_rgb, float* out_flow, int B, void* stream) {
-    if (h && h->finalized && h->side_stream && !h->timing.on && tar_lbl && tar_bbox && out_rgb) {
+int tsnet_forward_bank(tsnet_handle h, const int* slots, int Kc, const float* tar_lbl, const float* tar_bbox,
+                       float* out_rgb, float* out_flow, int B, void* stream) {
+    return forward_bank_any(h, slots, Kc, tar_in(tar_lbl, tar_bbox), out_rgb, out_flow, B, stream);
+}
+
+int tsnet_forward_bank_u8(tsnet_handle h, const int* slots, int Kc, const uint8_t* tar_lbl, const uint8_t* tar_bbox,
+                          float* out_rgb, float* out_flow, int B, void* stream) {
+    return forward_bank_any(h, slots, Kc, tar_in(tar_lbl, tar_bbox), out_rgb, out_flow, B, stream);
+}
+
+static int forward_any(tsnet_handle h, const SrcIn& in, const TarIn& tar, float* out_rgb, float* out_flow, int B, void* stream) {
+    if (h && h->finalized && h->side_stream && !h->timing.on && tar.lbl && tar.bbox && out_rgb) {
         // Full forward on two lanes: the driving-frame chain (label encoder, L2 norm, target half of FuseNet conv1 --
         // small launches that leave most CUs idle at B = 4) runs on the engine's side stream while the caller's stream
         // encodes the sources; they join before the flow kernel.  Same kernels, same arithmetic: the result is
@@ -1302,22 +1392,33 @@ int tsnet_forward(tsnet_handle h, const float* const* src_img, const float* cons
         // from here on the side lane has work in flight: whatever happens below (an exception included), the caller's stream waits
         // for it before this call returns -- the side lane must not outlive the call
         SideJoin join{h->side_stream, main, h->ev_join};
-        if (!src_img || !src_lbl || !src_bbox) throw ArgError("null source list");
+        if (!in.img || !in.lbl || !in.bbox) throw ArgError("null source list");
         for (int s = 0; s < h->K; ++s)
-            if (!src_img[s] || !src_lbl[s] || !src_bbox[s]) throw ArgError("null source tensor (need n_source entries)");
-        h->target_chain(cs, tar_lbl, B);
+            if (!in.img[s] || !in.lbl[s] || !in.bbox[s]) throw ArgError("null source tensor (need n_source entries)");
+        if (in.u8 || tar.u8) check_compact(h, &in);
+        h->target_chain(cs, tar, B);
         Ctx cm(main, h->cus);
-        h->set_sources(cm, src_img, src_lbl, src_bbox, B, h->side_stream);      // (the bounding-box copies ride the side lane, ahead of the flow kernel)
+        h->set_sources(cm, in, B, h->side_stream);      // (the bounding-box copies ride the side lane, ahead of the flow kernel)
         HIP_TRY(hipEventRecord(h->ev_join, h->side_stream));
         HIP_TRY(hipStreamWaitEvent(main, h->ev_join, 0));
         join.done = true;
         Ctx ctx(main, h->cus);
-        h->forward_rest(ctx, tar_bbox, out_rgb, out_flow, B, B);
+        h->forward_rest(ctx, tar, out_rgb, out_flow, B, B);
         API_END(h)
     }
-    int rc = tsnet_set_sources(h, src_img, src_lbl, src_bbox, B, stream);
+    int rc = set_sources_any(h, in, B, false, stream);
     if (rc != TSNET_OK) return rc;
-    return tsnet_forward_target(h, tar_lbl, tar_bbox, out_rgb, out_flow, B, stream);
+    return forward_target_any(h, tar, out_rgb, out_flow, B, stream);
+}
+
+int tsnet_forward(tsnet_handle h, const float* const* src_img, const float* const* src_lbl, const float* const* src_bbox,
+                  const float* tar_lbl, const float* tar_bbox, float* out_rgb, float* out_flow, int B, void* stream) {
+    return forward_any(h, src_in(src_img, src_lbl, src_bbox), tar_in(tar_lbl, tar_bbox), out_rgb, out_flow, B, stream);
+}
+
+int tsnet_forward_u8(tsnet_handle h, const uint8_t* const* src_img, const uint8_t* const* src_lbl, const uint8_t* const* src_bbox,
+                     const uint8_t* tar_lbl, const uint8_t* tar_bbox, const float* mean_bgr, float* out_rgb, float* out_flow, int B, void* stream) {
+    return forward_any(h, src_in(src_img, src_lbl, src_bbox, mean_bgr), tar_in(tar_lbl, tar_bbox), out_rgb, out_flow, B, stream);
 }
 
 int tsnet_train_extras(tsnet_handle h, const float* const* src_img, const float* tar_img, int B,
@@ -1773,9 +1874,9 @@ int tsnet_op_fuse_tail(const float* src_fea, const float* tar_fea, const float* 
     OP_END
 }
 
-int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S, int B, int H, int W, int L, int nimg, int Cp, int coords,
-                        const float* img_div, float* out, unsigned int* amax, void* stream) {
-    OP_BEGIN
+// both forms of the packing op: the checks, the coordinate table, the launch
+static void op_pack_any(bool u8, const void* const* img, const void* const* lbl, const void* const* bbox, int S, int B, int H, int W, int L, int nimg,
+                        int Cp, int coords, const float* img_div, const float* mean, float* out, float* bbox_out, unsigned int* amax, void* stream) {
     if (S < 1 || S > TSNET_MAX_SOURCES) throw ArgError("pack op: 1 <= S <= 8 sources");
     if (!lbl || !out || !amax) throw ArgError("pack op: null tensor");
     if (nimg != 0 && nimg != 3) throw ArgError("pack op: nimg is 3 (image + label) or 0 (label only)");
@@ -1789,10 +1890,18 @@ int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S,
     const int creal = nimg + L + (coords ? 3 : 0);
     if (Cp < creal) throw ArgError("pack op: Cp is smaller than the real channel count");
     if (Cp != conv_cin_pad(Cp)) throw ArgError("pack op: Cp must be 8 or a multiple of 16");
+    if (u8) {
+        if (L > 255) throw ArgError("pack op: class indices are bytes (L <= 255)");
+        if (nimg && !mean) throw ArgError("pack op: null tensor");
+        if (bbox) {
+            if (!bbox_out) throw ArgError("pack op: null tensor");
+            for (int s = 0; s < S; ++s) if (!bbox[s]) throw ArgError("pack op: null tensor");
+        }
+    }
     Ctx ctx((hipStream_t)stream, current_device_cus());
     DevBufs mem;
     PackArgs p{};
-    for (int s = 0; s < S; ++s) { p.img[s] = nimg ? img[s] : nullptr; p.lbl[s] = lbl[s]; p.img_div[s] = nimg ? img_div[s] : 1.f; }
+    for (int s = 0; s < S; ++s) p.img_div[s] = nimg ? img_div[s] : 1.f;
     if (coords) {                                   // as tsnet_finalize builds d_coords
         std::vector<float> t((size_t)H * W * 3);
         coord_table(H, W, t.data());
@@ -1801,8 +1910,22 @@ int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S,
         p.coords = d;
     }
     p.out = out; p.S = S; p.B = B; p.H = H; p.W = W; p.L = L; p.nimg = nimg; p.Cp = Cp; p.amax_out = amax;
-    run_pack_input(ctx, p, (size_t)S * B);
+    run_pack_any(ctx, p, (size_t)S * B, u8, nimg ? img : nullptr, lbl, bbox, mean, bbox_out, (size_t)B * H * W);
     HIP_TRY(hipStreamSynchronize(ctx.stream));
+}
+
+int tsnet_op_pack_input(const float* const* img, const float* const* lbl, int S, int B, int H, int W, int L, int nimg, int Cp, int coords,
+                        const float* img_div, float* out, unsigned int* amax, void* stream) {
+    OP_BEGIN
+    op_pack_any(false, vlist(img), vlist(lbl), nullptr, S, B, H, W, L, nimg, Cp, coords, img_div, nullptr, out, nullptr, amax, stream);
+    OP_END
+}
+
+int tsnet_op_pack_input_u8(const uint8_t* const* img, const uint8_t* const* lbl, const uint8_t* const* bbox, int S, int B, int H, int W, int L,
+                           int nimg, int Cp, int coords, const float* img_div, const float* mean_bgr, float* out, float* bbox_out,
+                           unsigned int* amax, void* stream) {
+    OP_BEGIN
+    op_pack_any(true, vlist(img), vlist(lbl), vlist(bbox), S, B, H, W, L, nimg, Cp, coords, img_div, mean_bgr, out, bbox_out, amax, stream);
     OP_END
 }
 
@@ -2069,12 +2192,12 @@ int tsnet_bicubic_table(int n_in, int n_out, int* first, int* count, int* coef) 
     OP_END
 }
 
-int tsnet_prepare_frames(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
-                         const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
-                         const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
-                         int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream) {
-    OP_BEGIN
-    if (!frames || !out || !mean_bgr) throw ArgError("prepare_frames: null tensor");
+// mean_bgr null: the byte form (out holds (F,3,OH,OW) bytes)
+static void prepare_frames_any(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
+                               const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                               const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                               int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, void* out, bool u8, void* stream) {
+    if (!frames || !out || (!u8 && !mean_bgr)) throw ArgError("prepare_frames: null tensor");
     if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("prepare_frames: bad frame shape");
     if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000) throw ArgError("prepare_frames: empty or absurd crop box");
     if (oh < 1 || ow < 1 || pad_top < 0 || pad_left < 0 || pad_top + oh > OH || pad_left + ow > OW || (double)OH * OW >= 2147483647.0 / 4)
@@ -2090,10 +2213,31 @@ int tsnet_prepare_frames(const unsigned char* frames, int F, int h, int w, int x
     if (frames_row_span(ch, oh, th) > kFrRows) throw ArgError("prepare_frames: vertical reduction too steep (more than 112 taps)");
     const int gy = (OH + th - 1) / th;
     if (gy > 65535) throw ArgError("prepare_frames: output too tall");
-    FrameArgs a{frames, out, xfirst, xcount, xcoef, yfirst, ycount, ycoef, h, w, x0, y0, cw, ch, ow, oh, xtaps, ytaps, pad_top, pad_left, OH, OW, th,
-                {mean_bgr[0], mean_bgr[1], mean_bgr[2]}};
-    hipLaunchKernelGGL(prepare_frames_kernel, dim3((OW + kFrTileW - 1) / kFrTileW, gy, F), dim3(256), 0, (hipStream_t)stream, a);
+    FrameArgs a{frames, static_cast<float*>(out), xfirst, xcount, xcoef, yfirst, ycount, ycoef, h, w, x0, y0, cw, ch, ow, oh, xtaps, ytaps, pad_top, pad_left, OH, OW, th,
+                {u8 ? 0.f : mean_bgr[0], u8 ? 0.f : mean_bgr[1], u8 ? 0.f : mean_bgr[2]}};
+    const dim3 grid((OW + kFrTileW - 1) / kFrTileW, gy, F);
+    if (u8) hipLaunchKernelGGL(prepare_frames_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(prepare_frames_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
     check_launch("prepare_frames");
+}
+
+int tsnet_prepare_frames(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
+                         const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                         const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                         int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream) {
+    OP_BEGIN
+    prepare_frames_any(frames, F, h, w, x0, y0, x1, y1, xfirst, xcount, xcoef, xtaps, yfirst, ycount, ycoef, ytaps, oh, ow, pad_top, pad_left, OH, OW,
+                       mean_bgr, out, false, stream);
+    OP_END
+}
+
+int tsnet_prepare_frames_u8(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
+                            const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                            const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                            int oh, int ow, int pad_top, int pad_left, int OH, int OW, unsigned char* out, void* stream) {
+    OP_BEGIN
+    prepare_frames_any(frames, F, h, w, x0, y0, x1, y1, xfirst, xcount, xcoef, xtaps, yfirst, ycount, ycoef, ytaps, oh, ow, pad_top, pad_left, OH, OW,
+                       nullptr, out, true, stream);
     OP_END
 }
 

@@ -73,7 +73,7 @@ inline int frames_row_span(int n_in, int n_out, int th) {
 
 struct FrameArgs {
     const unsigned char* frames;         // (F, h, w, 3) RGB
-    float* out;                          // (F, 3, OH, OW), planes B, G, R
+    float* out;                          // (F, 3, OH, OW), planes B, G, R -- floats (byte - mean), or the bytes themselves (prepare_frames_body<true>)
     const int *xfirst, *xcount, *xcoef, *yfirst, *ycount, *ycoef;
     int h, w, bx0, by0, cw, ch;          // frame size; the crop box's corner in frame coordinates and its size
     int ow, oh, xtaps, ytaps, pad_top, pad_left, OH, OW, th;
@@ -88,7 +88,10 @@ __device__ __forceinline__ int fr_clip8(int acc) { const int v = acc >> kBicubic
 // pass for the crop rows its output rows read, straight from the frame (the taps of neighbouring lanes overlap: the vector L1 serves them) into
 // LDS as bytes, plane by plane; then the vertical pass from LDS, and stores fp32 rows of 64 consecutive floats per plane.  The byte image
 // between the passes never reaches memory.  Every index that comes from a table is range-checked: a bad table gives wrong pixels, not a fault.
-__global__ __launch_bounds__(256) void prepare_frames_kernel(FrameArgs a) {
+// U8: store the resized byte itself (a.out holds bytes, a.mean is not read) -- the compact image of pack_input_u8_kernel, which subtracts the mean
+// on load: (float)byte - mean is then the float store below, bit for bit.
+template <bool U8>
+__device__ __forceinline__ void prepare_frames_body(const FrameArgs& a) {
     __shared__ unsigned char hbuf[kFrRows * kFrRowBytes];
     const int tid = threadIdx.x;
     const int X0 = blockIdx.x * kFrTileW, Y0 = blockIdx.y * a.th, f = blockIdx.z;
@@ -161,8 +164,13 @@ __global__ __launch_bounds__(256) void prepare_frames_kernel(FrameArgs a) {
             }
         }
         const int p = 2 - c;                                      // RGB -> BGR
-        a.out[(((size_t)f * 3 + p) * a.OH + Y) * a.OW + X] = (float)v - a.mean[p];
+        const size_t o = (((size_t)f * 3 + p) * a.OH + Y) * a.OW + X;
+        if (U8) reinterpret_cast<unsigned char*>(a.out)[o] = (unsigned char)v;
+        else a.out[o] = (float)v - a.mean[p];
     }
 }
+
+__global__ __launch_bounds__(256) void prepare_frames_kernel(FrameArgs a) { prepare_frames_body<false>(a); }
+__global__ __launch_bounds__(256) void prepare_frames_u8_kernel(FrameArgs a) { prepare_frames_body<true>(a); }
 
 }  // namespace tsnet

@@ -450,4 +450,109 @@ __global__ __launch_bounds__(256) void pack_input_kernel(PackArgs a) {
     if (a.amax_out) tsnet_publish_amax(a.amax_out + n, vmax);      // per image; block-uniform branch: every thread of the workgroup arrives
 }
 
+// The same assembly from COMPACT inputs: one byte per value instead of four.  img[s] (B,3,H,W) bytes (planes B, G, R), lbl[s] (B,H,W) class
+// indices, optionally bbox[s] (B,H,W) mask bytes.  The widening is the arithmetic the wide form went through on its way here -- (float)byte is
+// exact, - mean and / div are the loader's and pack_input_kernel's own two fp32 operations, one-hot is a comparison (an index >= L: all
+// zeros, as vl2ch's == ci) -- so `out` and `amax_out` carry the bits pack_input_kernel gives on the widened tensors.
+struct PackU8Args {
+    const unsigned char* img[8];    // per source: (B,3,H,W) or null (label encoder input)
+    const unsigned char* lbl[8];    // per source: (B,H,W)
+    const unsigned char* bbox[8];   // per source: (B,H,W), or all null
+    const float* coords;            // (H,W,3) table or null
+    float* out;                     // (S*B, H, W, Cp)
+    float* bbox_out;                // mask of image (s, b) -> bbox_out[s * bbox_sstride + b * H*W ..] as (float)byte
+    size_t bbox_sstride;
+    int S, B, H, W, L, nimg, Cp;
+    float img_div[8];
+    float mean[3];                  // B, G, R
+    unsigned* amax_out;
+};
+
+constexpr int kPackU8Px = 4;        // consecutive pixels of one lane: one 32-bit load per plane
+
+// four consecutive bytes of a plane from pixel `pix` on (a multiple of 4) as one word, pixel i in bits 8i..: ONE 32-bit load where the
+// address is 4-byte aligned and the four pixels exist, byte loads elsewhere (plane bases are odd when H*W is: the base of the plane is
+// wave-uniform, so only the lane holding an image's tail diverges)
+__device__ __forceinline__ unsigned pack_u8_ld4(const unsigned char* plane, size_t pix, int cnt) {
+    const unsigned char* p = plane + pix;
+    if (cnt == kPackU8Px && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) return *reinterpret_cast<const unsigned*>(p);
+    unsigned v = 0;
+#pragma unroll
+    for (int i = 0; i < kPackU8Px; ++i)
+        if (i < cnt) v |= (unsigned)p[i] << (8 * i);
+    return v;
+}
+
+// grid = (blocks per image, S * B images), a lane owns kPackU8Px consecutive pixels: 64 lanes read 256 consecutive bytes of a plane and
+// write 4 * Cp consecutive floats each, as the float4 stores of pack_input_kernel.  Channel kinds are picked by selects on compile-time
+// register names (no indexed register arrays).
+__global__ __launch_bounds__(256) void pack_input_u8_kernel(PackU8Args a) {
+    const size_t HW = (size_t)a.H * a.W;
+    const int nl = a.nimg + a.L, creal = nl + (a.coords ? 3 : 0);
+    const int n = blockIdx.y;
+    const int s = n / a.B, b = n - s * a.B;
+    const unsigned char* const lbl_b = a.lbl[s] + (size_t)b * HW;
+    const unsigned char* const img_b = a.nimg ? a.img[s] + (size_t)b * 3 * HW : lbl_b;      // (nimg = 0: never read)
+    const unsigned char* const box_b = a.bbox[s] ? a.bbox[s] + (size_t)b * HW : nullptr;
+    float* const box_o = a.bbox_out + (size_t)s * a.bbox_sstride + (size_t)b * HW;
+    const float div = a.img_div[s];
+    const size_t quads = (HW + kPackU8Px - 1) / kPackU8Px;
+    float vmax = 0.f;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
+        const size_t pix = q * kPackU8Px;
+        const int cnt = HW - pix < (size_t)kPackU8Px ? (int)(HW - pix) : kPackU8Px;
+        unsigned wi0 = 0, wi1 = 0, wi2 = 0;
+        if (a.nimg) { wi0 = pack_u8_ld4(img_b, pix, cnt); wi1 = pack_u8_ld4(img_b + HW, pix, cnt); wi2 = pack_u8_ld4(img_b + 2 * HW, pix, cnt); }
+        const unsigned wl = pack_u8_ld4(lbl_b, pix, cnt);
+        float4 cr0 = make_float4(0.f, 0.f, 0.f, 0.f), cr1 = cr0, cr2 = cr0;                  // xx yy rr of the four pixels, 12 consecutive floats
+        if (a.coords) {
+            const float* cp = a.coords + pix * 3;                                             // 48 q bytes: 16-byte aligned
+            if (cnt == kPackU8Px) {
+                cr0 = *reinterpret_cast<const float4*>(cp); cr1 = *reinterpret_cast<const float4*>(cp + 4); cr2 = *reinterpret_cast<const float4*>(cp + 8);
+            } else {
+                float t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int i = 0; i < 9; ++i) if (i < cnt * 3) t[i] = cp[i];
+                cr0 = make_float4(t[0], t[1], t[2], t[3]); cr1 = make_float4(t[4], t[5], t[6], t[7]); cr2 = make_float4(t[8], 0.f, 0.f, 0.f);
+            }
+        }
+        if (box_b) {
+            const unsigned wb = pack_u8_ld4(box_b, pix, cnt);
+            float* bo = box_o + pix;
+            if (cnt == kPackU8Px && (reinterpret_cast<uintptr_t>(bo) & 15u) == 0) {
+                *reinterpret_cast<float4*>(bo) = make_float4((float)(wb & 255u), (float)((wb >> 8) & 255u), (float)((wb >> 16) & 255u), (float)(wb >> 24));
+            } else {
+#pragma unroll
+                for (int i = 0; i < kPackU8Px; ++i) if (i < cnt) bo[i] = (float)((wb >> (8 * i)) & 255u);
+            }
+        }
+        const float crd[12] = {cr0.x, cr0.y, cr0.z, cr0.w, cr1.x, cr1.y, cr1.z, cr1.w, cr2.x, cr2.y, cr2.z, cr2.w};
+#pragma unroll
+        for (int p = 0; p < kPackU8Px; ++p) {
+            if (p < cnt) {
+                // set_test_input's /255 (TSNet.py:286) on the loader's byte - IMG_MEAN: two fp32 operations, IEEE division
+                const float i0 = ((float)((wi0 >> (8 * p)) & 255u) - a.mean[0]) / div;
+                const float i1 = ((float)((wi1 >> (8 * p)) & 255u) - a.mean[1]) / div;
+                const float i2 = ((float)((wi2 >> (8 * p)) & 255u) - a.mean[2]) / div;
+                const int cls = (int)((wl >> (8 * p)) & 255u) + a.nimg;                       // the channel that is 1
+                const float x0 = crd[3 * p], x1 = crd[3 * p + 1], x2 = crd[3 * p + 2];
+                float* o = a.out + ((size_t)n * HW + pix + p) * a.Cp;
+                for (int c0 = 0; c0 < a.Cp; c0 += 4) {                                        // Cp = 8 or a multiple of 16 (conv_cin_pad)
+                    float v[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int c = c0 + e, k = c - nl;
+                        const float im = c == 0 ? i0 : (c == 1 ? i1 : i2);
+                        const float cd = k == 0 ? x0 : (k == 1 ? x1 : x2);
+                        v[e] = c < a.nimg ? im : (c < nl ? (c == cls ? 1.f : 0.f) : (c < creal ? cd : 0.f));
+                        vmax = __builtin_fmaxf(vmax, __builtin_fabsf(v[e]));
+                    }
+                    *reinterpret_cast<float4*>(o + c0) = make_float4(v[0], v[1], v[2], v[3]);
+                }
+            }
+        }
+    }
+    if (a.amax_out) tsnet_publish_amax(a.amax_out + n, vmax);      // per image; block-uniform branch: every thread of the workgroup arrives
+}
+
 }  // namespace tsnet

@@ -137,6 +137,8 @@ class ClipRunner:
         `run()` walks the clip in groups of `batch` driving frames with a ragged last group -- the same bytes as batch 1, at the batch rate;
       * `replace_source(i, ...)` swaps one source for another at 1 / K of the encoding work: from the first call on the runner keeps its sources
         in slots 0 .. K-1 of the engine's source bank (`tsnet_bank_put`, `tsnet_forward_bank`) and re-encodes slot i alone;
+      * sources and driving frames may be COMPACT (uint8: image bytes before the mean subtraction, class maps, 0 / 1 masks; `img_mean` is what the
+        float32 images have subtracted) -- per call, either form, the same bytes out: the engine widens them on load (`tsnet_*_u8`);
       * the three-panel strips and the GIF are written with PIL.
     model: a wacv23_tsnet_amd.model.TSNet on the GPU.
 
@@ -144,22 +146,45 @@ class ClipRunner:
     Release it with `close()` or use the runner as a context manager (`with ClipRunner(...) as r:`); `__del__` is only a fallback (at
     interpreter shutdown the library may already be gone)."""
 
-    def __init__(self, model, src_img: Sequence[torch.Tensor], src_lbl: Sequence[torch.Tensor], src_bbox: Sequence[torch.Tensor], batch: int = 1):
+    def __init__(self, model, src_img: Sequence[torch.Tensor], src_lbl: Sequence[torch.Tensor], src_bbox: Sequence[torch.Tensor], batch: int = 1,
+                 img_mean=IMG_MEAN):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.model = model
         self.batch = batch
+        self.img_mean = [float(v) for v in np.asarray(img_mean, dtype=np.float32)]
         # its OWN engine (the model's weights at this moment, default /255 source divisors): the model's shared engine is
         # re-created when a later forward() needs a larger batch or new weights, and carries the divisors of the last set_train_input
         self.eng = model._new_engine(batch)
         K = model.n_source
         dev = model._device()
-        mv = lambda t: t.to(dev, dtype=torch.float32).contiguous()
+        u8 = self._is_compact(src_lbl[0])
+        mv = lambda t: self._mv(t, dev, u8)
         self.src_img = [mv(x) for x in src_img[:K]]
         self.src_lbl, self.src_bbox = [mv(x) for x in src_lbl[:K]], [mv(x) for x in src_bbox[:K]]
-        self.eng.set_sources(self.src_img, self.src_lbl, self.src_bbox, shared=batch > 1)
+        self.eng.set_sources(self.src_img, self.src_lbl, self.src_bbox, shared=batch > 1, **self._mean_kw(u8))
         self._bank = False                                          # replace_source moves the sources into the engine's source bank
-        self.post = DemoPostprocessor(self.src_img[0])              # ref_img_list[0] (:180)
+        self._set_ref()
+
+    @staticmethod
+    def _is_compact(lbl: torch.Tensor) -> bool:
+        return lbl.dtype == torch.uint8
+
+    @staticmethod
+    def _mv(t: torch.Tensor, dev, u8: bool) -> torch.Tensor:
+        """a call's tensor on the device in the call's form; a compact call keeps whatever is not uint8 as it is (the engine names it)"""
+        return (t.to(dev) if u8 else t.to(dev, dtype=torch.float32)).contiguous()
+
+    def _mean_kw(self, u8: bool):
+        return {"mean": self.img_mean} if u8 else {}
+
+    def _set_ref(self):
+        """the first source image as float32 BGR - mean (widened when it came as bytes): post-processing statistics (ref_img_list[0], :180) and strips"""
+        a = self.src_img[0]
+        if a.dtype == torch.uint8:
+            a = a.float() - torch.tensor(self.img_mean, dtype=torch.float32, device=a.device).view(1, 3, 1, 1)
+        self._src0 = a
+        self.post = DemoPostprocessor(a, lib=self.eng.lib)
 
     def replace_source(self, i: int, img: torch.Tensor, lbl: torch.Tensor, bbox: torch.Tensor):
         """Source i <- (img (1,3,H,W), lbl (1,L,H,W), bbox (1,H,W)); the frames produced afterwards are those of a fresh runner built
@@ -169,15 +194,22 @@ class ClipRunner:
         if not 0 <= i < K:
             raise ValueError(f"source {i} of {K}")
         dev = self.src_img[0].device
-        mv = lambda t: t.to(dev, dtype=torch.float32).contiguous()
+        u8 = self._is_compact(lbl)
+        mv = lambda t: self._mv(t, dev, u8)
         self.src_img[i], self.src_lbl[i], self.src_bbox[i] = mv(img), mv(lbl), mv(bbox)
+        put = lambda j, n: self.eng.bank_put(j, self.src_img[j:j + n], self.src_lbl[j:j + n], self.src_bbox[j:j + n],
+                                             **self._mean_kw(self._is_compact(self.src_lbl[j])))
         if self._bank:
-            self.eng.bank_put(i, self.src_img[i:i + 1], self.src_lbl[i:i + 1], self.src_bbox[i:i + 1])
+            put(i, 1)
         else:
-            self.eng.bank_put(0, self.src_img, self.src_lbl, self.src_bbox)
+            if len({self._is_compact(t) for t in self.src_lbl}) == 1:
+                put(0, K)
+            else:                                                   # sources in both forms: a put is one form
+                for j in range(K):
+                    put(j, 1)
             self._bank = True
         if i == 0:
-            self.post = DemoPostprocessor(self.src_img[0])
+            self._set_ref()
 
     def close(self):
         if self.eng is not None:
@@ -202,7 +234,8 @@ class ClipRunner:
         if tar_lbl.shape[0] > self.batch:
             raise ValueError(f"{tar_lbl.shape[0]} driving frames, runner built for batch {self.batch}")
         dev = self.src_img[0].device
-        tl, tb = tar_lbl.to(dev, dtype=torch.float32), tar_bbox.to(dev, dtype=torch.float32)
+        u8 = self._is_compact(tar_lbl)
+        tl, tb = self._mv(tar_lbl, dev, u8), self._mv(tar_bbox, dev, u8)
         if self._bank:
             rec, _ = self.eng.forward_bank([list(range(len(self.src_img)))] * tl.shape[0], tl, tb)
         else:
@@ -221,12 +254,13 @@ class ClipRunner:
         if out_dir:
             os.makedirs(out_dir, exist_ok=True)
             strips = []
-            src_rgb = input_to_rgb(self.src_img[0][0])
+            src_rgb = input_to_rgb(self._src0[0])
             for i in range(out.shape[0]):
                 if tar_imgs is not None:
                     tar_rgb = input_to_rgb(tar_imgs[i])
                 else:                                               # no ground-truth driving frame: show the label map (every non-background class) instead
-                    m = (tar_lbls[i, 0].detach().cpu().numpy() == 0).astype(np.uint8) * 255
+                    t = tar_lbls[i].detach().cpu().numpy()
+                    m = ((t != 0) if self._is_compact(tar_lbls) else (t[0] == 0)).astype(np.uint8) * 255
                     tar_rgb = np.repeat(m[:, :, None], 3, axis=2)
                 strips.append(save_strip(src_rgb, tar_rgb, out[i], os.path.join(out_dir, f"{i:06d}_{name}.png")))
             save_gif(strips, os.path.join(out_dir, f"{name}.gif"))

@@ -162,25 +162,68 @@ class TSNetEngine:
             raise TypeError(f"{name}: expected float32, got {t.dtype}")
         return t if t.is_contiguous() else t.contiguous()
 
+    # Compact inputs (include/tsnet_abi.h, tsnet_*_u8): a call whose LABEL tensor is torch.uint8 passes the bytes the wide tensors are made
+    # from -- img (B,3,H,W) before the mean subtraction, lbl (B,H,W) class indices, bbox (B,H,W) 0 / 1 -- and the image mean as `mean=`
+    # wherever images are passed.  Every tensor of such a call must be uint8; the result has the bits of the float32 call on the widened tensors.
+    @staticmethod
+    def _prep_u8(t: torch.Tensor, shape: tuple, name: str) -> torch.Tensor:
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected compact shape {tuple(shape)}, got {tuple(t.shape)}")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{name}: expected uint8 (a compact call: its label tensor is uint8), got {t.dtype}")
+        return t if t.is_contiguous() else t.contiguous()
+
+    def _form(self, lbl: torch.Tensor, B: int):
+        """(compact?, prep, image shape, label shape, bbox shape) of a call, decided by its label tensor"""
+        H, W, L = self.cfg.height, self.cfg.width, self.cfg.label_nc
+        u8 = lbl.dtype == torch.uint8
+        form = self._prep_u8 if u8 else self._prep
+
+        def prep(t, shape, name):
+            if (t.dtype == torch.uint8) != u8:                       # a call in both forms: named before any shape (the two forms differ in shape too)
+                raise TypeError(f"{name}: {t.dtype} in a {'compact (uint8)' if u8 else 'float32'} call -- the label tensor decides the form, and "
+                                "every tensor of a call has it")
+            return form(t, shape, name)
+        return u8, prep, (B, 3, H, W), ((B, H, W) if u8 else (B, L, H, W)), (B, H, W)
+
+    @staticmethod
+    def _mean_arg(mean, u8: bool, what: str):
+        if not u8:
+            if mean is not None:
+                raise ValueError(f"{what}: mean= belongs to a compact (uint8) call; float32 images have it subtracted already")
+            return None
+        if mean is None:
+            raise ValueError(f"{what}: a compact (uint8) call needs mean= (B, G, R), what the float32 images have subtracted")
+        m = [float(x) for x in mean]
+        if len(m) != 3:
+            raise ValueError(f"{what}: mean= takes three values (B, G, R)")
+        return (C.c_float * 3)(*m)
+
     def forward(self, src_img: List[torch.Tensor], src_lbl: List[torch.Tensor], src_bbox: List[torch.Tensor],
-                tar_lbl: torch.Tensor, tar_bbox: torch.Tensor, return_flow: bool = False):
-        """tsnet_forward.  All tensors on one device.  Returns (rec (B,3,H,W), flows K x (B,h,w,2) | None)."""
+                tar_lbl: torch.Tensor, tar_bbox: torch.Tensor, return_flow: bool = False, mean=None):
+        """tsnet_forward (tsnet_forward_u8 when tar_lbl is uint8).  All tensors on one device.  Returns (rec (B,3,H,W), flows K x (B,h,w,2) | None)."""
         B = tar_lbl.shape[0]
-        H, W, L, K = self.cfg.height, self.cfg.width, self.cfg.label_nc, self.K
+        H, W, K = self.cfg.height, self.cfg.width, self.K
         if len(src_img) < K or len(src_lbl) < K or len(src_bbox) < K:
             raise ValueError(f"need {K} sources")
-        si = [self._prep(src_img[i], (B, 3, H, W), f"src_img[{i}]") for i in range(K)]
-        sl = [self._prep(src_lbl[i], (B, L, H, W), f"src_lbl[{i}]") for i in range(K)]
-        sb = [self._prep(src_bbox[i], (B, H, W), f"src_bbox[{i}]") for i in range(K)]
-        tl = self._prep(tar_lbl, (B, L, H, W), "tar_lbl")
-        tb = self._prep(tar_bbox, (B, H, W), "tar_bbox")
+        u8, prep, ishape, lshape, bshape = self._form(tar_lbl, B)
+        si = [prep(src_img[i], ishape, f"src_img[{i}]") for i in range(K)]
+        sl = [prep(src_lbl[i], lshape, f"src_lbl[{i}]") for i in range(K)]
+        sb = [prep(src_bbox[i], bshape, f"src_bbox[{i}]") for i in range(K)]
+        tl = prep(tar_lbl, lshape, "tar_lbl")
+        tb = prep(tar_bbox, bshape, "tar_bbox")
+        m = self._mean_arg(mean, u8, "forward")
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=tl.device)
         flow = torch.empty((K, B, self.h, self.w, 2), dtype=torch.float32, device=tl.device) if return_flow else None
         self._same_device(*si, *sl, *sb, tl, tb)
         with self._on_device():
-            rc = self.lib.tsnet_forward(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb),
-                                        tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
-        self._check(rc, "tsnet_forward")
+            if u8:
+                rc = self.lib.tsnet_forward_u8(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb),
+                                               tl.data_ptr(), tb.data_ptr(), m, out.data_ptr(), _ptr(flow), B, _stream_of(tl))
+            else:
+                rc = self.lib.tsnet_forward(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb),
+                                            tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
+        self._check(rc, "tsnet_forward_u8" if u8 else "tsnet_forward")
         self._keep = (si, sl, sb, tl, tb)   # keep inputs alive until the stream has consumed them
         return out, ([flow[i] for i in range(K)] if return_flow else None)
 
@@ -192,37 +235,43 @@ class TSNetEngine:
         with self._on_device():
             self._check(self.lib.tsnet_set_source_divisors(self._h, arr, len(d)), "tsnet_set_source_divisors")
 
-    def set_sources(self, src_img, src_lbl, src_bbox, shared: bool = False):
+    def set_sources(self, src_img, src_lbl, src_bbox, shared: bool = False, mean=None):
         """tsnet_set_sources: encode and cache the K sources of a batch; forward_target then takes driving frames of that batch.
         shared=True (tsnet_set_sources_shared): ONE source set, tensors of batch 1, for every driving frame -- forward_target then
         takes any batch up to max_batch, and frame b of its result has the bits of forward() on (these sources, frame b)."""
         B = src_img[0].shape[0]
         if shared and B != 1:
             raise ValueError(f"shared sources must have batch 1, got {B}")
-        H, W, L, K = self.cfg.height, self.cfg.width, self.cfg.label_nc, self.K
-        si = [self._prep(src_img[i], (B, 3, H, W), f"src_img[{i}]") for i in range(K)]
-        sl = [self._prep(src_lbl[i], (B, L, H, W), f"src_lbl[{i}]") for i in range(K)]
-        sb = [self._prep(src_bbox[i], (B, H, W), f"src_bbox[{i}]") for i in range(K)]
+        K = self.K
+        u8, prep, ishape, lshape, bshape = self._form(src_lbl[0], B)
+        si = [prep(src_img[i], ishape, f"src_img[{i}]") for i in range(K)]
+        sl = [prep(src_lbl[i], lshape, f"src_lbl[{i}]") for i in range(K)]
+        sb = [prep(src_bbox[i], bshape, f"src_bbox[{i}]") for i in range(K)]
+        m = self._mean_arg(mean, u8, "set_sources")
         self._same_device(*si, *sl, *sb)
         with self._on_device():
-            if shared:
+            if u8:
+                rc = self.lib.tsnet_set_sources_u8(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), m, B, int(shared), _stream_of(si[0]))
+            elif shared:
                 rc = self.lib.tsnet_set_sources_shared(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), _stream_of(si[0]))
             else:
                 rc = self.lib.tsnet_set_sources(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), B, _stream_of(si[0]))
-        self._check(rc, "tsnet_set_sources_shared" if shared else "tsnet_set_sources")
+        self._check(rc, "tsnet_set_sources_u8" if u8 else ("tsnet_set_sources_shared" if shared else "tsnet_set_sources"))
         self._keep_src = (si, sl, sb)
 
     def forward_target(self, tar_lbl, tar_bbox, return_flow: bool = False):
         B = tar_lbl.shape[0]
-        H, W, L, K = self.cfg.height, self.cfg.width, self.cfg.label_nc, self.K
-        tl = self._prep(tar_lbl, (B, L, H, W), "tar_lbl")
-        tb = self._prep(tar_bbox, (B, H, W), "tar_bbox")
+        H, W, K = self.cfg.height, self.cfg.width, self.K
+        u8, prep, _, lshape, bshape = self._form(tar_lbl, B)
+        tl = prep(tar_lbl, lshape, "tar_lbl")
+        tb = prep(tar_bbox, bshape, "tar_bbox")
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=tl.device)
         flow = torch.empty((K, B, self.h, self.w, 2), dtype=torch.float32, device=tl.device) if return_flow else None
         self._same_device(tl, tb)
         with self._on_device():
-            rc = self.lib.tsnet_forward_target(self._h, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
-        self._check(rc, "tsnet_forward_target")
+            fn = self.lib.tsnet_forward_target_u8 if u8 else self.lib.tsnet_forward_target
+            rc = fn(self._h, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
+        self._check(rc, "tsnet_forward_target_u8" if u8 else "tsnet_forward_target")
         self._keep = (tl, tb)
         return out, ([flow[i] for i in range(K)] if return_flow else None)
 
@@ -232,7 +281,7 @@ class TSNetEngine:
         """tsnet_bank_capacity: slots of the source bank, n_source * max_batch."""
         return int(self.lib.tsnet_bank_capacity(self._h))
 
-    def bank_put(self, slots, src_img, src_lbl, src_bbox, divisors: Optional[Sequence[float]] = None):
+    def bank_put(self, slots, src_img, src_lbl, src_bbox, divisors: Optional[Sequence[float]] = None, mean=None):
         """tsnet_bank_put: encode sources of batch 1 into slots of the bank, one tsnet_set_sources' worth of work per n_source slots.
         slots: an int (the first slot: source i goes to slot slots + i) or one slot per source, in any order; a list is split into
         contiguous runs, one call each.  divisors: per source, 255 (default) or 1 for a frame already in [0,1]."""
@@ -243,10 +292,11 @@ class TSNetEngine:
                              + ("" if divisors is None else f", {len(divisors)} divisors") + ": need one of each per source")
         if len(set(sl)) != n:
             raise ValueError("bank_put: a slot is named twice")
-        H, W, L = self.cfg.height, self.cfg.width, self.cfg.label_nc
-        si = [self._prep(src_img[i], (1, 3, H, W), f"src_img[{i}]") for i in range(n)]
-        sb_ = [self._prep(src_bbox[i], (1, H, W), f"src_bbox[{i}]") for i in range(n)]
-        sl_ = [self._prep(src_lbl[i], (1, L, H, W), f"src_lbl[{i}]") for i in range(n)]
+        u8, prep, ishape, lshape, bshape = self._form(src_lbl[0], 1)
+        si = [prep(src_img[i], ishape, f"src_img[{i}]") for i in range(n)]
+        sb_ = [prep(src_bbox[i], bshape, f"src_bbox[{i}]") for i in range(n)]
+        sl_ = [prep(src_lbl[i], lshape, f"src_lbl[{i}]") for i in range(n)]
+        m = self._mean_arg(mean, u8, "bank_put")
         self._same_device(*si, *sl_, *sb_)
         lo = 0
         while lo < n:                                           # contiguous ascending runs
@@ -257,8 +307,11 @@ class TSNetEngine:
             arr = lambda ts: (C.c_void_p * c)(*[t.data_ptr() for t in ts[lo:hi]])
             div = None if divisors is None else (C.c_float * c)(*[float(x) for x in divisors[lo:hi]])
             with self._on_device():
-                rc = self.lib.tsnet_bank_put(self._h, sl[lo], c, arr(si), arr(sl_), arr(sb_), div, _stream_of(si[0]))
-            self._check(rc, "tsnet_bank_put")
+                if u8:
+                    rc = self.lib.tsnet_bank_put_u8(self._h, sl[lo], c, arr(si), arr(sl_), arr(sb_), m, div, _stream_of(si[0]))
+                else:
+                    rc = self.lib.tsnet_bank_put(self._h, sl[lo], c, arr(si), arr(sl_), arr(sb_), div, _stream_of(si[0]))
+            self._check(rc, "tsnet_bank_put_u8" if u8 else "tsnet_bank_put")
             lo = hi
         self._keep_bank = (si, sl_, sb_)
 
@@ -283,16 +336,18 @@ class TSNetEngine:
                                                                    and all(isinstance(v, int) for v in r) for r in rows):
             raise ValueError(f"forward_bank: index must have shape (B, Kc) with B = {B} driving frames")
         Kc = len(rows[0])
-        H, W, L = self.cfg.height, self.cfg.width, self.cfg.label_nc
-        tl = self._prep(tar_lbl, (B, L, H, W), "tar_lbl")
-        tb = self._prep(tar_bbox, (B, H, W), "tar_bbox")
+        H, W = self.cfg.height, self.cfg.width
+        u8, prep, _, lshape, bshape = self._form(tar_lbl, B)
+        tl = prep(tar_lbl, lshape, "tar_lbl")
+        tb = prep(tar_bbox, bshape, "tar_bbox")
         table = (C.c_int * (Kc * B))(*[rows[b][s] for s in range(Kc) for b in range(B)])     # the ABI's layout: entry s*B + b
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=tl.device)
         flow = torch.empty((Kc, B, self.h, self.w, 2), dtype=torch.float32, device=tl.device) if return_flow else None
         self._same_device(tl, tb)
         with self._on_device():
-            rc = self.lib.tsnet_forward_bank(self._h, table, Kc, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
-        self._check(rc, "tsnet_forward_bank")
+            fn = self.lib.tsnet_forward_bank_u8 if u8 else self.lib.tsnet_forward_bank
+            rc = fn(self._h, table, Kc, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
+        self._check(rc, "tsnet_forward_bank_u8" if u8 else "tsnet_forward_bank")
         self._keep = (tl, tb)
         return out, ([flow[i] for i in range(Kc)] if return_flow else None)
 

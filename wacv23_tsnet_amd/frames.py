@@ -97,10 +97,12 @@ class FrameLoader:
             self._tables[key] = (flat, coef.shape[1])
         return self._tables[key]
 
-    def prepare(self, frames, box: Sequence[int], size: Tuple[int, int], square: bool = False, mean=IMG_MEAN) -> torch.Tensor:
+    def prepare(self, frames, box: Sequence[int], size: Tuple[int, int], square: bool = False, mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """frames: (F,h,w,3) uint8 RGB, tensor or array (uploaded once when on the host).  box: (x0, y0, x1, y1) in PIL order; it may leave the
         frame (Image.crop: zeros there).  size: (ow, oh) as Image.resize takes it.  square: resize_square's centred padding with byte 0 to
-        max(ow, oh).  Returns (F,3,H,W) float32 on the device: BGR planes of frame.crop(box).resize(size) minus `mean` (B, G, R)."""
+        max(ow, oh).  Returns (F,3,H,W) float32 on the device: BGR planes of frame.crop(box).resize(size) minus `mean` (B, G, R).
+        as_bytes=True (`tsnet_prepare_frames_u8`): the resized bytes themselves, (F,3,H,W) uint8, `mean` not applied -- the image of a compact
+        call (Engine.forward(..., mean=)), a quarter of the size; bytes.float() - mean is the float32 result, bit for bit."""
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
@@ -118,26 +120,29 @@ class FrameLoader:
         yt, ytaps = self._axis(y1 - y0, oh)
         m = np.asarray(mean, dtype=np.float32)
         mean_c = (C.c_float * 3)(float(m[0]), float(m[1]), float(m[2]))
-        out = torch.empty((F, 3, OH, OW), dtype=torch.float32, device=self.device)
+        out = torch.empty((F, 3, OH, OW), dtype=torch.uint8 if as_bytes else torch.float32, device=self.device)
         p = lambda t, off: t.data_ptr() + 4 * off
         ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        geom = (fr.data_ptr(), F, h, w, x0, y0, x1, y1, p(xt, 0), p(xt, ow), p(xt, 2 * ow), xtaps, p(yt, 0), p(yt, oh), p(yt, 2 * oh), ytaps,
+                oh, ow, pad_top, pad_left, OH, OW)
         with ctx:
-            rc = self.lib.tsnet_prepare_frames(fr.data_ptr(), F, h, w, x0, y0, x1, y1,
-                                               p(xt, 0), p(xt, ow), p(xt, 2 * ow), xtaps, p(yt, 0), p(yt, oh), p(yt, 2 * oh), ytaps,
-                                               oh, ow, pad_top, pad_left, OH, OW, mean_c, out.data_ptr(), self._stream())
+            if as_bytes:
+                rc = self.lib.tsnet_prepare_frames_u8(*geom, out.data_ptr(), self._stream())
+            else:
+                rc = self.lib.tsnet_prepare_frames(*geom, mean_c, out.data_ptr(), self._stream())
         if rc != 0:
-            raise RuntimeError(f"tsnet_prepare_frames failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+            raise RuntimeError(f"tsnet_prepare_frames{'_u8' if as_bytes else ''} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
         self._keep = [fr]                                            # alive until the stream has consumed it
         return out
 
-    def face(self, frames, crop: Sequence[int], size: Tuple[int, int] = (256, 256), mean=IMG_MEAN) -> torch.Tensor:
+    def face(self, frames, crop: Sequence[int], size: Tuple[int, int] = (256, 256), mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """The face loader's image: crop = [min_y, max_y, min_x, max_x] as raster.crop_coords returns it (get_crop_coords, not clipped to the frame)."""
         min_y, max_y, min_x, max_x = crop
-        return self.prepare(frames, (min_x, min_y, max_x, max_y), size, square=False, mean=mean)
+        return self.prepare(frames, (min_x, min_y, max_x, max_y), size, square=False, mean=mean, as_bytes=as_bytes)
 
-    def pose(self, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mean=IMG_MEAN) -> torch.Tensor:
+    def pose(self, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """The pose loader's image: crop = (xs, ys, xe, ye) as raster.pose_crop_coords returns it; 128 x 256, then padded to 256 x 256."""
-        return self.prepare(frames, crop, img_size, square=True, mean=mean)
+        return self.prepare(frames, crop, img_size, square=True, mean=mean, as_bytes=as_bytes)
 
 
 class _Null:

@@ -152,12 +152,21 @@ class TSNet(nn.Module):
 
     # ------------------------------------------------------------------ reference protocol
     def set_test_input(self, src_img_list, src_lbl_list, src_bbox_list, tar_lbl, tar_bbox,
-                       prev_tar_img=None, prev_tar_lbl=None, prev_tar_bbox=None):
+                       prev_tar_img=None, prev_tar_lbl=None, prev_tar_bbox=None, img_mean=None):
         """Same argument meaning as TSNet.set_test_input (TSNet.py:283-294).  The reference moves
         tensors to the GPU and divides images by 255 here; the move happens here too, the /255 is
-        fused into the engine's input-packing kernel.  prev_* are stored and unused, as in the reference."""
+        fused into the engine's input-packing kernel.  prev_* are stored and unused, as in the reference.
+        Compact form: when tar_lbl is torch.uint8 every tensor is uint8 -- images (B,3,H,W) BEFORE the loader's mean subtraction, class
+        maps (B,H,W) instead of one-hot labels, 0 / 1 masks (B,H,W) -- and img_mean (B, G, R) is what the loader would have subtracted;
+        a quarter (labels: 1 / (4 L)) of the bytes, the same bits out of forward()."""
         dev = self._device()
-        mv = lambda t: t.to(dev, dtype=torch.float32, non_blocking=True)
+        compact = tar_lbl.dtype == torch.uint8
+        if compact and img_mean is None:
+            raise ValueError("set_test_input: compact (uint8) inputs need img_mean=, the (B, G, R) mean the float32 images have subtracted")
+        if not compact and img_mean is not None:
+            raise ValueError("set_test_input: img_mean= belongs to compact (uint8) inputs")
+        self._img_mean = None if img_mean is None else [float(v) for v in img_mean]
+        mv = (lambda t: t.to(dev, non_blocking=True)) if compact else (lambda t: t.to(dev, dtype=torch.float32, non_blocking=True))
         self.src_img_list = [mv(x) for x in src_img_list]
         self.src_lbl_list = [mv(x) for x in src_lbl_list]
         self.src_bbox_list = [mv(x) for x in src_bbox_list]
@@ -176,6 +185,8 @@ class TSNet(nn.Module):
         then also fills warp_src_img_list, loss_warp and loss_align -- the training-mode outputs of the FORWARD
         (TSNet.py:327-331, 372-390, 402-405).  The GAN / VGG losses and the backward pass are not part of this build.
         use_prev[i] marks source i as a previously generated frame that is already in [0,1]: it skips the /255 (TSNet.py:269-276)."""
+        if tar_lbl.dtype == torch.uint8:
+            raise ValueError("set_train_input takes float32 tensors: the training-mode extras read the float images")
         self.set_test_input(src_img_list, src_lbl_list, src_bbox_list, tar_lbl, tar_bbox)
         self.tar_img = tar_img.to(self._device(), dtype=torch.float32, non_blocking=True)
         self._use_prev = None if use_prev is None else [bool(x) for x in use_prev]
@@ -194,10 +205,11 @@ class TSNet(nn.Module):
             raise RuntimeError("call set_test_input() before forward()")
         eng = self._get_engine(self.tar_lbl.shape[0])
         K = self.n_source
+        mean = {} if getattr(self, "_img_mean", None) is None else {"mean": self._img_mean}       # compact inputs (set_test_input)
         if K < eng.K:                          # fewer sources than the engine holds (set_source_num): slot s*B + b = source s of frame b
             B = self.tar_lbl.shape[0]
             part = lambda ts: [ts[s][b:b + 1] for s in range(K) for b in range(B)]
-            eng.bank_put(0, part(self.src_img_list), part(self.src_lbl_list), part(self.src_bbox_list))
+            eng.bank_put(0, part(self.src_img_list), part(self.src_lbl_list), part(self.src_bbox_list), **mean)
             rec, flows = eng.forward_bank([[s * B + b for s in range(K)] for b in range(B)], self.tar_lbl, self.tar_bbox, return_flow=self.return_flow)
             self.rec_tar_img = rec
             if self.return_flow:
@@ -208,7 +220,7 @@ class TSNet(nn.Module):
             eng.set_source_divisors(None if use_prev is None else [1.0 if p else 255.0 for p in use_prev[:K]])
             eng._use_prev_applied = use_prev
         rec, flows = eng.forward(self.src_img_list[:K], self.src_lbl_list[:K], self.src_bbox_list[:K],
-                                 self.tar_lbl, self.tar_bbox, return_flow=self.return_flow)
+                                 self.tar_lbl, self.tar_bbox, return_flow=self.return_flow, **mean)
         self.rec_tar_img = rec
         if self.return_flow:
             self.warp_grid2d_list = flows

@@ -103,6 +103,19 @@ class FaceRasteriser:
         self._keep_l = lab
         return out
 
+    def clip_labels(self, keypoints: Sequence[np.ndarray], size: Tuple[int, int] = (256, 256), crop=None, relative: bool = False,
+                    compact: bool = False):
+        """The label tensors of a clip as the model takes them: rasterise, then the loader's resize to `size` (demo.resize_label).
+        compact=False: one-hot labels (F,2,H,W) float32 (vl2ch) and masks (F,H,W) float32 0/1.  compact=True: the class map (F,H,W) and the
+        mask (F,H,W) as uint8 -- what Engine.forward_target / ClipRunner take as a compact call; no vl2ch, the stem's packing kernel makes
+        the one-hot planes on load.  Returns (labels, masks, crop)."""
+        from .demo import resize_label
+        edges, bbox, crop, _ = self.rasterise(keypoints, crop, relative)
+        cls, box = resize_label(edges, size, lib=self.lib), resize_label(bbox, size, lib=self.lib)
+        if compact:
+            return cls.to(torch.uint8), box.to(torch.uint8), crop          # exact: the maps hold 0 / 1
+        return self.vl2ch(cls, 2), box, crop
+
 
 # ------------------------------------------------------------------------------------------------- cross-identity face pairs
 def _clip_array(kps, what: str) -> np.ndarray:
@@ -327,14 +340,19 @@ class PoseRasteriser:
         self._keep += [m, yt, xt]
         return out
 
-    def clip_labels(self, points: Sequence[np.ndarray], size: Tuple[int, int], window=None, img_size=(128, 256)):
+    def clip_labels(self, points: Sequence[np.ndarray], size: Tuple[int, int], window=None, img_size=(128, 256), compact: bool = False):
         """The label tensors of a clip as the data loader hands them to the model: class maps (F,256,256) float (vl2ch makes them one-hot),
-        bounding-box masks (F,256,256) float 0/1, and the crop used (from the first frame when not given, :331-334)."""
+        bounding-box masks (F,256,256) float 0/1, and the crop used (from the first frame when not given, :331-334).
+        compact=True: the same two maps as uint8 (class indices 0..24, masks 0 / 1) -- a compact call's labels and masks as they are, no
+        vl2ch: the stem's packing kernel makes the one-hot planes on load."""
         if window is None:
             window = pose_crop_coords(points[0], size)
         cls = self.rasterise(points, size, window)
         box = self.bbox(cls)
-        return self.to_square(cls, img_size), self.to_square(box, img_size, binarise=True), window
+        cls, box = self.to_square(cls, img_size), self.to_square(box, img_size, binarise=True)
+        if compact:
+            cls, box = cls.to(torch.uint8), box.to(torch.uint8)             # exact: small integers
+        return cls, box, window
 
 
 class _Null:
