@@ -371,10 +371,30 @@ void run_upsample(Ctx& ctx, const float* x, const float* alpha, const float* bet
     check_launch("upsample2x");
 }
 
-// RGB head (head_conv.hpp): head_conv3_kernel for widths that are multiples of 16 (every reference caller: ngf = 64), the
-// one-pixel-per-thread form for narrower nets.  The choice depends on the width alone; head_conv3's tile rows follow conv_plan.hpp head_rows
-// unless force_rows (8, 16, 32: operator tests) says otherwise.
-void launch_head(const HeadArgs& ha, int hh, int ww, int B, hipStream_t s, int cus, int force_rows = 0) {
+// RGB head.  Widths that are multiples of 16 under a fused InstanceNorm + ReLU (every forward of a model with n_downsampling > 0: the
+// operand then has the a-priori bound sqrt(H W)) run the folded MFMA form (head_mfma.hpp) on the packed planes `wq`; without the transform
+// head_conv3_kernel (head_conv.hpp), and the one-pixel-per-thread form for narrower nets.  The choice depends on the width and on the
+// presence of the transform alone, never on the batch; head_conv3's tile rows follow conv_plan.hpp head_rows, the folded form runs 8-row tiles,
+// unless force_rows (8, 16, 32: operator tests) says otherwise; tile rows are bit-neutral in both.
+void launch_head(const HeadArgs& ha, int hh, int ww, int B, hipStream_t s, int cus, int force_rows = 0, const unsigned short* wq = nullptr,
+                 const float* wq_unscale = nullptr) {
+    if (ha.C % (2 * kHead3Ch) == 0 && ha.alpha) {
+        if (!wq || !wq_unscale) throw std::logic_error("head: the folded filter planes are missing");
+        if ((double)B * hh * ww * ha.C * 4 >= 2147483648.0 || B > 65535) throw ArgError("head: tensor too large");
+        HeadMfmaArgs m{};
+        m.x = ha.x; m.alpha = ha.alpha; m.beta = ha.beta; m.wq = wq; m.w_unscale = wq_unscale; m.bias = ha.bias; m.y = ha.y;
+        m.N = B; m.H = hh; m.W = ww; m.C = ha.C; m.composite = ha.composite; m.fore_x0 = ha.fore_x0; m.fore_x1 = ha.fore_x1;
+        for (int c = 0; c < 3; ++c) m.bg[c] = ha.bg[c];
+        m.x_bf16 = ha.x_bf16;
+        const int sa = h2_scale_log2(std::sqrt((float)hh * (float)ww));        // |relu(IN(x))| <= sqrt(H W - 1)
+        m.in_scale = std::ldexp(1.0f, sa); m.in_unscale = std::ldexp(1.0f, -sa);
+        // 8-row tiles in every batch: 40 KB of LDS and 135 VGPRs put four workgroups = two waves on every SIMD, which hides the staging round trips
+        // the 16- and 32-row tiles (one wave per SIMD) wait out: 53 against 78 - 80 us at B = 4, 28 against 63 us for one frame (profiles/head_mfma.txt)
+        launch_head_mfma(m, force_rows ? force_rows : 8, s);
+        check_launch("head_mfma");
+        ++g_launch_counters[2];
+        return;
+    }
     if (ha.C % (2 * kHead3Ch) != 0) {
         if (force_rows) throw ArgError("head: the narrow head (C not a multiple of 16) has no tile rows to force");
         const int tiles = ((ww + kHeadT - 1) / kHeadT) * ((hh + kHeadT - 1) / kHeadT);
@@ -585,6 +605,8 @@ struct tsnet_engine {
     std::vector<ConvLayer*> all_layers;   // every layer that runs on the MFMA kernels (all but the RGB head)
     float* head_w = nullptr;              // [49][ngf][4] weights of the RGB head (head_conv.hpp)
     const float* head_bias = nullptr;
+    unsigned short* head_wq = nullptr;    // folded fp16 (hi, lo) filter planes of the head's MFMA form (head_mfma.hpp) and their un-scale factor
+    const float* head_wq_unscale = nullptr;
 
     // device memory
     float* wpack = nullptr; size_t wpack_floats = 0;    // ONE buffer: biases, RGB-head table, un-scale factors, operand planes of every layer
@@ -772,7 +794,10 @@ void tsnet_engine::alloc_all(hipStream_t s) {
     off += (size_t)49 * cfg.ngf * 4 + 64;  // + one 16-channel row: the narrow-net head kernel reads whole 16-channel rows of the last tap
     off = (off + 63) / 64 * 64;
     const size_t tab_off = off;
-    off += round_up((int)all_layers.size(), 64);
+    off += round_up((int)all_layers.size() + 1, 64);       // + the RGB head's folded planes
+    off = (off + 63) / 64 * 64;
+    const size_t head_planes_off = off;    // fp16 (hi, lo) planes of the head's folded filters (head_mfma.hpp): 80 ngf x 32 x 2 halves
+    if (cfg.ngf % 16 == 0) off += head_mfma_table_halves(cfg.ngf) / 2;
     off = (off + 63) / 64 * 64;
     const size_t planes_off = off;
     size_t o16 = 0;
@@ -821,6 +846,19 @@ void tsnet_engine::alloc_all(hipStream_t s) {
         head_bias = wpack + dec_head.b_off;
         hipLaunchKernelGGL(pack_head_weights_kernel, dim3(64), dim3(256), 0, s, stage, head_w, cfg.ngf);
         check_launch("pack_head_weights");
+        if (cfg.ngf % 16 == 0) {           // the folded form's planes, in every operand mode (the head always runs three products)
+            float mx = 0.f;
+            for (float v : pw.host) { const float av = std::fabs(v); if (av > mx) mx = av; }
+            if (!std::isfinite(mx)) throw WeightError("parameter '" + dec_head.wparam + "' holds a non-finite value");
+            const int sw = mx > 0.f ? h2_scale_log2(mx) : 0;
+            const float unscale = std::ldexp(1.0f, -sw);
+            const size_t slot = tab_off + all_layers.size();
+            HIP_TRY(hipMemcpyAsync(wpack + slot, &unscale, sizeof(float), hipMemcpyHostToDevice, s));
+            head_wq = reinterpret_cast<unsigned short*>(wpack + head_planes_off);
+            head_wq_unscale = wpack + slot;
+            pack_head_mfma(stage, cfg.ngf, std::ldexp(1.0f, sw), head_wq, s);
+            check_launch("pack_head_mfma");
+        }
         HIP_TRY(hipStreamSynchronize(s));
     }
     HIP_TRY(hipFree(stage));
@@ -1111,7 +1149,7 @@ void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, floa
         ha.N = B; ha.H = hh; ha.W = ww; ha.C = cc; ha.x_bf16 = st16 && cfg.n_downsampling > 0;
         ha.composite = cfg.pose_composite; ha.fore_x0 = 64; ha.fore_x1 = 192;          // TSNet_pose.py:279
         for (int c = 0; c < 3; ++c) ha.bg[c] = (-cfg.pose_mean[c]) / 255.0f;             // TSNet_pose.py:276
-        launch_head(ha, hh, ww, B, ctx.stream, ctx.cus);
+        launch_head(ha, hh, ww, B, ctx.stream, ctx.cus, 0, head_wq, head_wq_unscale);
     }
     last_B = B; last_SB = SB; last_shared = cached_shared; last_bank = slot != nullptr;
     HIP_TRY(hipEventRecord(ev_done, ctx.stream));       // what tsnet_stage_ptr orders its widening pass behind
@@ -1642,7 +1680,21 @@ int tsnet_op_head(const float* x, int N, int H, int W, int C, const float* in_al
     ha.N = N; ha.H = H; ha.W = W; ha.C = C;
     ha.composite = hr.composite; ha.fore_x0 = 64; ha.fore_x1 = 192;
     for (int c = 0; c < 3; ++c) ha.bg[c] = bg ? bg[c] : 0.f;
-    launch_head(ha, H, W, N, s, current_device_cus(), hr.rows);
+    unsigned short* wq = nullptr; float* un = nullptr;
+    if (C % 16 == 0 && in_alpha) {         // the folded MFMA form's planes for this call
+        std::vector<float> hw(wn);
+        HIP_TRY(hipMemcpy(hw.data(), w_oihw, wn * sizeof(float), hipMemcpyDefault));
+        float mx = 0.f;
+        for (float v : hw) mx = std::max(mx, std::fabs(v));
+        const int sw = mx > 0.f ? h2_scale_log2(mx) : 0;
+        const float unscale = std::ldexp(1.0f, -sw);
+        wq = mem.alloc<unsigned short>(head_mfma_table_halves(C) * sizeof(unsigned short));
+        un = mem.alloc<float>(sizeof(float));
+        HIP_TRY(hipMemcpy(un, &unscale, sizeof(float), hipMemcpyHostToDevice));
+        pack_head_mfma(wd, C, std::ldexp(1.0f, sw), wq, s);
+        check_launch("pack_head_mfma");
+    }
+    launch_head(ha, H, W, N, s, current_device_cus(), hr.rows, wq, un);
     HIP_TRY(hipStreamSynchronize(s));
     OP_END
 }

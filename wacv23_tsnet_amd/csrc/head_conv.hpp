@@ -2,12 +2,14 @@
 // (model/TSNet.py:151-152), with the producer's InstanceNorm+ReLU applied on load and, for the pose
 // model, the fixed-background composite (model/TSNet_pose.py:416-417) in the epilogue.
 //
-// Why not the MFMA kernel: with 3 output channels the GEMM's N pads to 32, so 91 % of the matrix work
-// is wasted (0.58 ms for 4.9 GFLOP).  Here every thread owns one output pixel and its 3 channels:
-// the (16+6)x(16+6) input patch is staged through LDS 16 channels at a time in a [channel-quad][pixel]
-// image (adjacent pixels = adjacent 16-byte slots: conflict-free ds_read_b128), and the weights are
-// wave-uniform, so they arrive through the scalar cache as SGPR operands of the FMAs (12 FMA per LDS
-// read).  VALU-bound: 2.47 GFMA per forward = ~35 us at the fp32 vector peak.
+// These are the VECTOR forms.  The forward of every model with n_downsampling > 0 (a fused InstanceNorm + ReLU in front of the head, widths that
+// are multiples of 16) runs the head on the matrix pipe instead: head_mfma.hpp folds a 2 x 4 block of output pixels x 3 channels into the
+// MFMA's N, so 0.46 of the matrix work is useful.  What was priced and dropped in earlier rounds was the im2col GEMM with ONE output pixel per
+// row: Cout = 3 pads to 32 columns and 91 % of the matrix work is zeros (0.58 ms for 4.9 GFLOP).  The kernels below stay for the cases without an
+// a-priori operand bound (alpha == null: head_conv3) and for narrow nets (head_conv_kernel).  Here every thread owns one output pixel and its
+// 3 channels: the (16+6)x(16+6) input patch is staged through LDS 16 channels at a time in a [channel-quad][pixel] image (adjacent pixels =
+// adjacent 16-byte slots: conflict-free ds_read_b128), and the weights are wave-uniform, so they arrive through the scalar cache as SGPR
+// operands of the FMAs (12 FMA per LDS read).  VALU-bound: 2.47 GFMA per forward = ~35 us at the fp32 vector peak.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -31,6 +31,26 @@ void launch_conv_g64(const ConvArgs& a, const ConvPlan& p, int nprod, hipStream_
 // conv_h2s32.hpp -- 7 x 7 stems at 32 raw input channels (the pose model) as a patch kernel: 4 x 32 pixels x 64 channels; the same bits as conv_h2r
 void launch_conv_h2s32(const ConvArgs& a, int nprod, hipStream_t s);
 
+// head_mfma.hpp -- the RGB head on the matrix pipe (2 x 4 output pixels x 3 channels folded into the MFMA's N); built in conv_g64_launch.cpp
+struct HeadMfmaArgs {
+    const float* x;             // (N,H,W,C) raw output of the last up-convolution, NHWC (bf16 if x_bf16)
+    const float* alpha;         // (N*C) InstanceNorm scale / shift of x
+    const float* beta;
+    const unsigned short* wq;   // folded filter planes [C/8 stages][40 steps][hi, lo][64 lanes][8] of w * 2^sw (pack_head_mfma_kernel)
+    const float* w_unscale;     // device scalar 2^-sw
+    const float* bias;          // (3)
+    float* y;                   // (N,3,H,W) NCHW
+    int N, H, W, C;
+    int composite, fore_x0, fore_x1;
+    float bg[3];
+    int x_bf16;
+    float in_scale, in_unscale; // 2^sa, 2^-sa from the bound sqrt(H W)
+};
+
+constexpr size_t head_mfma_table_halves(int C) { return (size_t)(C / 8) * 40 * 2 * 64 * 8; }     // 16-bit entries of the folded filter planes (80 C x 32 x 2)
+void launch_head_mfma(const HeadMfmaArgs& a, int rows, hipStream_t s);                             // rows: 8, 16 or 32 (tile height)
+void pack_head_mfma(const float* w_oihw_dev, int C, float scale, unsigned short* planes, hipStream_t s);
+
 // flow_persist.hpp -- flow_kernel_p: a.K, a.G (flowp_plan), a.part, a.cnt set by the caller; variant: tools build only
 void launch_flow_p(const FlowArgs& a, int variant, hipStream_t s, const int* slot = nullptr);      // slot (device): the source bank's form
 // flow_sweep.hpp -- flow_kernel<NT>: NT = 1 or 2 target blocks per workgroup, `grid` workgroups, `lds` = flow_lds_bytes(NT, h, w, C)
