@@ -123,7 +123,7 @@ inline HeadRequest decode_head_code(int code) {
 }
 
 constexpr size_t w1_lds_bytes_host(int Cin, int tables) {       // conv_w1.hpp w1_lds_bytes for the two-plane stages
-    return 3 * (size_t)(2 * (4 * 2 * 2 * (96 * 16 + 64) + 32)) + (size_t)tables * 2 * ((Cin + 31) / 32 * 32) * 4;
+    return 3 * (size_t)(2 * (4 * 2 * 2 * (96 * 16 + 64) + 16)) + (size_t)tables * 2 * ((Cin + 31) / 32 * 32) * 4;
 }
 // a layer packed in the Winograd-along-x form runs conv_w1 and nothing else: 3 x 3 / stride 1 / pad 1 on frames of whole 4 x 32 tiles
 inline bool w1_eligible(int ks, int stride, int pad, int cin, int H, int W) {

@@ -19,18 +19,21 @@
 //     64 VGPRs.  The K loop runs in PERIODS of two 16-channel slabs (six steps, one barrier, one accumulation chain); an A fragment = two
 //     consecutive V rows (32 pairs) of the wave's position: rows (ky, ky+1) and (ky+2, ky+3) for the two 32-pair halves -- five distinct
 //     fragments serve the six (half, ky) uses of a slab; weight fragments two steps ahead (three register sets); s_setprio 2;
-//   * six PRODUCERS (waves 8..13) turn the input patch into V: a period's V has 12 wave-sized items (input row, half of the pairs), two per
-//     producer; lane = (pair, channel quad): the 8 lanes of a pixel read its 32 channels as ONE 128-byte line (a lane per (pixel, octet)
-//     touched 32 - 64 lines per load, and the texture path -- shared with the weight fragments -- bound the first forms of this kernel);
-//     four input pixels per lane, fetched one item ahead (reflection / zero padding in the offsets); IN + ReLU; per position one add, the
-//     split, one ds_write_b64 per plane;
-//   * V lives in LDS, three stages of [slab][position][plane][octet][6 rows x 16 pairs] x 16 B (50 KiB each, region pitches padded so
-//     that a producer's 16-lane write group spans all banks): period s is consumed while period s+2 is produced, so the first A fragments
+//   * six PRODUCERS (waves 8..13) turn the input patch into V: a period's V has 6 wave-sized items (one input row x all 16 pairs), one per
+//     producer; lane = (two ADJACENT pairs, channel quad): the 8 lanes of a pixel read its 32 channels as ONE 128-byte line (a lane per
+//     (pixel, octet) touched 32 - 64 lines per load, and the texture path -- shared with the weight fragments -- bound the first forms of this
+//     kernel); SIX input pixels per lane serve its two pairs (a lane per pair fetched eight: every pixel twice -- 36 producer wave loads per
+//     period instead of 48 beside the 96 weight-fragment loads, and the K loop is bound by the count of its wave loads: DESIGN.md section
+//     4.7-B), fetched one item ahead (reflection / zero padding in the offsets); IN + ReLU once per pixel; per pair and position one add,
+//     the split, one ds_write_b64 per plane;
+//   * V lives in LDS, three stages of [slab][position][plane][octet][6 rows x 16 pairs] x 16 B (50 KiB each, region and slab pitches padded
+//     so that a producer's 16-lane write group spans all banks): period s is consumed while period s+2 is produced, so the first A fragments
 //     of period s+1 are fetched BEFORE the barrier (no exposed LDS latency at a period's start);
 //   * epilogue: the four positions of a pair meet through LDS (64 KiB over the V stages), consumer (row, half) forms its 32 pixels x 32
 //     channels and runs the shared conv_epilogue (bias, addend, fp64 statistics, in-kernel finalize, amax); the producers keep the
 //     barriers company;
 //   * <= 128 VGPRs (two SIMDs carry four of the fourteen waves; tests/test_isa.py), 154 - 158 KiB of LDS.
+// Bits: the item shape moves no arithmetic -- tests/test_emu_w1_pair_lanes.py holds the kernel to the record of the half-row items, value for value.
 // How it got here, form by form with measurements: DESIGN.md section 4.4.
 #pragma once
 #include <type_traits>
@@ -39,10 +42,10 @@
 
 namespace tsnet {
 
-constexpr int kW1Prod = 6;                                                        // producer waves (transform): two items of a period each
+constexpr int kW1Prod = 6;                                                        // producer waves (transform): one item (input row) of a period each
 constexpr int kW1Waves = 8 + kW1Prod;                                             // eight consumers (MFMA) + the producers
 constexpr int kW1Reg = 96 * 16 + 64;                                              // one (slab, position, plane, octet) region of V + its bank pad
-constexpr int kW1Stage(int npl) { return 2 * (4 * npl * 2 * kW1Reg + 32); }       // bytes of one V stage: two slabs
+constexpr int kW1Stage(int npl) { return 2 * (4 * npl * 2 * kW1Reg + 16); }       // bytes of one V stage: two slabs
 constexpr int w1_lds_bytes(int Cin, int npl = 2, int tables = 1) {
     const int v = 3 * kW1Stage(npl), ex = 4 * 64 * 64 * 4 + 2048;                  // V stages | output exchange
     return (v > ex ? v : ex) + tables * 2 * ((Cin + 31) / 32 * 32) * 4;           // + the transform table(s): whole periods of 32 channels
@@ -81,26 +84,87 @@ static __device__ unsigned long long g_w1_prof[kW1ProfTiles * kW1Waves * kW1Prof
 
 // ---------------------------------------------------------------------------------------------------------------
 // THE ARITHMETIC of the kernel, written once: the chunk path below and the one-tile path (conv_w1_one.hpp) differ in how a workgroup is
-// scheduled -- prologue, tiles per workgroup, where the next fetch comes from -- and share these three pieces, so a change to the
-// transform, the split, the product order or the output transform is made in one place (the two kernels used to carry a copy each).
+// scheduled -- prologue, tiles per workgroup, where the next fetch comes from -- and share these three pieces, so a change to the item's
+// shape, the transform, the split, the product order or the output transform is made in one place (the two kernels used to carry a copy each).
 //
-// (1) Producer: four input pixels x four channels of one column pair -> the four Winograd positions, split, one ds_write_b64 per plane.
-//     b[q] = pixel q of the pair as fetched (zeros for a padded pixel); pad[q] = that pixel lies in the ZERO padding of an InstanceNorm-ed
-//     input (re-zeroed after the affine transform: a padded pixel is zero, not beta); ta = the image's table at the item's first channel
-//     (alpha * s, then beta * s at + cp32); scale = the operand scale s of a raw input.
+// (1) Producer.  An ITEM = one input row of the patch x all 16 column pairs x 32 channels (the two slabs of a period): lane = (g = lane >> 3, channel
+//     quad = lane & 7) owns the ADJACENT pairs 2g and 2g + 1 and fetches the SIX pixels at columns ox0 - 1 + 4g + q, q = 0..5, once: pair 2g is formed
+//     from pixels 0..3, pair 2g + 1 from pixels 2..5 -- the two pixels the pairs share stay in the lane's own registers (six wave loads serve what eight
+//     served while a lane owned one pair; passing them between lanes cost what it saved).  Load q of the wave still reads eight
+//     whole 128-byte lines.  Written once for the chunk path below and the one-tile path (conv_w1_one.hpp), which differ in schedule only:
+//       w1_item_offsets  byte offsets of the item's pixels at the lane's channel quad, kOOB for a pixel in the padding (or of a tile that does not exist: !real)
+//       w1_item_dst      where pair 2g of input row prow goes inside a V stage (pair 2g + 1: + 16 B, an immediate)
+//       w1_item_fetch    the six loads
+//       w1_item_values   IN + ReLU (or the operand scale) ONCE per fetched pixel: b -> d
+//       w1_item_store    the four Winograd positions of both pairs from d, the split, one ds_write_b64 per (pair, position, plane)
+//     b[q] = pixel q as fetched (zeros for a padded pixel); pad[q] = that pixel lies in the ZERO padding of an InstanceNorm-ed input (re-zeroed after
+//     the affine transform: a padded pixel is zero, not beta -- for both pairs a shared pixel belongs to); ta = the image's table at the item's first
+//     channel (alpha * s, then beta * s at + cp32); scale = the operand scale s of a raw input.
 //     A raw input WITHOUT ReLU (the residual stream, the upsampled maps: NO_RELU) is transformed unscaled and scaled inside the split --
-//     s is a power of two, (d0 - d2) s == d0 s - d2 s exactly, and v_fma_mix takes the factor as an operand (TSNET_SPLIT_2PAIRS_SCALED):
-//     16 multiplies fewer per item in the waves whose instruction count bounds the K loop (60 -> 52 VALU per item).
-template <int NPROD, bool AFFINE, bool ZPAD_KEEP, bool NO_RELU, int POSB, int PLANE_V>
-__device__ __forceinline__ void w1_put_item(const F4 (&b)[4], const bool (&pad)[4], const float* ta, const int cp32, const float scale,
-                                            const float relu_floor, unsigned char* dst) {
-    struct alignas(8) U2 { unsigned x, y; };
+//     s is a power of two, (d0 - d2) s == d0 s - d2 s exactly, and v_fma_mix takes the factor as an operand (TSNET_SPLIT_2PAIRS_SCALED).
+constexpr int kW1Pix = 6;                                                         // pixels a lane fetches per item: two pairs of four, two of them shared
+// Of a lane's six pixels only the first and the last can lie outside the row (columns ox0 - 1 and ox0 + 32 of the lanes at the tile's edges: reflected,
+// or in the zero padding); pixels 1..4 are columns ox0 + 4g .. ox0 + 4g + 3 of the tile itself, one pixel pitch (Cin * 4 bytes, wave-uniform: it
+// goes into the load's scalar offset) apart.  Three offsets per item instead of six: the producers hold two tiles' worth across the epilogue.
+struct W1ItemOffs { unsigned first, mid, last; };                                 // pixel 0 | pixel 1 (pixels 2..4: + the pixel pitch each) | pixel 5; kOOB = zeros
+
+__device__ __forceinline__ void w1_item_offsets(const ConvArgs& a, const int img, const int oy0, const int ox0, const int prow, const int g, const int quad,
+                                                const bool real, W1ItemOffs& o) {
+    int iy = oy0 - 1 + prow;
+    bool rok = real;
+    if (a.reflect) {
+        iy = iy < 0 ? -iy : iy;
+        iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
+    } else {
+        rok = rok && iy >= 0 && iy < a.H;
+    }
+    auto at = [&](int q) __attribute__((always_inline)) {
+        int ix = ox0 - 1 + 4 * g + q;
+        bool ok = rok;
+        if (a.reflect) {
+            ix = ix < 0 ? -ix : ix;
+            ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
+        } else {
+            ok = ok && ix >= 0 && ix < a.W;
+        }
+        return ok ? (unsigned)(((img * a.H * a.W + iy * a.W + ix) * a.Cin + quad * 4) * 4) : kOOB;
+    };
+    o.first = at(0); o.mid = at(1); o.last = at(kW1Pix - 1);
+}
+
+__device__ __forceinline__ void w1_item_pads(const W1ItemOffs& o, bool (&pad)[kW1Pix]) {     // which pixels read zeros
+#pragma unroll
+    for (int q = 0; q < kW1Pix; ++q) pad[q] = (q == 0 ? o.first : (q == kW1Pix - 1 ? o.last : o.mid)) == kOOB;
+}
+
+__device__ __forceinline__ W1ItemOffs w1_item_masked(const W1ItemOffs& o, const bool keep) {  // the item's offsets, or zeros for the whole item
+    W1ItemOffs m;
+    m.first = keep ? o.first : kOOB; m.mid = keep ? o.mid : kOOB; m.last = keep ? o.last : kOOB;
+    return m;
+}
+
+template <int SLABB>
+__device__ __forceinline__ int w1_item_dst(const int prow, const int g, const int quad) {   // [slab quad >> 2][octet (quad >> 1) & 1][row][pair] x 16 B, + 8 B for the odd quad
+    return (quad >> 2) * SLABB + ((quad >> 1) & 1) * kW1Reg + (prow * 16 + 2 * g) * 16 + (quad & 1) * 8;
+}
+
+__device__ __forceinline__ void w1_item_fetch(const tsnet_brsrc_t& rsx, const W1ItemOffs& o, const unsigned soff, const unsigned pitch, F4 (&b)[kW1Pix]) {
+#pragma unroll
+    for (int q = 0; q < kW1Pix; ++q) {
+        if (q == 0) b[q] = TSNET_BUF_LOAD16(rsx, o.first, soff);
+        else if (q == kW1Pix - 1) b[q] = TSNET_BUF_LOAD16(rsx, o.last, soff);
+        else b[q] = TSNET_BUF_LOAD16(rsx, o.mid, soff + (unsigned)(q - 1) * pitch);
+    }
+}
+
+template <int NPROD, bool AFFINE, bool ZPAD_KEEP, bool NO_RELU>
+__device__ __forceinline__ void w1_item_values(const F4 (&b)[kW1Pix], const bool (&pad)[kW1Pix], const float* ta, const int cp32, const float scale,
+                                               const float relu_floor, F4 (&d)[kW1Pix]) {
     constexpr bool LATE_SCALE = !AFFINE && NO_RELU && NPROD != 1;
-    F4 d[4];
     if (AFFINE) {
         const F4 al = *reinterpret_cast<const F4*>(ta), be = *reinterpret_cast<const F4*>(ta + cp32);
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
+        for (int q = 0; q < kW1Pix; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float v = __builtin_fmaxf(__builtin_fmaf(b[q].v[e], al.v[e], be.v[e]), relu_floor);
@@ -108,31 +172,46 @@ __device__ __forceinline__ void w1_put_item(const F4 (&b)[4], const bool (&pad)[
             }
     } else {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
+        for (int q = 0; q < kW1Pix; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) d[q].v[e] = LATE_SCALE ? b[q].v[e] : (NO_RELU ? b[q].v[e] * scale : __builtin_fmaxf(b[q].v[e] * scale, relu_floor));
     }
+    __builtin_amdgcn_sched_barrier(0);                               // the values are complete before the caller's next fetch reuses b's registers
+}
+
+template <int NPROD, bool AFFINE, bool NO_RELU, int POSB, int PLANE_V>
+__device__ __forceinline__ void w1_item_store(const F4 (&d)[kW1Pix], const float scale, unsigned char* dst) {
+    struct alignas(8) U2 { unsigned x, y; };
+    constexpr bool LATE_SCALE = !AFFINE && NO_RELU && NPROD != 1;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        float v[4];
+    for (int k = 0; k < 2; ++k) {                                    // pair 2g + k: pixels 2k .. 2k + 3
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d0 = d[0].v[e], d1 = d[1].v[e], d2 = d[2].v[e], d3 = d[3].v[e];
-            v[e] = p == 0 ? d0 - d2 : (p == 1 ? d1 + d2 : (p == 2 ? d2 - d1 : d1 - d3));
+        for (int p = 0; p < 4; ++p) {
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d0 = d[2 * k].v[e], d1 = d[2 * k + 1].v[e], d2 = d[2 * k + 2].v[e], d3 = d[2 * k + 3].v[e];
+                v[e] = p == 0 ? d0 - d2 : (p == 1 ? d1 + d2 : (p == 2 ? d2 - d1 : d1 - d3));
+            }
+            unsigned char* const at = dst + k * 16 + p * POSB;
+            if (NPROD == 1) {
+                U2 h;
+                h.x = TSNET_CVT_PK_BF16(v[0], v[1]);
+                h.y = TSNET_CVT_PK_BF16(v[2], v[3]);
+                *reinterpret_cast<U2*>(at) = h;
+            } else {
+                U2 h, l;
+                if (LATE_SCALE) TSNET_SPLIT_2PAIRS_SCALED(v[0], v[1], v[2], v[3], scale, h.x, l.x, h.y, l.y);
+                else TSNET_SPLIT_2PAIRS(v[0], v[1], v[2], v[3], h.x, l.x, h.y, l.y);
+                *reinterpret_cast<U2*>(at) = h;
+                *reinterpret_cast<U2*>(at + PLANE_V) = l;
+            }
         }
-        if (NPROD == 1) {
-            U2 h;
-            h.x = TSNET_CVT_PK_BF16(v[0], v[1]);
-            h.y = TSNET_CVT_PK_BF16(v[2], v[3]);
-            *reinterpret_cast<U2*>(dst + p * POSB) = h;
-        } else {
-            U2 h, l;
-            if (LATE_SCALE) TSNET_SPLIT_2PAIRS_SCALED(v[0], v[1], v[2], v[3], scale, h.x, l.x, h.y, l.y);
-            else TSNET_SPLIT_2PAIRS(v[0], v[1], v[2], v[3], h.x, l.x, h.y, l.y);
-            *reinterpret_cast<U2*>(dst + p * POSB) = h;
-            *reinterpret_cast<U2*>(dst + p * POSB + PLANE_V) = l;
-        }
+        // one pair at a time: left to interleave the eight positions of both pairs, the scheduler holds their 32 differences and 32 split halves at
+        // once beside the item in flight, and the kernel spills at its 128 VGPRs
+        if (k == 0) __builtin_amdgcn_sched_barrier(0);
     }
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // (2) Consumer: the MFMA products of one step (tap row, slab) on the wave's two 32-pair halves: lo * hi, hi * lo, hi * hi in this order into
@@ -203,9 +282,11 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
     constexpr bool NO_RELU = (OPT & 2) != 0;                          // a raw input without ReLU (the residual stream): no max in the producer
     constexpr int BD = 3;                                            // weight register sets: fragments BD - 1 steps ahead
     // one (slab, position, plane, octet) region: 6 rows x 16 pairs x 16 B, + 64 B so that the two octet regions a producer's 16-lane write
-    // group spans fall on different banks (and + 32 B per slab for the same reason)
+    // group spans fall on different banks, and + 16 B per slab for the same reason.  A group of a producer's ds_write_b64 = two lane groups g x the
+    // eight channel quads; in banks of 4 B, (a / 4) mod 32: the odd quad + 2, the slab + 4 (this pad), g + 8 (a lane's pairs are 32 B apart), the octet
+    // + 16 (the region pad) -- sixteen lanes x two banks, all distinct.  (+ 32 B, right while a lane owned one pair, now puts the slab on g's banks.)
     constexpr int REG = kW1Reg;
-    constexpr int PLANE_V = 2 * REG, POSB = NPL * PLANE_V, SLABB = 4 * POSB + 32, STAGE = 2 * SLABB;
+    constexpr int PLANE_V = 2 * REG, POSB = NPL * PLANE_V, SLABB = 4 * POSB + 16, STAGE = 2 * SLABB;
     static_assert(STAGE == kW1Stage(NPL), "stage size");
     static_assert(NPL == 1 || STAGE >= 4 * 32 * 64 * 4 + 4096, "a stage holds half the output exchange and the epilogue's reductions (one plane: chunks of one tile only)");
     constexpr int OFF_END = 3 * STAGE, OFF_EX_END = 4 * 64 * 64 * 4 + 2048;
@@ -340,134 +421,108 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
 
     if (wave >= 8) {
         // ================= producers (waves 8..13): V of period pp + 2 while the consumers run period pp =================
-        // A period's V has 6 rows x 16 pairs x 8 channel quads (32 channels) = 12 wave-sized items (row, half of the pairs); producer w owns
-        // items NIT w .. NIT w + NIT - 1 (NIT = 2).  lane -> (pair (lane >> 3) of the half, quad lane & 7): the 8 lanes of a pixel read its 32 channels as ONE
-        // 128-byte line -- a wave's load touches 8 lines, all of them whole (a lane per (pixel, octet) touches 32+ lines for the same bytes, and
-        // the texture path, shared with the consumers' weight fragments, was what bound the first forms of this kernel).  Per item: the four
-        // input pixels of the pair (columns ox0 - 1 + 2 pair + q of input row oy0 - 1 + row; reflection / zero padding in the offsets), fetched
-        // one item ahead; IN + ReLU; per position: one add, the split, one ds_write_b64 per plane.  Periods past the tile's last one are the
-        // first periods of the chunk's next tile (`nxt`); behind the last tile of the chunk nothing is produced.
-        constexpr int NIT = 12 / kW1Prod;                            // items per producer and period
-        static_assert(NIT * kW1Prod == 12 && (NIT & 1) == 0, "an even number of items per producer (the fetch buffers alternate)");
-        const int pw = wave - 8, quad = lane & 7;
-        const int psl = quad >> 2, poct = (quad >> 1) & 1, psub = quad & 1;
-        struct Offs { unsigned vP[NIT][4]; };                       // byte offset of (pixel, channel quad), or kOOB for a padded pixel
-        int ldst[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int item = NIT * pw + it;
-            ldst[it] = psl * SLABB + poct * REG + ((item >> 1) * 16 + (item & 1) * 8 + (lane >> 3)) * 16 + psub * 8;
-        }
+        // A period's V has 6 rows x 16 pairs x 8 channel quads (32 channels) = 6 wave-sized items (one input row each, w1_item_* above); producer w
+        // owns row w.  Per item: the six input pixels of the lane's two pairs, fetched one item ahead (reflection / zero padding in the offsets);
+        // IN + ReLU once per pixel; per pair and position one add, the split, one ds_write_b64 per plane.  Periods past the tile's last one are
+        // the first periods of the chunk's next tile (`nxt`); behind the last tile of the chunk nothing is produced.
+        static_assert(kW1Prod == 6, "one item (input row) per producer and period");
+        const int pw = wave - 8, quad = lane & 7, pg = lane >> 3;
+        using Offs = W1ItemOffs;
+        const int ldst = w1_item_dst<SLABB>(pw, pg, quad);
         auto offsets = [&](const W1Tile& t, const bool real, Offs& o) __attribute__((always_inline)) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int item = NIT * pw + it, prow = item >> 1, ppair = (item & 1) * 8 + (lane >> 3);
-                int iy = t.oy0 - 1 + prow;
-                bool rok = real;
-                if (a.reflect) {
-                    iy = iy < 0 ? -iy : iy;
-                    iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-                } else {
-                    rok = rok && iy >= 0 && iy < a.H;
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    int ix = t.ox0 - 1 + 2 * ppair + q;
-                    bool ok = rok;
-                    if (a.reflect) {
-                        ix = ix < 0 ? -ix : ix;
-                        ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
-                    } else {
-                        ok = ok && ix >= 0 && ix < a.W;
-                    }
-                    o.vP[it][q] = ok ? (unsigned)(((t.img * a.H * a.W + iy * a.W + ix) * a.Cin + quad * 4) * 4) : kOOB;
-                }
-            }
+            w1_item_offsets(a, t.img, t.oy0, t.ox0, pw, pg, quad, real, o);
         };
         Offs cur, nxt;
         W1Tile Tn = T;
         bool has_next = nrun > 1;
         offsets(T, true, cur);
         offsets(T, false, nxt);                                      // (nothing behind this tile yet: zeros)
-        // the offsets of a tile's LAST period: with an odd slab count its second slab lies past Cin -- those lanes read zeros, like the weights
-        // of that slab (the transform table holds zeros there too)
-        unsigned curT[NIT][4];
-        auto tail_of = [&](const Offs& o) __attribute__((always_inline)) {
-            const bool cok = (npp - 1) * 32 + quad * 4 < a.Cin;
-#pragma unroll
-            for (int it = 0; it < NIT; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) curT[it][q] = cok ? o.vP[it][q] : kOOB;
-        };
-        tail_of(cur);
+        // a tile's LAST period: with an odd slab count its second slab lies past Cin -- those lanes read zeros, like the weights of that slab (the
+        // transform table holds zeros there too).  Masked where that one item is fetched: three selects per tile, no second table of offsets held
+        const bool tail_ok = (npp - 1) * 32 + quad * 4 < a.Cin;
         const float* tab_cur = tab0;
         const float* tab_nxt = tab0;
         const float relu_floor = a.in_relu ? 0.f : -__builtin_inff();
-        F4 sx[2][4];                                                 // two items in turn: four pixels x four channels each
+        const unsigned pitch = (unsigned)(a.Cin * 4);                // bytes between two pixels of a row
+        // sx: the item in flight (six pixels x four channels as fetched); sd: the item being written (the same after IN + ReLU / the scale).  The
+        // values pass from sx to sd BEFORE the next fetch is issued into sx, so the roles never alternate and the period loop needs no unrolling.
+        F4 sx[kW1Pix], sd[kW1Pix];
         // Which tile an item belongs to is decided where the loop is written, not per load: the period loop below is split at the tile
         // boundary (every select, compare and branch in here is an issue slot taken from the MFMA waves of the same SIMD; the first form
         // spent 71 scalar instructions and 27 s_nop per two items).  SRC: 0 = the current tile, 1 = its last period, 2 = the next tile.
         using SrcCur = std::integral_constant<int, 0>;
         using SrcTail = std::integral_constant<int, 1>;
         using SrcNxt = std::integral_constant<int, 2>;
-        auto v_fetch = [&](auto SRC, int pe, int it, F4 (&b)[4]) __attribute__((always_inline)) {
+        auto v_fetch = [&](auto SRC, int pe, F4 (&b)[kW1Pix]) __attribute__((always_inline)) {
             constexpr int src = decltype(SRC)::value;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                b[q] = TSNET_BUF_LOAD16(rsx, src == 2 ? nxt.vP[it][q] : (src == 1 ? curT[it][q] : cur.vP[it][q]), (unsigned)(pe * 128));
+            const unsigned soff = (unsigned)(pe * 128);
+            if (src == 1) w1_item_fetch(rsx, w1_item_masked(cur, tail_ok), soff, pitch, b);
+            else w1_item_fetch(rsx, src == 2 ? nxt : cur, soff, pitch, b);
         };
-        auto v_put = [&](auto SRC, int pe, int it, int st, const F4 (&b)[4]) __attribute__((always_inline)) {   // transform + split + store of a fetched item into the stage at st
+        auto v_vals = [&](auto SRC, int pe, const F4 (&b)[kW1Pix]) __attribute__((always_inline)) {   // IN + ReLU / scale of a fetched item: b -> sd
             constexpr bool nx = decltype(SRC)::value == 2;
             const int c0 = pe * 32 + quad * 4;
-            bool pad[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) pad[q] = ZPAD_KEEP && (nx ? nxt.vP[it][q] : cur.vP[it][q]) == kOOB;
-            w1_put_item<NPROD, AFFINE, ZPAD_KEEP, NO_RELU, POSB, PLANE_V>(b, pad, (nx ? tab_nxt : tab_cur) + c0, cp32, nx ? Tn.in_scale : T.in_scale, relu_floor,
-                                                                        smem_raw + st + ldst[it]);
+            bool pad[kW1Pix] = {};
+            if (ZPAD_KEEP) w1_item_pads(nx ? nxt : cur, pad);
+            w1_item_values<NPROD, AFFINE, ZPAD_KEEP, NO_RELU>(b, pad, (nx ? tab_nxt : tab_cur) + c0, cp32, nx ? Tn.in_scale : T.in_scale, relu_floor, sd);
         };
-        // an item by its period pq counted from the current tile (pq >= npp: the next tile's), the source picked by branches: the prologue
-        // and tiles of fewer than five periods (the hot layers have 16 and 32)
-        auto fetch_any = [&](int pq, int it, F4 (&b)[4]) __attribute__((always_inline)) {
-            if (pq >= npp) v_fetch(SrcNxt{}, pq - npp, it, b);
-            else if (pq == npp - 1) v_fetch(SrcTail{}, pq, it, b);
-            else v_fetch(SrcCur{}, pq, it, b);
+        auto v_store = [&](auto SRC, int st) __attribute__((always_inline)) {   // transform + split + store of sd into the stage at st
+            constexpr bool nx = decltype(SRC)::value == 2;
+            w1_item_store<NPROD, AFFINE, NO_RELU, POSB, PLANE_V>(sd, nx ? Tn.in_scale : T.in_scale, smem_raw + st + ldst);
         };
-        auto put_any = [&](int pq, int it, int st, const F4 (&b)[4]) __attribute__((always_inline)) {
-            if (pq >= npp) v_put(SrcNxt{}, pq - npp, it, st, b);
-            else v_put(SrcCur{}, pq, it, st, b);
+        // an item by its period pq counted from the current tile (pq >= npp: the next tile's), the source picked by SELECTS at run time, one copy
+        // of the code: the prologue and tiles of fewer than five periods (the hot layers have 16 and 32)
+        auto offs_any = [&](int pq) __attribute__((always_inline)) {
+            const bool nx = pq >= npp;
+            W1ItemOffs o;
+            o.first = nx ? nxt.first : cur.first; o.mid = nx ? nxt.mid : cur.mid; o.last = nx ? nxt.last : cur.last;
+            return o;
         };
-        // the item stream (period, item): each item is fetched while its predecessor is transformed; two buffers in turn.  The chunk's
-        // prologue -- V(0), V(1) of its first tile, the only ones the consumers wait for -- fetches its four items at once (one exposed
-        // memory latency instead of two).
-        static_assert(NIT == 2, "the prologue and the period loop are written for two items per producer");
+        auto fetch_any = [&](int pq, F4 (&b)[kW1Pix]) __attribute__((always_inline)) {
+            const bool nx = pq >= npp;
+            w1_item_fetch(rsx, w1_item_masked(offs_any(pq), pq != npp - 1 || tail_ok), (unsigned)((nx ? pq - npp : pq) * 128), pitch, b);
+        };
+        auto vals_any = [&](int pq, const F4 (&b)[kW1Pix]) __attribute__((always_inline)) {
+            const bool nx = pq >= npp;
+            const int c0 = (nx ? pq - npp : pq) * 32 + quad * 4;
+            bool pad[kW1Pix] = {};
+            if (ZPAD_KEEP) w1_item_pads(offs_any(pq), pad);
+            w1_item_values<NPROD, AFFINE, ZPAD_KEEP, NO_RELU>(b, pad, (nx ? tab_nxt : tab_cur) + c0, cp32, nx ? Tn.in_scale : T.in_scale, relu_floor, sd);
+        };
+        auto store_any = [&](int pq, int st) __attribute__((always_inline)) {
+            w1_item_store<NPROD, AFFINE, NO_RELU, POSB, PLANE_V>(sd, pq >= npp ? Tn.in_scale : T.in_scale, smem_raw + st + ldst);
+        };
+        // the item stream, one item per period: each item is fetched while its predecessor is transformed.  The chunk's prologue -- V(0), V(1)
+        // of its first tile, the only ones the consumers wait for -- fetches its two items at once (one exposed memory latency instead of two).
         {
-            F4 sp[2][4];                                             // with sx: four buffers, the prologue's four items in flight at once
+            F4 sp[kW1Pix];                                           // with sx: the prologue's two items in flight at once
             TabRegs tr{};
             if (AFFINE) tr = tab_request(T);
-            fetch_any(0, 0, sx[0]); fetch_any(0, 1, sx[1]); fetch_any(1, 0, sp[0]); fetch_any(1, 1, sp[1]);
+            fetch_any(0, sx); fetch_any(1, sp);
             if (AFFINE) {
                 tab_store(tab0, T, tr);
                 __syncthreads();                                     // the first tile's table (the consumers fill their share)
             }
             if (has_next) { Tn = tile_at(1); offsets(Tn, true, nxt); }
-            put_any(0, 0, 0, sx[0]);
-            fetch_any(2, 0, sx[0]);                                  // item 0 of period 2 stays in flight in buffer 0
-            put_any(0, 1, 0, sx[1]);
-            if (1 < npp || has_next) { put_any(1, 0, STAGE, sp[0]); put_any(1, 1, STAGE, sp[1]); }
+            vals_any(0, sx);
+            store_any(0, 0);
+            const bool put1 = 1 < npp || has_next;
+            if (put1) vals_any(1, sp);
+            fetch_any(2, sx);                                        // the item of period 2 stays in flight (requested once sp's values have left it:
+            if (put1) store_any(1, STAGE);                           // never three items of registers at once)
         }
         TSNET_W1_STAMP(1);
         __syncthreads();                                             // (the consumers' prologue barrier)
         TSNET_W1_STAMP(2);
         int st_wr = 2 * STAGE;
-        // consumer period pp: item (pp + 2, 1) fetched, (pp + 2, 0) written, (pp + 3, 0) fetched, (pp + 2, 1) written.  L1 / L2: where the
-        // two fetched items live; PUT: where the written period lives; pe*: their period numbers inside their own tile
-        auto iter = [&](auto L1, auto L2, auto PUT, int pe1, int pe2, int pep, bool put_ok) __attribute__((always_inline)) {
+        // consumer period pp: the item of period pp + 2 leaves sx, the item of period pp + 3 is fetched, the item of period pp + 2 is written.
+        // LD: where the fetched item lives; PUT: where the written period lives; pe*: their period numbers inside their own tile
+        auto iter = [&](auto LD, auto PUT, int pel, int pep, bool put_ok) __attribute__((always_inline)) {
             if (!(OPT & 128)) TSNET_W1_LOOP_BARRIER(bar_wait);       // every read of the stage produced next has been issued
             if (!(OPT & 16)) {
-                v_fetch(L1, pe1, 1, sx[1]);
-                if (put_ok) v_put(PUT, pep, 0, st_wr, sx[0]);
-                v_fetch(L2, pe2, 0, sx[0]);
-                if (put_ok) v_put(PUT, pep, 1, st_wr, sx[1]);
+                if (put_ok) v_vals(PUT, pep, sx);
+                v_fetch(LD, pel, sx);
+                if (put_ok) v_store(PUT, st_wr);
             }
             st_wr = st_wr == 2 * STAGE ? 0 : st_wr + STAGE;
         };
@@ -480,19 +535,19 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
                 tab_nxt = tb;
             }
             if (npp >= 5) {
-                for (int pp = 0; pp < npp - 4; ++pp) iter(SrcCur{}, SrcCur{}, SrcCur{}, pp + 2, pp + 3, pp + 2, true);
-                iter(SrcCur{}, SrcTail{}, SrcCur{}, npp - 2, npp - 1, npp - 2, true);
-                iter(SrcTail{}, SrcNxt{}, SrcCur{}, npp - 1, 0, npp - 1, true);
-                iter(SrcNxt{}, SrcNxt{}, SrcNxt{}, 0, 1, 0, has_next);
-                iter(SrcNxt{}, SrcNxt{}, SrcNxt{}, 1, 2, 1, has_next);
+                for (int pp = 0; pp < npp - 4; ++pp) iter(SrcCur{}, SrcCur{}, pp + 3, pp + 2, true);
+                iter(SrcTail{}, SrcCur{}, npp - 1, npp - 2, true);
+                iter(SrcNxt{}, SrcCur{}, 0, npp - 1, true);
+                iter(SrcNxt{}, SrcNxt{}, 1, 0, has_next);
+                iter(SrcNxt{}, SrcNxt{}, 2, 1, has_next);
             } else {
                 for (int pp = 0; pp < npp; ++pp) {
                     if (!(OPT & 128)) TSNET_W1_LOOP_BARRIER(bar_wait);
                     if (!(OPT & 16)) {
-                        fetch_any(pp + 2, 1, sx[1]);
-                        if (pp + 2 < npp || has_next) put_any(pp + 2, 0, st_wr, sx[0]);
-                        fetch_any(pp + 3, 0, sx[0]);
-                        if (pp + 2 < npp || has_next) put_any(pp + 2, 1, st_wr, sx[1]);
+                        const bool put_ok = pp + 2 < npp || has_next;
+                        if (put_ok) vals_any(pp + 2, sx);
+                        fetch_any(pp + 3, sx);
+                        if (put_ok) store_any(pp + 2, st_wr);
                     }
                     st_wr = st_wr == 2 * STAGE ? 0 : st_wr + STAGE;
                 }
@@ -503,7 +558,6 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
             if (j < 3) TSNET_W1_STAMP(5 + 3 * j);
             // on to the next tile: its offsets become the current ones
             T = Tn; cur = nxt; tab_cur = tab_nxt;
-            tail_of(cur);
             has_next = j + 2 < nrun;
             if (has_next) Tn = tile_at(j + 2);
             offsets(Tn, has_next, nxt);

@@ -19,9 +19,9 @@ __device__ __forceinline__ void w1_tile_one(const ConvArgs& a, unsigned char* sm
     constexpr bool NO_RELU = (OPT & 2) != 0;                          // a raw input without ReLU (the residual stream): no max in the producer
     constexpr int BD = 3;                                            // weight register sets: fragments BD - 1 steps ahead
     // one (slab, position, plane, octet) region: 6 rows x 16 pairs x 16 B, + 64 B so that the two octet regions a producer's 16-lane write
-    // group spans fall on different banks (and + 32 B per slab for the same reason)
+    // group spans fall on different banks (and + 16 B per slab for the same reason: conv_w1.hpp)
     constexpr int REG = kW1Reg;
-    constexpr int PLANE_V = 2 * REG, POSB = NPL * PLANE_V, SLABB = 4 * POSB + 32, STAGE = 2 * SLABB;
+    constexpr int PLANE_V = 2 * REG, POSB = NPL * PLANE_V, SLABB = 4 * POSB + 16, STAGE = 2 * SLABB;
     static_assert(STAGE == kW1Stage(NPL), "stage size");
     constexpr int OFF_END = 3 * STAGE, OFF_EX_END = 4 * 64 * 64 * 4 + 2048;
     constexpr int OFF_TAB = OFF_END > OFF_EX_END ? OFF_END : OFF_EX_END;
@@ -68,75 +68,48 @@ __device__ __forceinline__ void w1_tile_one(const ConvArgs& a, unsigned char* sm
 
     if (wave >= 8) {
         // ================= producers (waves 8..13): V of period pp + 2 while the consumers run period pp =================
-        // A period's V has 6 rows x 16 pairs x 8 channel quads (32 channels) = 12 wave-sized items (row, half of the pairs); producer w owns
-        // items NIT w .. NIT w + NIT - 1 (NIT = 2).  lane -> (pair (lane >> 3) of the half, quad lane & 7): the 8 lanes of a pixel read its 32 channels as ONE
-        // 128-byte line -- a wave's load touches 8 lines, all of them whole (a lane per (pixel, octet) touches 32+ lines for the same bytes, and
-        // the texture path, shared with the consumers' weight fragments, was what bound the first forms of this kernel).  Per item: the four
-        // input pixels of the pair (columns ox0 - 1 + 2 pair + q of input row oy0 - 1 + row; reflection / zero padding in the offsets), fetched
-        // one item ahead; IN + ReLU; per position: one add, the split, one ds_write_b64 per plane.
-        constexpr int NIT = 12 / kW1Prod;                            // items per producer and period
-        static_assert(NIT * kW1Prod == 12 && (NIT & 1) == 0, "an even number of items per producer (the fetch buffers alternate)");
-        const int pw = wave - 8, quad = lane & 7;
-        const int psl = quad >> 2, poct = (quad >> 1) & 1, psub = quad & 1;
-        unsigned vP[NIT][4];
-        int ldst[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int item = NIT * pw + it, prow = item >> 1, ppair = (item & 1) * 8 + (lane >> 3);
-            int iy = oy0 - 1 + prow;
-            bool rok = true;
-            if (a.reflect) {
-                iy = iy < 0 ? -iy : iy;
-                iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-            } else {
-                rok = iy >= 0 && iy < a.H;
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                int ix = ox0 - 1 + 2 * ppair + q;
-                bool ok = rok;
-                if (a.reflect) {
-                    ix = ix < 0 ? -ix : ix;
-                    ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
-                } else {
-                    ok = ok && ix >= 0 && ix < a.W;
-                }
-                vP[it][q] = ok ? (unsigned)(((img * a.H * a.W + iy * a.W + ix) * a.Cin + quad * 4) * 4) : kOOB;
-            }
-            ldst[it] = psl * SLABB + poct * REG + (prow * 16 + ppair) * 16 + psub * 8;
-        }
+        // A period's V has 6 rows x 16 pairs x 8 channel quads (32 channels) = 6 wave-sized items, one input row each; producer w owns row w.
+        // lane -> (pairs 2g and 2g + 1, g = lane >> 3; quad lane & 7): six pixels per lane, the two that the pairs share fetched once -- the item
+        // code (offsets, fetch, IN + ReLU once per pixel, transform + split + store) is conv_w1.hpp's w1_item_*, shared with the chunk path.
+        static_assert(kW1Prod == 6, "one item (input row) per producer and period");
+        const int pw = wave - 8, quad = lane & 7, pg = lane >> 3;
+        W1ItemOffs vP;
+        w1_item_offsets(a, img, oy0, ox0, pw, pg, quad, true, vP);
+        const int ldst = w1_item_dst<SLABB>(pw, pg, quad);
+        bool pad[kW1Pix] = {};
+        if (ZPAD_KEEP) w1_item_pads(vP, pad);
+        const unsigned pitch = (unsigned)(a.Cin * 4);                // bytes between two pixels of a row
         const float relu_floor = a.in_relu ? 0.f : -__builtin_inff();
-        F4 sx[2][4];                                                 // two items in turn: four pixels x four channels each
-        auto v_load = [&](int pq, int it, int buf) __attribute__((always_inline)) {   // period pq; channels past Cin (the second slab of an odd count) read zeros, like the weights of that slab
-            const bool cok = pq * 32 + quad * 4 < a.Cin;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sx[buf][q] = TSNET_BUF_LOAD16(rsx, cok ? vP[it][q] : kOOB, (unsigned)(pq * 128));
+        F4 sx[kW1Pix], sd[kW1Pix];                                   // the item in flight as fetched; the item being written, after IN + ReLU / the scale
+        auto v_load = [&](int pq, F4 (&b)[kW1Pix]) __attribute__((always_inline)) {   // period pq; channels past Cin (the second slab of an odd count) read zeros, like the weights of that slab
+            w1_item_fetch(rsx, w1_item_masked(vP, pq * 32 + quad * 4 < a.Cin), (unsigned)(pq * 128), pitch, b);
         };
-        auto v_item = [&](int pq, int it, int st, int buf) __attribute__((always_inline)) {   // transform + split + store of a fetched item into the stage at st
+        auto v_vals = [&](int pq, const F4 (&b)[kW1Pix]) __attribute__((always_inline)) {   // b -> sd
             const int c0 = pq * 32 + quad * 4;
-            bool pad[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) pad[q] = ZPAD_KEEP && vP[it][q] == kOOB;
-            w1_put_item<NPROD, AFFINE, ZPAD_KEEP, NO_RELU, POSB, PLANE_V>(sx[buf], pad, tab + (c0 < cp32 ? c0 : 0) /* (periods past the tile: never read) */, cp32, in_scale,
-                                                                        relu_floor, smem_raw + st + ldst[it]);
+            w1_item_values<NPROD, AFFINE, ZPAD_KEEP, NO_RELU>(b, pad, tab + (c0 < cp32 ? c0 : 0) /* (periods past the tile: never read) */, cp32, in_scale, relu_floor, sd);
         };
-        // the item stream (period, item): each item is fetched while its predecessor is transformed; two buffers in turn
-        v_load(0, 0, 0);
-#pragma unroll
-        for (int u = 0; u < 2 * NIT; ++u) {                          // V(0), V(1); item 0 of period 2 left in flight in buffer 0
-            v_load((u + 1) / NIT, (u + 1) % NIT, (u + 1) & 1);
-            v_item(u / NIT, u % NIT, (u / NIT) * STAGE, u & 1);
+        auto v_store = [&](int st) __attribute__((always_inline)) {   // transform + split + store of sd into the stage at st
+            w1_item_store<NPROD, AFFINE, NO_RELU, POSB, PLANE_V>(sd, in_scale, smem_raw + st + ldst);
+        };
+        // the item stream, one item per period: each item is fetched while its predecessor is transformed; V(0) and V(1), the only ones the
+        // consumers wait for, are requested together
+        {
+            F4 sp[kW1Pix];
+            v_load(0, sx); v_load(1, sp);
+            v_vals(0, sx);
+            v_load(2, sx);                                           // the item of period 2 left in flight
+            v_store(0);
+            v_vals(1, sp);
+            v_store(STAGE);
         }
         __syncthreads();                                             // (the consumers' prologue barrier)
         int st_wr = 2 * STAGE;
         for (int pp = 0; pp < npp; ++pp) {
             if (!(OPT & 128)) __syncthreads();                       // every read of the stage produced next has been issued
             if (!(OPT & 16)) {
-#pragma unroll
-                for (int it = 0; it < NIT; ++it) {
-                    v_load(it == NIT - 1 ? pp + 3 : pp + 2, it == NIT - 1 ? 0 : it + 1, (it & 1) ^ 1);
-                    v_item(pp + 2, it, st_wr, it & 1);
-                }
+                v_vals(pp + 2, sx);
+                v_load(pp + 3, sx);
+                v_store(st_wr);
             }
             st_wr = st_wr == 2 * STAGE ? 0 : st_wr + STAGE;
         }
