@@ -6,8 +6,11 @@
                         loop over the same B frames; one JSON line with the per-round figures, their medians and the spread of (a)
     --bank [--lib2 SO [--lib2-first]] [--rounds R]
                         the source bank (tsnet_bank_put / tsnet_forward_bank), one process, interleaved rounds, one JSON line:
-                        (1) with --lib2 (another build of the same ABI, e.g. the parent commit's): the one-shot forward and the shared cache's
-                            forward_target at B = 4 on both libraries, with each library's own spread over the rounds;
+                        (1) with --lib2 (another build of the same ABI, e.g. the parent commit's): the one-shot forward, forward_target on the
+                            per-batch and on the shared cache and forward_bank (frame b on source set b) on both libraries, with each library's
+                            own spread over the rounds; every case must give equal bits on the two ("lib2_bit_identical");
+                            [--size N] [--sources K] [--operands MODE]: another frame size, source count, operand mode (BASELINE.json configs[4]:
+                            --batch 1 --size 512 --sources 5 --operands bf16, the shape that runs flow_kernel_p);
                         (2) forward_bank with the identity table against forward_target on the shared cache;
                         (3) bank_put of ONE slot against a full set_sources (K = 3 images), and four source sets x one driving frame as one
                             forward_bank(B = 4) against four forward_bank(B = 1) calls
@@ -25,6 +28,8 @@ B, H, W = 4, 256, 256
 NB = int(sys.argv[sys.argv.index("--n-blocks") + 1]) if "--n-blocks" in sys.argv else 0
 if "--batch" in sys.argv:
     B = int(sys.argv[sys.argv.index("--batch") + 1])
+if "--size" in sys.argv:
+    H = W = int(sys.argv[sys.argv.index("--size") + 1])
 
 
 def bank_bench():
@@ -32,10 +37,11 @@ def bank_bench():
     from wacv23_tsnet_amd import _lib
     rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5
     lib2 = sys.argv[sys.argv.index("--lib2") + 1] if "--lib2" in sys.argv else None
-    K = 3
+    K = int(sys.argv[sys.argv.index("--sources") + 1]) if "--sources" in sys.argv else 3
+    operands = sys.argv[sys.argv.index("--operands") + 1] if "--operands" in sys.argv else "fp32"
 
     def engine(lib=None):
-        e = TSNetEngine(label_nc=2, n_blocks=NB, n_downsampling=3, n_source=K, height=H, width=W, max_batch=B, lib=lib)
+        e = TSNetEngine(label_nc=2, n_blocks=NB, n_downsampling=3, n_source=K, height=H, width=W, max_batch=B, operands=operands, lib=lib)
         e.load_state_dict(synth.state_dict(e.param_shapes(), seed=0)); e.finalize("cuda")
         return e
 
@@ -55,31 +61,41 @@ def bank_bench():
         """{name: [ms per round]} -> {name: {median, spread (max - min over the rounds)}}"""
         return {k: {"median_ms": round(statistics.median(v), 4), "spread_ms": round(max(v) - min(v), 4), "per_round_ms": [round(x, 4) for x in v]} for k, v in runs.items()}
 
-    out = {"batch": B, "n_blocks": NB, "rounds": rounds, "lib2_first": "--lib2-first" in sys.argv}
+    out = {"batch": B, "n_blocks": NB, "size": H, "sources": K, "operands": operands, "rounds": rounds, "lib2_first": "--lib2-first" in sys.argv}
+    ident = [list(range(K))] * B
+    mixed = [[K * b + s for s in range(K)] for b in range(B)]                                   # frame b on source set b
     eng = engine()
     # (1) legacy paths, this library against --lib2
     if lib2:
         engs = {"this": eng, "lib2": engine(_lib.bind(ctypes.CDLL(lib2)))}
         if "--lib2-first" in sys.argv:                       # which library goes first in a round: an order effect shows as a sign change
             engs = dict(reversed(list(engs.items())))
-        runs = {f"{w} {k}": [] for w in ("forward", "shared forward_target") for k in engs}
+        def put_all(e):
+            for b in range(B):
+                e.bank_put(K * b, *sets[b])
+        cases = {"forward": (lambda e: None, lambda e: e.forward(si, sl, sb, tl, tb)),
+                 "per-batch forward_target": (lambda e: e.set_sources(si, sl, sb), lambda e: e.forward_target(tl, tb)),
+                 "shared forward_target": (lambda e: e.set_sources(*sets[0], shared=True), lambda e: e.forward_target(tl, tb)),
+                 "forward_bank": (put_all, lambda e: e.forward_bank(mixed, tl, tb))}
+        runs = {f"{w} {k}": [] for w in cases for k in engs}
+        same2 = True
         for r in range(rounds + 1):
-            for k, e in engs.items():
-                t = ms(lambda: e.forward(si, sl, sb, tl, tb))
-                if r: runs[f"forward {k}"].append(t)
-            for k, e in engs.items():
-                e.set_sources(*sets[0], shared=True)
-                t = ms(lambda: e.forward_target(tl, tb))
-                if r: runs[f"shared forward_target {k}"].append(t)
+            for w, (prep, step) in cases.items():
+                res = {}
+                for k, e in engs.items():
+                    prep(e)
+                    t = ms(lambda: step(e))
+                    if r: runs[f"{w} {k}"].append(t)
+                    res[k] = step(e)[0].clone()
+                same2 = same2 and bool(torch.equal(res["this"], res["lib2"]))
         out["legacy_this_vs_lib2"] = table(runs)
-        for w in ("forward", "shared forward_target"):
+        out["lib2_bit_identical"] = same2
+        for w in cases:
             a, b = out["legacy_this_vs_lib2"][f"{w} this"], out["legacy_this_vs_lib2"][f"{w} lib2"]
             out["legacy_this_vs_lib2"][f"{w}: this - lib2, % of lib2"] = round((a["median_ms"] - b["median_ms"]) / b["median_ms"] * 100, 3)
             out["legacy_this_vs_lib2"][f"{w}: lib2 spread, % of its median"] = round(b["spread_ms"] / b["median_ms"] * 100, 3)
         engs["lib2"].close()
     # (2) identity table against the shared cache, (3) the use cases
-    ident = [list(range(K))] * B
-    mixed = [[K * b + s for s in range(K)] for b in range(B)]                                   # frame b on source set b
     runs = {n: [] for n in ("shared forward_target", "forward_bank identity", "set_sources shared (K images)", "bank_put one slot",
                             "forward_bank B=4, 4 source sets", "4 x forward_bank B=1")}
     same = True

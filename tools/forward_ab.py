@@ -2,7 +2,9 @@
 Interleaved rounds, medians.  knob 0 = largest conv_w1 chunk the launcher may choose (3 = product behaviour, 1 = one tile per workgroup).
     python tools/forward_ab.py [--batch 4] [--n-blocks 0] [--rounds 7] [--iters 20] [--knob 0] [--values 3,1]
 --lib2 PATH: A/B of two BUILDS instead (this tree's tools library against another .so of the same ABI, e.g. the previous commit's, built
-into wacv23_tsnet_amd/lib/libtsnet_tools_prev.so): one engine per library, interleaved rounds in one process on one box."""
+into wacv23_tsnet_amd/lib/libtsnet_tools_prev.so): one engine per library, interleaved rounds in one process on one box.
+--lib PATH (with --lib2): the library that stands for this tree, e.g. the product build wacv23_tsnet_amd/lib/libtsnet_hip.so when --lib2 is
+a product build too -- the tools build carries more instantiations and is not the same binary."""
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,6 +20,7 @@ ap.add_argument("--knob", type=int, default=0)
 ap.add_argument("--values", default="3,1")
 ap.add_argument("--operands", default="fp32", help="fp32 | bf16 | bf16s | fp16 (tsnet_cfg.operand_mode)")
 ap.add_argument("--lib2", default=None)
+ap.add_argument("--lib", default=None, help="this tree's library in a --lib2 comparison (default: the tools build)")
 ap.add_argument("--reps", type=int, default=6, help="engine instantiations per build (--lib2)")
 a = ap.parse_args()
 lib = _lib.load_tools()
@@ -47,7 +50,7 @@ if a.lib2:
     import ctypes
     lib2 = _lib.bind(ctypes.CDLL(a.lib2))
     names = ["this tree", os.path.basename(a.lib2)]
-    libs2 = {names[0]: lib, names[1]: lib2}
+    libs2 = {names[0]: _lib.bind(ctypes.CDLL(a.lib)) if a.lib else lib, names[1]: lib2}
     per = {k: [] for k in names}
     cls = {}
     for rep in range(a.reps):

@@ -325,11 +325,8 @@ void launch_finalize_impl(const double* part, float* alpha, float* beta, int N, 
     check_launch("in_finalize");
 }
 
-// y = x + add[n % add_nmod] with the InstanceNorm statistics of y -> (alpha, beta); `part` must hold N*64*C*2 doubles.  x_sb: source-batch
-// extent of x (AddStatsArgs; 0 = add_nmod: x holds N images)
-// slot (device, N ints; source bank): image n reads x[slot[n]] instead
-void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, float* y, int N, int HW, int C, double* part, float* alpha, float* beta, int x_sb = 0,
-                   const int* slot = nullptr) {
+// y[n] = x[slot[n]] + add[n % add_nmod] with the InstanceNorm statistics of y -> (alpha, beta); `part` must hold N*64*C*2 doubles; slot: device, N ints
+void run_add_stats(Ctx& ctx, const float* x, const int* slot, const float* add, int add_nmod, float* y, int N, int HW, int C, double* part, float* alpha, float* beta) {
     if (C & 3) throw ArgError("add_stats: C must be a multiple of 4");
     TimeScope ts(ctx, TSNET_T_STATS);
     const int cq = C / 4, cols = cq < 256 ? cq : 256, R = 256 / cols;
@@ -339,10 +336,8 @@ void run_add_stats(Ctx& ctx, const float* x, const float* add, int add_nmod, flo
     const int rps = (HW + S - 1) / S;
     S = (HW + rps - 1) / rps;
     const int nmod = add_nmod > 0 ? add_nmod : 1;
-    if (x_sb < 0 || x_sb > nmod || (x_sb && nmod % x_sb)) throw ArgError("add_stats: the source-batch extent must divide add_nmod");
-    AddStatsArgs sa{x, add, y, part, HW, C, S, rps, nmod, x_sb ? x_sb : nmod};
-    if (slot) hipLaunchKernelGGL(add_stats_slots_kernel, dim3(S, N, (cq + 255) / 256), dim3(256), 0, ctx.stream, AddStatsSlotArgs{sa, slot});
-    else hipLaunchKernelGGL(add_stats_partial_kernel, dim3(S, N, (cq + 255) / 256), dim3(256), 0, ctx.stream, sa);
+    AddStatsArgs sa{x, slot, add, y, part, HW, C, S, rps, nmod};
+    hipLaunchKernelGGL(add_stats_partial_kernel, dim3(S, N, (cq + 255) / 256), dim3(256), 0, ctx.stream, sa);
     check_launch("add_stats_partial");
     // (its finalize stays a launch: 64 splits x 1024 channels per image are a megabyte of partials -- one last-arriving workgroup per image
     // would read them at a single block's rate, in_finalize2 spreads them over 64 x N)
@@ -426,11 +421,10 @@ void run_l2norm_split(Ctx& ctx, const float* x, unsigned short* q, int N, int P,
 }
 
 // variant (tsnet_op_flow_k; the forward passes 0): 1 = flow_kernel whatever the plan says; 2 = flow_kernel_p without the exp pass (tools build)
-// slot (device, NB ints; source bank): the kernels' slot forms
-void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0, const int* slot = nullptr) {
+// slot (device, NB ints): the slot table, entry s*B + b the image of a.sq / a.src_bbox that (source s, driving frame b) reads
+void run_flow(Ctx& ctx, FlowArgs a, int NB, const int* slot, int variant = 0) {
     if (a.C & 7) throw ArgError("flow: C must be a multiple of 8");
-    if (a.SB == 0) a.SB = a.B;
-    if (a.SB < 1 || a.B % a.SB) throw ArgError("flow: the source-batch extent must divide the batch");
+    a.slot = slot;
     if (variant < 0 || variant > 2) throw ArgError("flow: variant 0, 1 or 2");
     TimeScope ts(ctx, TSNET_T_FLOW);
     const size_t budget = 160 * 1024;
@@ -439,7 +433,7 @@ void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0, const int* slot = n
     if (G) {
         a.K = NB / a.B; a.G = G; a.S = flowp_slices(a.h, a.w);
         try {
-            launch_flow_p(a, variant, ctx.stream, slot);
+            launch_flow_p(a, variant, ctx.stream);
         } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
         check_launch("flow_p");
         return;
@@ -449,16 +443,16 @@ void run_flow(Ctx& ctx, FlowArgs a, int NB, int variant = 0, const int* slot = n
     const size_t lds = flow_lds_bytes(NT, a.h, a.w, a.C);
     if (lds > budget) throw ArgError("flow: feature width / position count exceed the LDS budget");
     try {
-        launch_flow(a, NT, lds, (unsigned)(flow_ppad(a.P) / (32 * NT) * NB), ctx.stream, slot);
+        launch_flow(a, NT, lds, (unsigned)(flow_ppad(a.P) / (32 * NT) * NB), ctx.stream);
     } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     check_launch("flow");
 }
 
-void run_warp(Ctx& ctx, const float* src, const float* flow, float* out, int B, int K, int h, int w, int C, int SB = 0, const int* slot = nullptr) {
+// slot (device, K*B ints): the slot table, entry s*B + b the image of src that (source s, driving frame b) reads
+void run_warp(Ctx& ctx, const float* src, const int* slot, const float* flow, float* out, int B, int K, int h, int w, int C) {
     TimeScope ts(ctx, TSNET_T_WARP);
-    WarpArgs a{src, flow, out, B, K, h, w, C, SB > 0 ? SB : B};
-    if (slot) hipLaunchKernelGGL(warp_mean_slots_kernel, dim3(ew_grid((size_t)B * h * w * C / 4)), dim3(256), 0, ctx.stream, WarpSlotArgs{a, slot});
-    else hipLaunchKernelGGL(warp_mean_kernel, dim3(ew_grid((size_t)B * h * w * C / 4)), dim3(256), 0, ctx.stream, a);
+    WarpArgs a{src, flow, out, slot, B, K, h, w, C};
+    hipLaunchKernelGGL(warp_mean_kernel, dim3(ew_grid((size_t)B * h * w * C / 4)), dim3(256), 0, ctx.stream, a);
     check_launch("warp_mean");
 }
 
@@ -508,10 +502,9 @@ void run_pack_any(Ctx& ctx, PackArgs p, size_t amax_clear, bool u8, const void* 
 }
 
 // FuseNet tail: zbar = mean over sources of cat(src_fea, tar_fea) + (y2 * alpha + beta)   (FuseTailArgs)
-void run_fuse_tail(Ctx& ctx, const FuseTailArgs& t, const int* slot = nullptr) {
+void run_fuse_tail(Ctx& ctx, const FuseTailArgs& t) {
     TimeScope ts(ctx, TSNET_T_ELEMWISE);
-    if (slot) hipLaunchKernelGGL(fuse_resid_mean_slots_kernel, dim3(ew_grid((size_t)t.B * t.P * 2 * t.C1 / 4)), dim3(256), 0, ctx.stream, FuseTailSlotArgs{t, slot});
-    else hipLaunchKernelGGL(fuse_resid_mean_kernel, dim3(ew_grid((size_t)t.B * t.P * 2 * t.C1 / 4)), dim3(256), 0, ctx.stream, t);
+    hipLaunchKernelGGL(fuse_resid_mean_kernel, dim3(ew_grid((size_t)t.B * t.P * 2 * t.C1 / 4)), dim3(256), 0, ctx.stream, t);
     check_launch("fuse_resid_mean");
 }
 
@@ -644,23 +637,25 @@ struct tsnet_engine {
     hipEvent_t ev_done = nullptr;      // recorded behind the last launch of a forward on the caller's stream
     float* train_ws = nullptr;         // workspace of tsnet_train_extras, allocated on first use
 
-    // clip-mode cache.  Source-side tensors (x_img, X, shat, F1s, bbox_copy) hold K * SB images, SB = the cache's source-batch extent:
-    // (source s, driving frame b) reads image s*SB + b % SB.  Whatever is indexed by the (source, driving frame) pair -- flows, F1, F2 and
-    // their InstanceNorm pairs -- stays at n = s*B + b.
-    int cached_B = 0;               // SB of the cached sources: the batch of tsnet_set_sources, 1 for tsnet_set_sources_shared; 0 = no cache
+    // The encoded sources: ONE scheme.  The source-side tensors are K * Bmax SLOTS of one source each -- slot j is image j of X / shat / F1s
+    // and mask j of bbox_copy, all dense -- and every forward names, in a table, the slot that each (source s, driving frame b) pair reads:
+    // entry s*B + b (use_table; the kernels read nothing else to find a source).  Whatever is indexed by the pair itself -- flows, F1, F2 and
+    // their InstanceNorm pairs -- stays at n = s*B + b.  The modes differ in who fills the slots and who writes the table:
+    //   per-batch cache (tsnet_set_sources at batch B, the one-shot forward)   source s of frame b in slot s*B + b    table: the identity
+    //   shared cache (tsnet_set_sources_shared)                               source s in slot s                     table: s for every b
+    //   bank (tsnet_bank_put / tsnet_forward_bank)                            the slots the caller puts              table: the caller's
+    // They write the same buffers: whichever was written last is the one that can be read.
+    int cached_B = 0;               // batch of the cached sources: that of tsnet_set_sources, 1 for tsnet_set_sources_shared; 0 = no cache
     bool cached_shared = false;     // one source set for every driving frame: tsnet_forward_target takes any batch
-    float* bbox_copy = nullptr;     // (K, Bmax, H, W) device copies of the source bboxes (the first SB of every source's Bmax slots)
+    bool bank = false;              // the slots hold a bank (cached_B = 0 then)
+    std::vector<char> bank_filled;  // per slot: put since the bank was started
+    float* bbox_copy = nullptr;     // (K * Bmax, H, W) device copies of the source bboxes, one per slot
+    int* slot_tab = nullptr;        // device (arena): K * Bmax ints, the table of the forward being enqueued (written by slot_fill_kernel)
+    std::vector<int> slot_tab_host; // what slot_tab holds once everything enqueued so far has run: a forward with the same table skips the fill
     float* tbox = nullptr;          // (Bmax, H, W): the driving frames' masks widened from a compact call (wide calls pass their own tensor on)
     int last_B = 0;
-    int last_SB = 0;                // source-batch extent of the last forward (what "src_fea" holds per source)
+    int last_SB = 0;                // images per source the last forward's sources held: its batch, 1 on a shared source set (what "src_fea" holds per source)
     bool last_shared = false;       // ... and whether it ran on a shared source set (tsnet_train_extras refuses: its src_img is per batch element)
-    // source bank (tsnet_bank_put / tsnet_forward_bank): the same five buffers seen as K * Bmax SLOTS of one image each -- slot j is image j of
-    // x_img / X / shat / F1s and mask j of bbox_copy, read densely ((K*Bmax, H, W); the two caches above keep their (K, Bmax, H, W) stride).  A
-    // forward names the slot of every (source, driving frame) pair in a table, entry s*B + b; both caches above are the tables s*SB + b % SB.
-    // The bank and the caches overwrite each other: whichever was written last is the one that can be read.
-    bool bank = false;              // the source-side buffers hold a bank (cached_B = 0 then)
-    std::vector<char> bank_filled;  // per slot: put since the bank was started
-    int* slot_tab = nullptr;        // device (arena): K * Bmax ints, the table of the bank forward being enqueued (written by slot_fill_kernel)
     bool last_bank = false;         // the last forward ran on the bank ("src_fea" holds K * Bmax images; tsnet_train_extras refuses)
     int cur_B = 0;                        // batch of the forward being enqueued
     float src_div[TSNET_MAX_SOURCES];  // per-source image divisor (255; 1 for use_prev sources), tsnet_set_source_divisors
@@ -709,10 +704,11 @@ struct tsnet_engine {
     void set_sources(Ctx& ctx, const SrcIn& in, int B, hipStream_t bbox_stream = nullptr);
     void target_chain(Ctx& ctx, const TarIn& tar, int B);
     void bank_put(Ctx& ctx, int first, int count, const SrcIn& in, const float* div);
-    void forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int SB, int Kc = 0, const int* slot = nullptr);
-    void forward_target(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int SB) {
+    void use_table(Ctx& ctx, int B, int Kc, const int* bank_slots);
+    void forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int Kc, const int* bank_slots = nullptr);
+    void forward_target(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B) {
         target_chain(ctx, tar, B);
-        forward_rest(ctx, tar, out_rgb, out_flow, B, SB);
+        forward_rest(ctx, tar, out_rgb, out_flow, B, K);
     }
 };
 
@@ -907,7 +903,7 @@ void tsnet_engine::alloc_all(hipStream_t s) {
     for (int i = 0; i < 2; ++i) { want(&ab_side[i][0], NB * 2 * C); want(&ab_side[i][1], NB * 2 * C); }
     want(&bbox_copy, NB * H * W);
     float* slot_f = nullptr;
-    want(&slot_f, NB);                                                       // the source bank's slot table (ints)
+    want(&slot_f, NB);                                                       // the slot table (ints)
     if (P >= 2048 && P % 64 == 0) want(&flow_part, 2 * flowp_part_words((int)NB, P, flowp_slices(h, w)));   // flow_kernel_p: one softmax state per (image, target tile, slice, column), 8-byte words
     // InstanceNorm partials (doubles = 2 floats each): the stand-alone pass N*64*C*2, a conv epilogue N * tiles-per-image * Cout * 2
     // with tiles of at least 64 positions (ceil for ragged images), per lane
@@ -991,6 +987,7 @@ void tsnet_engine::encode(Ctx& ctx, std::vector<ConvLayer>& L, const float* xin,
 // passes its side stream (the flow kernel's own lane: the copies are ordered ahead of it there and cost the caller's lane nothing --
 // three 4.7 us copy kernels + their boundaries sat in front of the stem until round 5); null = the caller's stream (clip mode).
 // Compact sources: the packing kernel widens the masks into bbox_copy itself, on the caller's lane (ordered ahead of the flow kernel by the join).
+// Source s of frame b goes to slot s*B + b of every source-side tensor, the masks included.
 void tsnet_engine::set_sources(Ctx& ctx, const SrcIn& in, int B, hipStream_t bbox_stream) {
     cur_B = B;
     const int H = cfg.height, W = cfg.width;
@@ -1001,9 +998,9 @@ void tsnet_engine::set_sources(Ctx& ctx, const SrcIn& in, int B, hipStream_t bbo
         p.coords = cfg.addcoords ? d_coords : nullptr;
         p.out = x_img; p.S = K; p.B = B; p.H = H; p.W = W; p.L = cfg.label_nc; p.nimg = 3; p.Cp = cp_img;
         p.amax_out = amax_src();
-        run_pack_any(ctx, p, (size_t)K * B, in.u8, in.img, in.lbl, in.bbox, in.mean, bbox_copy, (size_t)Bmax * H * W);
+        run_pack_any(ctx, p, (size_t)K * B, in.u8, in.img, in.lbl, in.bbox, in.mean, bbox_copy, (size_t)B * H * W);
         for (int s = 0; s < K && !in.u8; ++s)
-            HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)s * Bmax * H * W, in.bbox[s], (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice,
+            HIP_TRY(hipMemcpyAsync(bbox_copy + (size_t)s * B * H * W, in.bbox[s], (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice,
                                    bbox_stream ? bbox_stream : ctx.stream));
     }
     encode(ctx, img_enc, x_img, amax_src(), K * B, raw_img, X, cfg.enc_blocks);
@@ -1064,13 +1061,28 @@ void tsnet_engine::target_chain(Ctx& ctx, const TarIn& tar, int B) {
     conv(ctx, fuse_c1_tar, t);
 }
 
-// SB: source-batch extent of what set_sources left behind (B, or 1 for the shared cache)
-// slot (device table, entry s*B + b) and Kc sources per frame: a forward on the source bank
-void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int SB, int Kc, const int* slot) {
+// The slot table of a forward of B driving frames on Kc sources each -> slot_tab, on the caller's stream.  The one place that says what the
+// modes are (struct tsnet_engine): the bank forward passes its caller's table, the caches' tables are written here.  The fill is skipped when
+// the device already holds (or, stream-ordered, will hold) the same entries: a clip's forwards at one batch share one table.  That rests on
+// what tsnet_abi.h asks of any two calls on one handle -- they share the arena, so the caller orders them, and with them this fill.
+void tsnet_engine::use_table(Ctx& ctx, int B, int Kc, const int* bank_slots) {
+    std::vector<int> t((size_t)Kc * B);
+    for (int s = 0; s < Kc; ++s)
+        for (int b = 0; b < B; ++b) t[s * B + b] = bank_slots ? bank_slots[s * B + b] : cached_shared ? s : s * B + b;
+    if (t.size() <= slot_tab_host.size() && std::equal(t.begin(), t.end(), slot_tab_host.begin())) return;
+    slot_tab_host.clear();                                  // (a launch that throws leaves no claim behind)
+    run_slot_fill(ctx.stream, slot_tab, t.data(), (int)t.size());
+    slot_tab_host = std::move(t);
+}
+
+// Kc sources per driving frame; bank_slots (host, entry s*B + b): the table of a forward on the source bank, null on the caches
+void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, float* out_flow, int B, int Kc, const int* bank_slots) {
     cur_B = B;
     const float* tar_bbox = tar.u8 ? tbox : static_cast<const float*>(tar.bbox);      // compact: widened by target_chain's packing kernel
-    const int K = Kc > 0 ? Kc : this->K;                   // sources per driving frame of THIS forward
+    const int K = Kc;                                      // sources per driving frame of THIS forward
     const int H = cfg.height, W = cfg.width, NB = K * B;
+    use_table(ctx, B, K, bank_slots);                      // ahead of the fork: the side lane's readers are ordered behind it
+    const int* slot = slot_tab;
     // ---- transformation branch.  Its result (pg) is first needed by the decoder, and its kernels are latency-bound (384 workgroups):
     // with the side stream available it runs there, concurrently with the MFMA-bound synthesis branch below, and joins before dec_map.
     const bool fork = side_stream && !ctx.timing && ctx.lane == 0;
@@ -1083,14 +1095,14 @@ void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, floa
     }
     FlowArgs fa{};
     fa.tq = reinterpret_cast<const unsigned short*>(that); fa.sq = reinterpret_cast<const unsigned short*>(shat); fa.tar_bbox = tar_bbox;
-    for (int s = 0; s < K; ++s) fa.src_bbox[s] = bbox_copy + (size_t)s * Bmax * H * W;
+    fa.src_bbox = bbox_copy;
     fa.gx = d_gx; fa.gy = d_gy; fa.flow = flow;
     fa.part = reinterpret_cast<unsigned long long*>(flow_part); fa.cnt = flow_cnt;
-    fa.B = B; fa.SB = SB; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
-    run_flow(cx, fa, NB, 0, slot);                          // (with a table the kernels read the masks densely from src_bbox[0] = bbox_copy)
+    fa.B = B; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
+    run_flow(cx, fa, NB, slot);
     if (out_flow)
         HIP_TRY(hipMemcpyAsync(out_flow, flow, (size_t)NB * P * 2 * sizeof(float), hipMemcpyDeviceToDevice, cx.stream));
-    run_warp(cx, X, flow, pg, B, K, h, w, C, SB, slot);
+    run_warp(cx, X, slot, flow, pg, B, K, h, w, C);
     if (fork) HIP_TRY(hipEventRecord(ev_join2, side_stream));
 
     // ---- synthesis branch
@@ -1099,11 +1111,11 @@ void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, floa
         auto s1 = next_ab(ctx);
         auto s2 = next_ab(ctx);
         // F1 = conv_src(src) [from set_sources] + conv_tar(tar) [target chain], and its InstanceNorm statistics
-        run_add_stats(ctx, F1s, FT, B, F1, NB, P, 2 * C, part, s1.first, s1.second, SB, slot);
+        run_add_stats(ctx, F1s, slot, FT, B, F1, NB, P, 2 * C, part, s1.first, s1.second);
         ConvCall b; b.x = F1; b.alpha = s1.first; b.beta = s1.second; b.relu = 1; b.bound = sqP;
         b.N = NB; b.H = h; b.W = w; b.y = F2;
         conv_stats(ctx, fuse_c2, b, NB, P, s2.first, s2.second);
-        run_fuse_tail(ctx, FuseTailArgs{X, tar_fea, F2, s2.first, s2.second, zbar, B, K, P, C, SB}, slot);
+        run_fuse_tail(ctx, FuseTailArgs{X, tar_fea, F2, s2.first, s2.second, zbar, slot, B, K, P, C});
         // zbar = mean over sources of cat(src_fea, tar_fea) + IN(.): bounded by enc_bound + sqrt(P).  fuse_net.conv has no norm behind it:
         // it publishes max |sg| per image for dec.map_conv's operand scale
         ConvCall c; c.x = zbar; c.bound = enc_bound() + sqP; c.N = B; c.H = h; c.W = w; c.y = sg;
@@ -1151,7 +1163,7 @@ void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, floa
         for (int c = 0; c < 3; ++c) ha.bg[c] = (-cfg.pose_mean[c]) / 255.0f;             // TSNet_pose.py:276
         launch_head(ha, hh, ww, B, ctx.stream, ctx.cus, 0, head_wq, head_wq_unscale);
     }
-    last_B = B; last_SB = SB; last_shared = cached_shared; last_bank = slot != nullptr;
+    last_B = B; last_SB = bank ? 1 : cached_B; last_shared = cached_shared; last_bank = bank;
     HIP_TRY(hipEventRecord(ev_done, ctx.stream));       // what tsnet_stage_ptr orders its widening pass behind
 }
 
@@ -1343,7 +1355,7 @@ static int forward_target_any(tsnet_handle h, const TarIn& tar, float* out_rgb, 
     if (!h->cached_shared && h->cached_B != B) throw ArgError("forward_target: batch differs from the cached sources (call tsnet_set_sources first)");
     if (tar.u8) check_compact(h, nullptr);
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
-    h->forward_target(ctx, tar, out_rgb, out_flow, B, h->cached_B);
+    h->forward_target(ctx, tar, out_rgb, out_flow, B);
     API_END(h)
 }
 
@@ -1399,9 +1411,8 @@ static int forward_bank_any(tsnet_handle h, const int* slots, int Kc, const TarI
     }
     if (tar.u8) check_compact(h, nullptr);
     Ctx ctx((hipStream_t)stream, h->cus, h->timing.on ? &h->timing : nullptr);
-    run_slot_fill(ctx.stream, h->slot_tab, slots, Kc * B);
     h->target_chain(ctx, tar, B);
-    h->forward_rest(ctx, tar, out_rgb, out_flow, B, 1, Kc, h->slot_tab);
+    h->forward_rest(ctx, tar, out_rgb, out_flow, B, Kc, slots);
     API_END(h)
 }
 
@@ -1441,7 +1452,7 @@ static int forward_any(tsnet_handle h, const SrcIn& in, const TarIn& tar, float*
         HIP_TRY(hipStreamWaitEvent(main, h->ev_join, 0));
         join.done = true;
         Ctx ctx(main, h->cus);
-        h->forward_rest(ctx, tar, out_rgb, out_flow, B, B);
+        h->forward_rest(ctx, tar, out_rgb, out_flow, B, h->K);
         API_END(h)
     }
     int rc = set_sources_any(h, in, B, false, stream);
@@ -1727,19 +1738,30 @@ int tsnet_op_upsample2x(const float* x, const float* alpha, const float* beta, i
     OP_END
 }
 
-// tar_fea (B), src_fea / src_bbox / flow (K*B, image k*B + b).  repeat > 1 re-launches the flow kernel (identical results) for timing.
-// a host slot table of n entries in 0 .. n_src - 1 -> a device copy (operator entry points: they return after the stream has drained)
-static int* op_slot_table(DevBufs& bufs, const char* op, const int* slots, int n, int n_src) {
+// The operator entry points run the forward's kernels, which find a source image through a slot table alone: every spelling of an operator is
+// one launch on the table that expresses it.  The table lives in the call's DevBufs, so each of these entries returns after the stream has drained.
+static const int* op_table(DevBufs& bufs, const int* t, int n) {      // n host entries -> a device copy
+    int* d = bufs.alloc<int>((size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpy(d, t, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    return d;
+}
+// the legacy spellings' source-batch extent: src holds K * ext images and (source k, frame b) reads image k*ext + b % ext (ext = B: the identity)
+static const int* op_table_ext(DevBufs& bufs, int B, int K, int ext) {
+    std::vector<int> t((size_t)K * B);
+    for (int n = 0; n < K * B; ++n) t[n] = n / B * ext + n % B % ext;
+    return op_table(bufs, t.data(), K * B);
+}
+// a caller's table of n entries in 0 .. n_src - 1
+static const int* op_slot_table(DevBufs& bufs, const char* op, const int* slots, int n, int n_src) {
     if (!slots) throw ArgError(std::string(op) + ": null slot table");
     if (n_src < 1) throw ArgError(std::string(op) + ": the number of source images must be >= 1");
     for (int i = 0; i < n; ++i)
         if (slots[i] < 0 || slots[i] >= n_src) throw ArgError(std::string(op) + ": slot " + std::to_string(slots[i]) + " is outside the " + std::to_string(n_src) + " source images");
-    int* d = bufs.alloc<int>((size_t)n * sizeof(int));
-    HIP_TRY(hipMemcpy(d, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    return d;
+    return op_table(bufs, slots, n);
 }
 
-// slots (host, K*B entries, or null) + n_src: src_fea / src_bbox hold n_src images and (source k, frame b) reads image slots[k*B + b]
+// tar_fea (B), flow (K*B, image k*B + b).  repeat > 1 re-launches the flow kernel (identical results) for timing.
+// slots (host, K*B entries) + n_src: src_fea / src_bbox hold n_src images and (source k, frame b) reads image slots[k*B + b]; null: K*B images, the identity
 static void op_flow_impl(const float* tar_fea, const float* src_fea, const float* tar_bbox, const float* src_bbox,
                          int B, int K, int h, int w, int C, int H, int W, float* flow, int variant, int repeat, float* ms_out, hipStream_t stream,
                          const int* slots = nullptr, int n_src = 0) {
@@ -1749,7 +1771,7 @@ static void op_flow_impl(const float* tar_fea, const float* src_fea, const float
     Ctx ctx(stream, current_device_cus());
     const int P = h * w, NB = K * B;
     DevBufs bufs;
-    const int* dslot = slots ? op_slot_table(bufs, "flow op", slots, NB, n_src) : nullptr;
+    const int* dslot = slots ? op_slot_table(bufs, "flow op", slots, NB, n_src) : op_table_ext(bufs, B, K, B);
     const int NS = slots ? n_src : NB;                      // source images
     auto* that = bufs.alloc<unsigned short>(flow_plane_halves(B, P, C) * 2);
     auto* shat = bufs.alloc<unsigned short>(flow_plane_halves(NS, P, C) * 2);
@@ -1769,12 +1791,12 @@ static void op_flow_impl(const float* tar_fea, const float* src_fea, const float
     run_l2norm_split(ctx, tar_fea, that, B, P, C);
     run_l2norm_split(ctx, src_fea, shat, NS, P, C);
     fa.tq = that; fa.sq = shat; fa.tar_bbox = tar_bbox; fa.gx = gx; fa.gy = gy; fa.flow = flow;
-    for (int k = 0; k < K; ++k) fa.src_bbox[k] = src_bbox + (size_t)k * B * H * W;
+    fa.src_bbox = src_bbox;
     fa.B = B; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
     std::unique_ptr<EventPair> ev(ms_out ? new EventPair : nullptr);
-    run_flow(ctx, fa, NB, variant, dslot);
+    run_flow(ctx, fa, NB, dslot, variant);
     if (ev) HIP_TRY(hipEventRecord(ev->a, ctx.stream));
-    for (int r = 1; r < repeat; ++r) run_flow(ctx, fa, NB, variant, dslot);
+    for (int r = 1; r < repeat; ++r) run_flow(ctx, fa, NB, dslot, variant);
     if (ev) HIP_TRY(hipEventRecord(ev->b, ctx.stream));
     HIP_TRY(hipStreamSynchronize(ctx.stream));
     if (ms_out) *ms_out = repeat > 1 ? ev->ms() / (float)(repeat - 1) : 0.f;
@@ -1810,7 +1832,9 @@ int tsnet_op_warp(const float* src_fea, const float* flow, int B, int h, int w, 
     if (!src_fea || !flow || !out) throw ArgError("null tensor");
     if (C & 3) throw ArgError("warp op: C must be a multiple of 4");
     Ctx ctx((hipStream_t)stream, current_device_cus());
-    run_warp(ctx, src_fea, flow, out, B, 1, h, w, C);
+    DevBufs mem;
+    run_warp(ctx, src_fea, op_table_ext(mem, B, 1, B), flow, out, B, 1, h, w, C);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
     OP_END
 }
 
@@ -1821,85 +1845,71 @@ int tsnet_op_warp_k(const float* src_fea, const float* flow, int B, int K, int h
     if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape");
     Ctx ctx((hipStream_t)stream, current_device_cus());
     if (ms_out) *ms_out = 0.f;
-    run_warp(ctx, src_fea, flow, out, B, K, h, w, C);
+    DevBufs mem;
+    const int* d = op_table_ext(mem, B, K, B);        // uploaded once, outside the events
+    run_warp(ctx, src_fea, d, flow, out, B, K, h, w, C);
     if (repeat > 1) {                    // launches 2 .. repeat between two events: the kernel ALONE (tools/warp_bench.py)
         EventPair ev;
         HIP_TRY(hipEventRecord(ev.a, ctx.stream));
-        for (int i = 1; i < repeat; ++i) run_warp(ctx, src_fea, flow, out, B, K, h, w, C);
+        for (int i = 1; i < repeat; ++i) run_warp(ctx, src_fea, d, flow, out, B, K, h, w, C);
         HIP_TRY(hipEventRecord(ev.b, ctx.stream));
         const float t = ev.ms();
         if (ms_out) *ms_out = t / (float)(repeat - 1);
     }
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
     OP_END
+}
+
+// tsnet_op_warp_k_shared (ext = its SB) and tsnet_op_warp_k_slots (ext < 0: the caller's table)
+static void op_warp_any(const float* src_fea, const float* flow, int B, int K, int ext, const int* slots, int n_src, int h, int w, int C, float* out, void* stream) {
+    if (!src_fea || !flow || !out) throw ArgError("warp op: null tensor");
+    if (C < 4 || (C & 3)) throw ArgError("warp op: C must be a multiple of 4");
+    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape (1 <= K <= 8 sources, B, h, w >= 1)");
+    if (ext >= 0 && (ext < 1 || B % ext)) throw ArgError("warp op: the source-batch extent must divide the batch");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    DevBufs mem;
+    run_warp(ctx, src_fea, ext >= 0 ? op_table_ext(mem, B, K, ext) : op_slot_table(mem, "warp op", slots, K * B, n_src), flow, out, B, K, h, w, C);
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
 }
 
 int tsnet_op_warp_k_shared(const float* src_fea, const float* flow, int B, int K, int SB, int h, int w, int C, float* out, void* stream) {
     OP_BEGIN
-    if (!src_fea || !flow || !out) throw ArgError("warp op: null tensor");
-    if (C < 4 || (C & 3)) throw ArgError("warp op: C must be a multiple of 4");
-    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape (1 <= K <= 8 sources, B, h, w >= 1)");
-    if (SB < 1 || B % SB) throw ArgError("warp op: the source-batch extent must divide the batch");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    run_warp(ctx, src_fea, flow, out, B, K, h, w, C, SB);
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    op_warp_any(src_fea, flow, B, K, SB < 0 ? 0 : SB, nullptr, 0, h, w, C, out, stream);
     OP_END
 }
 
 int tsnet_op_warp_k_slots(const float* src_fea, const float* flow, int B, int K, int h, int w, int C, float* out, const int* slots, int n_src, void* stream) {
     OP_BEGIN
-    if (!src_fea || !flow || !out) throw ArgError("warp op: null tensor");
-    if (C < 4 || (C & 3)) throw ArgError("warp op: C must be a multiple of 4");
-    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape (1 <= K <= 8 sources, B, h, w >= 1)");
+    op_warp_any(src_fea, flow, B, K, -1, slots, n_src, h, w, C, out, stream);
+    OP_END
+}
+
+// tsnet_op_add_stats (ext = its x_sb) and tsnet_op_add_stats_slots (ext < 0: the caller's table)
+static void op_add_stats_any(const float* x, const float* add, int add_nmod, int ext, const int* slots, int n_src, int N, int HW, int C,
+                             float* y, float* alpha, float* beta, void* stream) {
+    if (!x || !add || !y || !alpha || !beta) throw ArgError("add_stats op: null tensor");
+    if (C < 4 || (C & 3)) throw ArgError("add_stats op: C must be a multiple of 4");
+    if (N < 1 || N > 65535 || HW < 1) throw ArgError("add_stats op: bad shape (1 <= N <= 65535, HW >= 1)");
+    if (add_nmod < 1 || N % add_nmod) throw ArgError("add_stats op: add_nmod must divide N");
+    if (ext >= 0 && (ext < 1 || add_nmod % ext)) throw ArgError("add_stats op: the source-batch extent must divide add_nmod");
     Ctx ctx((hipStream_t)stream, current_device_cus());
     DevBufs mem;
-    const int* d = op_slot_table(mem, "warp op", slots, K * B, n_src);
-    run_warp(ctx, src_fea, flow, out, B, K, h, w, C, 1, d);
+    const int* d = ext >= 0 ? op_table_ext(mem, add_nmod, N / add_nmod, ext) : op_slot_table(mem, "add_stats op", slots, N, n_src);
+    double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
+    run_add_stats(ctx, x, d, add, add_nmod, y, N, HW, C, part, alpha, beta);
     HIP_TRY(hipStreamSynchronize(ctx.stream));
+}
+
+int tsnet_op_add_stats(const float* x, const float* add, int add_nmod, int x_sb, int N, int HW, int C, float* y, float* alpha, float* beta, void* stream) {
+    OP_BEGIN
+    op_add_stats_any(x, add, add_nmod, x_sb < 0 ? 0 : x_sb, nullptr, 0, N, HW, C, y, alpha, beta, stream);
     OP_END
 }
 
 int tsnet_op_add_stats_slots(const float* x, const float* add, int add_nmod, int N, int HW, int C, float* y, float* alpha, float* beta,
                              const int* slots, int n_src, void* stream) {
     OP_BEGIN
-    if (!x || !add || !y || !alpha || !beta) throw ArgError("add_stats op: null tensor");
-    if (C < 4 || (C & 3)) throw ArgError("add_stats op: C must be a multiple of 4");
-    if (N < 1 || N > 65535 || HW < 1) throw ArgError("add_stats op: bad shape (1 <= N <= 65535, HW >= 1)");
-    if (add_nmod < 1 || N % add_nmod) throw ArgError("add_stats op: add_nmod must divide N");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    DevBufs mem;
-    const int* d = op_slot_table(mem, "add_stats op", slots, N, n_src);
-    double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
-    run_add_stats(ctx, x, add, add_nmod, y, N, HW, C, part, alpha, beta, 0, d);
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    OP_END
-}
-
-int tsnet_op_fuse_tail_slots(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
-                             int B, int K, int P, int C1, float* zbar, const int* slots, int n_src, void* stream) {
-    OP_BEGIN
-    if (!src_fea || !tar_fea || !y2 || !alpha || !beta || !zbar) throw ArgError("fuse_tail op: null tensor");
-    if (C1 < 4 || (C1 & 3)) throw ArgError("fuse_tail op: C1 must be a multiple of 4");
-    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || P < 1) throw ArgError("fuse_tail op: bad shape (1 <= K <= 8 sources, B, P >= 1)");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    DevBufs mem;
-    const int* d = op_slot_table(mem, "fuse_tail op", slots, K * B, n_src);
-    run_fuse_tail(ctx, FuseTailArgs{src_fea, tar_fea, y2, alpha, beta, zbar, B, K, P, C1, 1}, d);
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    OP_END
-}
-
-int tsnet_op_add_stats(const float* x, const float* add, int add_nmod, int x_sb, int N, int HW, int C, float* y, float* alpha, float* beta, void* stream) {
-    OP_BEGIN
-    if (!x || !add || !y || !alpha || !beta) throw ArgError("add_stats op: null tensor");
-    if (C < 4 || (C & 3)) throw ArgError("add_stats op: C must be a multiple of 4");
-    if (N < 1 || N > 65535 || HW < 1) throw ArgError("add_stats op: bad shape (1 <= N <= 65535, HW >= 1)");
-    if (add_nmod < 1 || N % add_nmod) throw ArgError("add_stats op: add_nmod must divide N");
-    if (x_sb < 1 || add_nmod % x_sb) throw ArgError("add_stats op: the source-batch extent must divide add_nmod");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    DevBufs mem;
-    double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
-    run_add_stats(ctx, x, add, add_nmod, y, N, HW, C, part, alpha, beta, x_sb);
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    op_add_stats_any(x, add, add_nmod, -1, slots, n_src, N, HW, C, y, alpha, beta, stream);
     OP_END
 }
 
@@ -1913,16 +1923,31 @@ int tsnet_op_finalize_stats(const double* part, int N, int S, int C, int HW, flo
     OP_END
 }
 
-int tsnet_op_fuse_tail(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
-                       int B, int K, int SB, int P, int C1, float* zbar, void* stream) {
-    OP_BEGIN
+// tsnet_op_fuse_tail (ext = its SB) and tsnet_op_fuse_tail_slots (ext < 0: the caller's table)
+static void op_fuse_tail_any(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
+                             int B, int K, int ext, const int* slots, int n_src, int P, int C1, float* zbar, void* stream) {
     if (!src_fea || !tar_fea || !y2 || !alpha || !beta || !zbar) throw ArgError("fuse_tail op: null tensor");
     if (C1 < 4 || (C1 & 3)) throw ArgError("fuse_tail op: C1 must be a multiple of 4");
     if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || P < 1) throw ArgError("fuse_tail op: bad shape (1 <= K <= 8 sources, B, P >= 1)");
-    if (SB < 1 || B % SB) throw ArgError("fuse_tail op: the source-batch extent must divide the batch");
+    if (ext >= 0 && (ext < 1 || B % ext)) throw ArgError("fuse_tail op: the source-batch extent must divide the batch");
     Ctx ctx((hipStream_t)stream, current_device_cus());
-    run_fuse_tail(ctx, FuseTailArgs{src_fea, tar_fea, y2, alpha, beta, zbar, B, K, P, C1, SB});
+    DevBufs mem;
+    const int* d = ext >= 0 ? op_table_ext(mem, B, K, ext) : op_slot_table(mem, "fuse_tail op", slots, K * B, n_src);
+    run_fuse_tail(ctx, FuseTailArgs{src_fea, tar_fea, y2, alpha, beta, zbar, d, B, K, P, C1});
     HIP_TRY(hipStreamSynchronize(ctx.stream));
+}
+
+int tsnet_op_fuse_tail(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
+                       int B, int K, int SB, int P, int C1, float* zbar, void* stream) {
+    OP_BEGIN
+    op_fuse_tail_any(src_fea, tar_fea, y2, alpha, beta, B, K, SB < 0 ? 0 : SB, nullptr, 0, P, C1, zbar, stream);
+    OP_END
+}
+
+int tsnet_op_fuse_tail_slots(const float* src_fea, const float* tar_fea, const float* y2, const float* alpha, const float* beta,
+                             int B, int K, int P, int C1, float* zbar, const int* slots, int n_src, void* stream) {
+    OP_BEGIN
+    op_fuse_tail_any(src_fea, tar_fea, y2, alpha, beta, B, K, -1, slots, n_src, P, C1, zbar, stream);
     OP_END
 }
 

@@ -21,24 +21,18 @@ inline size_t flow_lds_bytes(int NT, int h, int w, int C) { return flow_lds_byte
 
 struct FlowArgs {
     const unsigned short* tq; // target planes of B images (l2norm_split_kernel)
-    const unsigned short* sq; // source planes of K*SB images: (source s, driving frame b) reads image s*SB + b % SB
+    const unsigned short* sq; // source planes, one image per slot
     const float* tar_bbox;    // (B, H, W)
-    const float* src_bbox[8]; // per source (SB, H, W)
+    const float* src_bbox;    // source masks, one (H, W) mask per slot
+    const int* slot;          // [NB] device, the slot table: (source s, driving frame b) reads image slot[s*B + b] of sq and mask slot[s*B + b] of src_bbox
     const float* gx;          // (w) linspace(-1,1,w)
     const float* gy;          // (h)
     float* flow;              // (NB, P, 2)
     int B, P, C, h, w, H, W, sy, sx;
-    int SB;                   // source-batch extent: B (every driving frame has its own sources) or 1 (one source set shared by the batch)
     // flow_kernel_p only
     unsigned long long* part; // [NB][tiles][S][64][2]: (max, sum) and (x, y) of a slice's softmax state, two floats per 8-byte word
     int* cnt;                 // [B][tiles] arrival counters, zero between launches
     int K, G, S;              // sources per batch element; workgroups per target tile; slices per source image (flowp_slices: S % G == 0)
-};
-// source bank: the argument block of the kernels' slot forms (flow_slots_kernel, flow_kernel_p_slots).  Its own block, so that the kernels of
-// the two cache modes keep their argument layout -- and with it their ISA -- to the instruction.
-struct FlowSlotArgs {
-    FlowArgs a;               // a.SB is not read; a.src_bbox[0] alone: one (H, W) mask per source image
-    const int* slot;          // [NB] device: (source s, driving frame b) reads image slot[s*B + b] of a.sq and the mask a.src_bbox[0] + slot[s*B + b]*H*W
 };
 
 // LDS bytes of flow_kernel_p (64 targets per workgroup): target planes, two merge buffers [kFlowWaves][64][4] floats, a 64-float mask row

@@ -9,36 +9,24 @@
 
 namespace tsnet {
 
-void launch_flow_p(const FlowArgs& a, int variant, hipStream_t s, const int* slot) {
+void launch_flow_p(const FlowArgs& a, int variant, hipStream_t s) {
     const size_t lds = flowp_lds_bytes(a.h, a.w, a.C);
     const dim3 grid(a.B * (a.P / 64) * a.G), block(64 * kFlowWaves);
 #ifdef TSNET_TOOLS
     if (variant == 2) {                          // ablation: no exp / accumulate pass
-        if (slot) throw std::invalid_argument("flow: the ablation variant takes no slot table");
         ensure_dynamic_lds(reinterpret_cast<const void*>(flow_kernel_p<2>), lds);
         hipLaunchKernelGGL(flow_kernel_p<2>, grid, block, lds, s, a);
         return;
     }
 #endif
     if (variant) throw std::invalid_argument("flow: experiment variants exist in the tools build only");
-    if (slot) {                                  // source bank: the slot form
-        ensure_dynamic_lds(reinterpret_cast<const void*>(flow_kernel_p_slots), lds);
-        hipLaunchKernelGGL(flow_kernel_p_slots, grid, block, lds, s, FlowSlotArgs{a, slot});
-        return;
-    }
     ensure_dynamic_lds(reinterpret_cast<const void*>(flow_kernel_p<0>), lds);
     hipLaunchKernelGGL(flow_kernel_p<0>, grid, block, lds, s, a);
 }
 
 // flow_kernel<NT> (flow_sweep.hpp): NT = 2 (64 targets per workgroup) while their planes fit the LDS, else 1; grid = workgroups
-void launch_flow(const FlowArgs& a, int NT, size_t lds, unsigned grid, hipStream_t s, const int* slot) {
-    if (slot && NT == 2) {                       // source bank: the slot forms
-        ensure_dynamic_lds(reinterpret_cast<const void*>(flow_slots_kernel<2>), lds);
-        hipLaunchKernelGGL(flow_slots_kernel<2>, dim3(grid), dim3(64 * kFlowWaves), lds, s, FlowSlotArgs{a, slot});
-    } else if (slot && NT == 1) {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(flow_slots_kernel<1>), lds);
-        hipLaunchKernelGGL(flow_slots_kernel<1>, dim3(grid), dim3(64 * kFlowWaves), lds, s, FlowSlotArgs{a, slot});
-    } else if (NT == 2) {
+void launch_flow(const FlowArgs& a, int NT, size_t lds, unsigned grid, hipStream_t s) {
+    if (NT == 2) {
         ensure_dynamic_lds(reinterpret_cast<const void*>(flow_kernel<2>), lds);
         hipLaunchKernelGGL(flow_kernel<2>, dim3(grid), dim3(64 * kFlowWaves), lds, s, a);
     } else if (NT == 1) {

@@ -44,9 +44,9 @@ __device__ __forceinline__ void flow_unpack2(unsigned long long v, float& a, flo
 }
 
 // grid = B * (P / 64) * G (1-D), block = 512.  OPT (tools): bit 1 = skip the exp / accumulate pass (ablation: computes garbage).
-// SL: the source image of a (source, frame) pair comes from the slot table (FlowSlotArgs: a source bank), one scalar load per source of the sweep.
-template <int OPT, bool SL>
-__device__ __forceinline__ void flow_persist_body(const FlowArgs& a, const int* slot) {
+// The source image of a (source, frame) pair comes from the slot table (flow_args.hpp), one scalar load per source of the sweep.
+template <int OPT>
+__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
     constexpr int NT = 2, NTH = 64 * kFlowWaves;
     HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) unsigned char, smem_raw)
     const int KC = (a.C + 31) / 32 * 2;
@@ -63,7 +63,6 @@ __device__ __forceinline__ void flow_persist_body(const FlowArgs& a, const int* 
     const int item = xcd_item(blockIdx.x, (int)gridDim.x);
     const int t = item % tiles, gb = item / tiles;
     const int b = gb % a.B, g = gb / a.B;
-    const int bs = b % a.SB;                  // the frame's image within a source (flow_args.hpp)
     const int tb0 = t * NT;
 
     {   // the workgroup's target fragments: one contiguous region of the plane buffer
@@ -101,8 +100,8 @@ __device__ __forceinline__ void flow_persist_body(const FlowArgs& a, const int* 
         const int n = s_idx * a.B + b;
         const int buf = it & 1;
         const int sp_base = slice * nps;
-        const int img = SL ? slot[n] : s_idx * a.SB + bs;
-        const float* sb = SL ? a.src_bbox[0] + (size_t)img * a.H * a.W : a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
+        const int img = a.slot[n];
+        const float* sb = a.src_bbox + (size_t)img * a.H * a.W;
         float m_run[NT], l_run[NT], ax[NT], ay[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) { m_run[j] = -3.0e38f; l_run[j] = 0.f; ax[j] = 0.f; ay[j] = 0.f; }
@@ -303,9 +302,5 @@ __device__ __forceinline__ void flow_persist_body(const FlowArgs& a, const int* 
         }
     }
 }
-
-template <int OPT>
-__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) { flow_persist_body<OPT, false>(a, nullptr); }
-__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p_slots(FlowSlotArgs s) { flow_persist_body<0, true>(s.a, s.slot); }
 
 }  // namespace tsnet

@@ -13,9 +13,9 @@ namespace tsnet {
 
 // grid = Ppad / (32 NT) * NB (1-D), block = 512.  dyn LDS: target planes NT * KC * 2 KiB, then ms[Ppad], gx[w], gy[h]; the merge buffer
 // [16][NT * 32][4] floats aliases the target planes after the sweep.
-// SL: the source image comes from the slot table (FlowSlotArgs) -- one scalar load per workgroup, (s, b) being fixed per workgroup.
-template <int NT, bool SL>
-__device__ __forceinline__ void flow_sweep_body(const FlowArgs& a, const int* slot) {
+// The source image comes from the slot table (flow_args.hpp) -- one scalar load per workgroup, (s, b) being fixed per workgroup.
+template <int NT>
+__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
     constexpr int NTH = 64 * kFlowWaves;
     HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) unsigned char, smem_raw)
     const int Ppad = (a.P + 63) / 64 * 64, KC = (a.C + 31) / 32 * 2;
@@ -33,7 +33,6 @@ __device__ __forceinline__ void flow_sweep_body(const FlowArgs& a, const int* sl
     const int item = xcd_item(blockIdx.x, (int)gridDim.x);
     const int n = item / tiles;
     const int s_idx = n / a.B, b = n - s_idx * a.B;
-    const int bs = b % a.SB;                                             // the frame's image within a source (flow_args.hpp)
     const int tb0 = (item - n * tiles) * NT;
 
     // the workgroup's target fragments: one contiguous region of the plane buffer
@@ -49,8 +48,8 @@ __device__ __forceinline__ void flow_sweep_body(const FlowArgs& a, const int* sl
             for (int u = 0; u < 8; ++u) { const int i = i0 + u * NTH + tid; if (i < cnt) d[i] = v[u]; }
         }
     }
-    const int img = SL ? slot[n] : s_idx * a.SB + bs;                 // the (source, frame) pair's image of the source planes
-    const float* sb = SL ? a.src_bbox[0] + (size_t)img * a.H * a.W : a.src_bbox[s_idx] + (size_t)bs * a.H * a.W;
+    const int img = a.slot[n];                                           // the (source, frame) pair's image of the source planes and masks
+    const float* sb = a.src_bbox + (size_t)img * a.H * a.W;
     for (int p = tid; p < Ppad; p += NTH) {
         float v = 0.f;
         if (p < a.P) {
@@ -205,11 +204,5 @@ __device__ __forceinline__ void flow_sweep_body(const FlowArgs& a, const int* sl
         f[1] = Y / L;
     }
 }
-
-template <int NT>
-__global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) { flow_sweep_body<NT, false>(a, nullptr); }
-// the same sweep on a source bank (its own name: tests/test_isa.py counts the instantiations of flow_kernel)
-template <int NT>
-__global__ __launch_bounds__(64 * kFlowWaves) void flow_slots_kernel(FlowSlotArgs s) { flow_sweep_body<NT, true>(s.a, s.slot); }
 
 }  // namespace tsnet

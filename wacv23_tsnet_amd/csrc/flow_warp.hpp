@@ -73,28 +73,22 @@ __global__ __launch_bounds__(256) void l2norm_split_kernel(const float* __restri
 // flow, fused with the mean over sources.  NHWC makes every neighbour a contiguous C-float row:
 // the "gather" is four fully coalesced row reads per (target, source).
 struct WarpArgs {
-    const float* src;    // (K*SB, h, w, C): (source s, driving frame b) reads image s*SB + b % SB
+    const float* src;    // (slots, h, w, C): (source s, driving frame b) reads image slot[s*B + b]
     const float* flow;   // (K*B, P, 2)
     float* out;          // (B, P, C)
+    const int* slot;     // [K*B] device, the slot table (flow_args.hpp)
     int B, K, h, w, C;
-    int SB;              // source-batch extent: B, or 1 for one source set shared by the batch
 };
-// source bank (warp_mean_slots_kernel): (source s, driving frame b) reads image slot[s*B + b] of a.src; a.SB is not read.  Its own block:
-// warp_mean_kernel keeps its argument layout, and its ISA, to the instruction.
-struct WarpSlotArgs { WarpArgs a; const int* slot; };
 
-// i0, stride: the thread's first element and the grid's stride, read from blockIdx / blockDim / gridDim by the KERNEL (where the compiler
-// knows the workgroup size is uniform: read here, warp_mean_kernel's prologue grows by the partial-workgroup case)
-template <bool SL>
-__device__ __forceinline__ void warp_mean_body(const WarpArgs& a, const int* slot, size_t i0, size_t stride) {
+__global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
     const int P = a.h * a.w;
     const int c4n = a.C >> 2;
     const size_t total = (size_t)a.B * P * c4n;
-    for (size_t i = i0; i < total; i += stride) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const int c = (int)(i % c4n) * 4;
         const size_t bp = i / c4n;
         const int b = (int)(bp / P), p = (int)(bp - (size_t)b * P);
-        const int bs = b % a.SB;
         float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int s = 0; s < a.K; ++s) {
             const int n = s * a.B + b;
@@ -106,7 +100,7 @@ __device__ __forceinline__ void warp_mean_body(const WarpArgs& a, const int* slo
             const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
             const float wnw = (x1 - ix) * (y1 - iy), wne = (ix - x0) * (y1 - iy);
             const float wsw = (x1 - ix) * (iy - y0), wse = (ix - x0) * (iy - y0);
-            const float* base = a.src + ((size_t)(SL ? slot[n] : s * a.SB + bs) * P) * a.C + c;
+            const float* base = a.src + ((size_t)a.slot[n] * P) * a.C + c;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             const bool xin0 = x0 >= 0 && x0 < a.w, xin1 = x1 >= 0 && x1 < a.w;
             const bool yin0 = y0 >= 0 && y0 < a.h, yin1 = y1 >= 0 && y1 < a.h;
@@ -124,13 +118,6 @@ __device__ __forceinline__ void warp_mean_body(const WarpArgs& a, const int* slo
         sum.x /= kf; sum.y /= kf; sum.z /= kf; sum.w /= kf;
         *reinterpret_cast<float4*>(a.out + ((size_t)b * P + p) * a.C + c) = sum;
     }
-}
-
-__global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
-    warp_mean_body<false>(a, nullptr, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
-}
-__global__ __launch_bounds__(256) void warp_mean_slots_kernel(WarpSlotArgs s) {
-    warp_mean_body<true>(s.a, s.slot, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 }  // namespace tsnet

@@ -66,24 +66,20 @@ __global__ __launch_bounds__(256) void in_stats_partial_kernel(StatsArgs a) {
     }
 }
 
-// The same reduction fused with an addition: y[n] = x[n (or its source image, x_sb)] + add[n % add_nmod], statistics of y.  FuseNet's first convolution is split at
+// The same reduction fused with an addition: y[n] = x[slot[n]] + add[n % add_nmod], statistics of y.  FuseNet's first convolution is split at
 // the channel concat (TSNet.py:195-197: cat(src_fea, tar_fea) -> conv): the per-source half is computed once per source set
 // (tsnet_set_sources, cached in clip mode), the shared target half once per driving frame; this kernel joins them and produces the
 // InstanceNorm statistics of the sum.  One-shot forward and clip mode run the SAME kernels in the same order: bit-identical results.
 struct AddStatsArgs {
-    const float* x;      // (N / add_nmod * x_sb, HW, C): image n reads x[n / add_nmod * x_sb + n % add_nmod % x_sb] (x_sb = add_nmod: x[n])
+    const float* x;      // (slots, HW, C): image n reads x[slot[n]]
+    const int* slot;     // [N] device, the slot table (flow_args.hpp); n is fixed per workgroup: one scalar load
     const float* add;    // (add_nmod, HW, C)
     float* y;            // (N, HW, C)
     double* part;        // (N, S, C, 2)
     int HW, C, S, rows_per_split, add_nmod;
-    int x_sb;            // source-batch extent of x: add_nmod, or 1 when the images n with one n / add_nmod share one image of x
 };
-// source bank (add_stats_slots_kernel): image n reads x[slot[n]]; a.x_sb is not read.  Its own block, as FlowSlotArgs (flow_args.hpp).
-struct AddStatsSlotArgs { AddStatsArgs a; const int* slot; };
 
-// SL: x's image comes from the slot table -- n is fixed per workgroup: one scalar load
-template <bool SL>
-__device__ __forceinline__ void add_stats_partial_body(const AddStatsArgs& a, const int* slot) {
+__global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) {
     __shared__ double red[256 * 8];
     const int cq_total = a.C >> 2;
     const int cols = cq_total < 256 ? cq_total : 256;
@@ -99,7 +95,7 @@ __device__ __forceinline__ void add_stats_partial_body(const AddStatsArgs& a, co
     if (rg < R && cq < cq_total) {
         const size_t cb = (size_t)cq * 4;
         const int nb = n % a.add_nmod;
-        const float* bx = a.x + ((size_t)(SL ? slot[n] : n / a.add_nmod * a.x_sb + nb % a.x_sb) * a.HW) * a.C + cb;
+        const float* bx = a.x + ((size_t)a.slot[n] * a.HW) * a.C + cb;
         const float* ba = a.add + ((size_t)nb * a.HW) * a.C + cb;
         float* by = a.y + ((size_t)n * a.HW) * a.C + cb;
         for (int r = r0 + rg; r < r1; r += R) {
@@ -129,9 +125,6 @@ __device__ __forceinline__ void add_stats_partial_body(const AddStatsArgs& a, co
         for (int e = 0; e < 4; ++e) { o[e * 2] = tsm[e]; o[e * 2 + 1] = tsq[e]; }
     }
 }
-
-__global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) { add_stats_partial_body<false>(a, nullptr); }
-__global__ __launch_bounds__(256) void add_stats_slots_kernel(AddStatsSlotArgs s) { add_stats_partial_body<true>(s.a, s.slot); }
 
 // stage 2: alpha = 1/sqrt(var+eps), beta = -mean*alpha  (the x*alpha+beta form ATen's CPU
 // batch-norm transform uses), one thread per (n, c).
@@ -252,39 +245,35 @@ __global__ __launch_bounds__(256) void norm_act_kernel(NormActArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// FuseNet tail: zbar[b,p,:] = (1/K) * sum_i ( cat(src_fea[i*SB+b%SB], tar_fea[b])[p,:] + IN(y2[i*B+b])[p,:] )
+// FuseNet tail: zbar[b,p,:] = (1/K) * sum_i ( cat(src_fea[slot[i*B+b]], tar_fea[b])[p,:] + IN(y2[i*B+b])[p,:] )
 // The 1x1 `fuse_net.conv` that follows is linear, so it is applied once to the mean
 // (mean_i conv(z_i)+bias == conv(mean_i z_i)+bias).
 struct FuseTailArgs {
-    const float* src_fea;   // (K*SB, P, C1): (source s, driving frame b) reads image s*SB + b % SB
+    const float* src_fea;   // (slots, P, C1): (source s, driving frame b) reads image slot[s*B + b]
     const float* tar_fea;   // (B, P, C1)
     const float* y2;        // (K*B, P, 2*C1)
     const float* alpha;     // (K*B * 2*C1)
     const float* beta;
     float* zbar;            // (B, P, 2*C1)
+    const int* slot;        // [K*B] device, the slot table (flow_args.hpp)
     int B, K, P, C1;
-    int SB;                 // source-batch extent: B, or 1 for one source set shared by the batch
 };
-// source bank (fuse_resid_mean_slots_kernel): (source s, driving frame b) reads image slot[s*B + b] of a.src_fea; a.SB is not read
-struct FuseTailSlotArgs { FuseTailArgs a; const int* slot; };
 
-// i0, stride: as warp_mean_body's (flow_warp.hpp)
-template <bool SL>
-__device__ __forceinline__ void fuse_resid_mean_body(const FuseTailArgs& a, const int* slot, size_t i0, size_t stride) {
+__global__ __launch_bounds__(256) void fuse_resid_mean_kernel(FuseTailArgs a) {
     const int C = 2 * a.C1;
     const int c4n = C >> 2;
     const size_t total = (size_t)a.B * a.P * c4n;
-    for (size_t i = i0; i < total; i += stride) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const int c = (int)(i % c4n) * 4;
         const size_t bp = i / c4n;                  // b*P + p
         const int b = (int)(bp / a.P);
         const int p = (int)(bp - (size_t)b * a.P);
-        const int bs = b % a.SB;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int s = 0; s < a.K; ++s) {
             const int n = s * a.B + b;
             float4 xr;
-            if (c < a.C1) xr = *reinterpret_cast<const float4*>(a.src_fea + ((size_t)(SL ? slot[n] : s * a.SB + bs) * a.P + p) * a.C1 + c);
+            if (c < a.C1) xr = *reinterpret_cast<const float4*>(a.src_fea + ((size_t)a.slot[n] * a.P + p) * a.C1 + c);
             else          xr = *reinterpret_cast<const float4*>(a.tar_fea + ((size_t)b * a.P + p) * a.C1 + (c - a.C1));
             const float4 y = *reinterpret_cast<const float4*>(a.y2 + ((size_t)n * a.P + p) * C + c);
             const float4 al = *reinterpret_cast<const float4*>(a.alpha + (size_t)n * C + c);
@@ -300,14 +289,7 @@ __device__ __forceinline__ void fuse_resid_mean_body(const FuseTailArgs& a, cons
     }
 }
 
-__global__ __launch_bounds__(256) void fuse_resid_mean_kernel(FuseTailArgs a) {
-    fuse_resid_mean_body<false>(a, nullptr, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
-}
-__global__ __launch_bounds__(256) void fuse_resid_mean_slots_kernel(FuseTailSlotArgs s) {
-    fuse_resid_mean_body<true>(s.a, s.slot, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
-}
-
-// The slot table of a source bank forward: up to kSlotFill entries per launch, passed by value and written with ordinary vector stores.
+// The slot table of a forward: up to kSlotFill entries per launch, passed by value and written with ordinary vector stores.
 // Stream-ordered by construction -- no host buffer outlives the call that enqueues it.
 constexpr int kSlotFill = 64;
 struct SlotFillArgs { int* dst; int n; int v[kSlotFill]; };
