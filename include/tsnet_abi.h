@@ -17,7 +17,8 @@
  * tsnet_face_adapt_apply, tsnet_smooth_keypoints -- the face loader's key-point preparation of a cross-identity pair; tsnet_bank_capacity,
  * tsnet_bank_put, tsnet_forward_bank -- the source bank; tsnet_op_flow_k_slots, tsnet_op_warp_k_slots, tsnet_op_add_stats_slots,
  * tsnet_op_fuse_tail_slots -- its kernels one at a time; tsnet_forward_u8, tsnet_set_sources_u8, tsnet_forward_target_u8, tsnet_bank_put_u8,
- * tsnet_forward_bank_u8, tsnet_op_pack_input_u8, tsnet_prepare_frames_u8 -- compact (byte) inputs.
+ * tsnet_forward_bank_u8, tsnet_op_pack_input_u8, tsnet_prepare_frames_u8 -- compact (byte) inputs; tsnet_paste_frames -- generated frames
+ * back into the video frames.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -450,6 +451,31 @@ int tsnet_prepare_frames_u8(const unsigned char* frames, int F, int h, int w, in
                             const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
                             const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
                             int oh, int ow, int pad_top, int pad_left, int OH, int OW, unsigned char* out, void* stream);
+
+/* The way back of tsnet_prepare_frames: the generated frames resized to the crop box they came from and put back into the full frames.  Per frame
+ * f, in Pillow's terms (default bicubic filter, 8 bits per channel):
+ *     g = Image.fromarray(gen[f]).crop((sx0, sy0, sx1, sy1)).resize((x1 - x0, y1 - y0))
+ *     m = None if mask is None else Image.fromarray(mask[f], "L").crop((sx0, sy0, sx1, sy1)).resize((x1 - x0, y1 - y0))
+ *     frame_f.paste(g, (x0, y0), m)               # in place
+ * reproduced byte for byte, with these three behaviours of Pillow:
+ *   - crop, then resize: the resampling window clamps to the source rectangle (sx0, sy0, sx1, sy1), never to the rest of gen;
+ *   - clipped paste: the box may leave the frame; exactly box ∩ frame is written, destination pixel (X, Y) gets resized pixel (X - x0, Y - y0);
+ *     a box entirely outside the frame writes nothing, launches nothing and returns 0;
+ *   - masked paste (paste_mask_L), per byte with a = frame, b = resized gen, m = resized mask: t = b * m + a * (255 - m) + 128,
+ *     out = (t + (t >> 8)) >> 8 (a at m = 0, b at m = 255).  The mask is one channel and goes through the same tables and rounding as a
+ *     colour channel: the horizontal pass first, rounded to bytes, then the vertical pass.
+ * gen: (F,GH,GW,3) device bytes, RGB interleaved (what tsnet_demo_postprocess writes); mask: (F,GH,GW) device bytes or NULL (plain paste);
+ * frames: (F,h,w,3) device bytes, RGB interleaved, written in place.  gen and mask must NOT overlap frames (not checked).  The x tables are those
+ * of (sx1 - sx0 -> x1 - x0), the y tables of (sy1 - sy0 -> y1 - y0): DEVICE ints from tsnet_bicubic_table; an axis that keeps its size is
+ * skipped, its tables are not read (may be NULL) and its taps are not looked at.  One kernel on `stream` over box ∩ frame: no allocation, no
+ * synchronisation.
+ * TSNET_ERR_ARG (message in tsnet_op_last_error, nothing written): F < 1; gen or frames NULL; an empty box; a source rectangle that is empty or not
+ * inside GH x GW; taps that are not tsnet_bicubic_taps of the axis' size pair; a missing table of an axis that is not skipped; a vertical
+ * reduction too steep for the kernel's 112-row buffer (about 256 -> 9 rows and beyond). */
+int tsnet_paste_frames(const unsigned char* gen, const unsigned char* mask, int F, int GH, int GW, int sx0, int sy0, int sx1, int sy1,
+                       const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                       const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                       unsigned char* frames, int h, int w, int x0, int y0, int x1, int y1, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,10 @@ and smoothed over the clip (raster.face_driving_keypoints), then drawn from the 
 
 `--compact` hands the runner the compact form of every input -- image bytes before the mean subtraction, class maps, byte masks (a quarter of the
 bytes and less) -- and must write the same files, byte for byte.
+
+`--paste-back` also puts every generated frame back into the full video frame at the clip's crop box on the device (FrameLoader.paste_face) and
+writes "<i>_<name>_full.png".  The goldens hold key points and the cropped source regions only, no driving frames, so the frames pasted into are
+synthetic (a gradient of the clip's frame size); the tool says so.
 """
 import argparse
 import os
@@ -53,6 +57,13 @@ def synthetic_face_keypoints(n_frames: int, seed: int = 0) -> np.ndarray:
         ang = np.linspace(np.pi, -np.pi, 8, endpoint=False)
         out[f, 60:68] = np.stack([cx + 0.28 * s * np.cos(ang), cy + 0.6 * s - op * s * np.sin(ang)], 1)
     return np.round(out)
+
+
+def synthetic_frames(n: int, h: int, w: int) -> np.ndarray:
+    """(n,h,w,3) uint8: a colour gradient standing in for the video frames that are not at hand"""
+    y, x = np.mgrid[0:h, 0:w]
+    a = np.stack([x * 255 // max(w - 1, 1), y * 255 // max(h - 1, 1), (x + y) * 255 // max(w + h - 2, 1)], 2).astype(np.uint8)
+    return np.ascontiguousarray(np.broadcast_to(a, (n, h, w, 3)))
 
 
 GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
@@ -98,6 +109,8 @@ def main():
                     "the driving labels are adapted to the subject's face proportions and smoothed as the reference's loader does")
     ap.add_argument("--compact", action="store_true", help="compact inputs: image bytes, class maps and byte masks, widened by the engine on load "
                     "(tsnet_*_u8); the files written equal those of a run without the flag")
+    ap.add_argument("--paste-back", action="store_true", help="paste every generated frame into a full video frame at the clip's crop box on the "
+                    "device and write <i>_<name>_full.png; the frames pasted into are synthetic (no driving frames are stored with the goldens)")
     args = ap.parse_args()
     if args.drive and not args.clip:
         ap.error("--drive needs --clip (the subject)")
@@ -176,9 +189,15 @@ def main():
         print(f"[demo_clip] driving labels of {args.drive} adapted to {args.clip}: {tar_lbl.shape[0]} frames (crop {dcrop}, brush {dbw}) in {(time.perf_counter() - t0) * 1e3:.2f} ms")
         tar_lbl, tar_box, name = tar_lbl[:F], tar_box[:F], f"{args.clip}_by_{args.drive}"
     runner = demo.ClipRunner(model, src_img, [src_lbl[i:i + 1] for i in range(K)], [src_box[i:i + 1] for i in range(K)], batch=args.batch)
-    frames = runner.run(tar_lbl, tar_box, out_dir=args.out, name=name)
+    paste = {}
+    if args.paste_back:
+        fw, fh = tuple(fmeta["frame_size"]) if args.clip else (640, 480)
+        min_y, max_y, min_x, max_x = (int(v) for v in crop)
+        paste = dict(paste_into=synthetic_frames(F, fh, fw), paste_box=(min_x, min_y, max_x, max_y))
+        print(f"[demo_clip] --paste-back: pasting into SYNTHETIC {fw} x {fh} frames (a gradient; only key points are at hand) at box {paste['paste_box']}")
+    frames = runner.run(tar_lbl, tar_box, out_dir=args.out, name=name, **paste)
     print(f"[demo_clip] {demo.RESIZE_NOTE}")
-    print(f"[demo_clip] {frames.shape[0]} frames written to {args.out} (crop {crop}, brush {bw}); rasterisation of {F + K} frames: {t_raster * 1e3:.2f} ms on the first call; "
+    print(f"[demo_clip] {frames.shape[0]} {'full ' if args.paste_back else ''}frames written to {args.out} (crop {crop}, brush {bw}); rasterisation of {F + K} frames: {t_raster * 1e3:.2f} ms on the first call; "
           f"steady state " + ", ".join(f"{k} {v * 1e3:.2f} ms" for k, v in t_steps.items()) + f" = {sum(t_steps.values()) / (F + K) * 1e3:.3f} ms per frame")
 
     # ---- the demo-shaped figure: B = 1, n_blocks = 4, K = 3, clip mode, post-processing included, frames stay on the device

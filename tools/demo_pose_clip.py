@@ -9,6 +9,10 @@ reachable from this image, so the generator is randomly initialised and goes thr
 path is the real one.
 
     python tools/demo_pose_clip.py --out gpurun_out/demo_pose --frames 16
+
+`--paste-back` also puts the 128 x 256 picture of every generated frame (without resize_square's bars) back into the full video frame at the
+clip's crop box on the device (FrameLoader.paste_pose) and writes "<i>_<name>_full.png".  Only key points are at hand, so the frames pasted into
+are synthetic (a gradient of the clip's frame size); the tool says so.
 """
 import argparse
 import os
@@ -84,6 +88,8 @@ def main():
                     "tests/golden/g9_raster_pose.npz: 00110 or 00164) instead of the synthetic dancer; the frames' pixels stay synthetic")
     ap.add_argument("--compact", action="store_true", help="compact inputs: image bytes, class maps (one byte per pixel instead of 25 floats) and "
                     "byte masks, widened by the engine on load (tsnet_*_u8); the files written equal those of a run without the flag")
+    ap.add_argument("--paste-back", action="store_true", help="paste every generated frame into a full video frame at the clip's crop box on the "
+                    "device and write <i>_<name>_full.png; the frames pasted into are synthetic (only key points are at hand)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -124,8 +130,16 @@ def main():
     src_byte = [(torch.rand((1, 3, 256, 256), generator=g) * 256.0).floor().clamp(max=255.0) for _ in range(K)]
     src_img = [b.to(torch.uint8) if args.compact else b - torch.from_numpy(demo.IMG_MEAN).view(1, 3, 1, 1) for b in src_byte]
     runner = demo.ClipRunner(model, src_img, [lbl[i:i + 1] for i in range(K)], [box[i:i + 1] for i in range(K)], batch=args.batch)
-    frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_pose")
-    print(f"[demo_pose_clip] {frames.shape[0]} frames written to {args.out} (crop {tuple(crop)}, classes present {present}); "
+    paste = {}
+    if args.paste_back:
+        y, x = np.mgrid[0:size[1], 0:size[0]]
+        grad = np.stack([x * 255 // (size[0] - 1), y * 255 // (size[1] - 1), (x + y) * 255 // (size[0] + size[1] - 2)], 2).astype(np.uint8)
+        paste = dict(paste_into=np.ascontiguousarray(np.broadcast_to(grad, (F,) + grad.shape)), paste_box=tuple(int(v) for v in crop),
+                     paste_src_box=(64, 0, 192, 256))
+        print(f"[demo_pose_clip] --paste-back: pasting into SYNTHETIC {size[0]} x {size[1]} frames (a gradient; only key points are at hand) "
+              f"at box {paste['paste_box']}, source rectangle {paste['paste_src_box']}")
+    frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_pose", **paste)
+    print(f"[demo_pose_clip] {frames.shape[0]} {'full ' if args.paste_back else ''}frames written to {args.out} (crop {tuple(crop)}, classes present {present}); "
           f"labels of {F + K} frames from the key points: {t_raster * 1e3:.2f} ms")
 
     nb = min(args.batch, F)                                      # driving frames per step: groups of the clip's frames, wrapping around

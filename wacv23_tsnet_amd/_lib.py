@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "tsnet_op_flow_k_slots", "tsnet_op_warp_k_slots", "tsnet_op_add_stats_slots", "tsnet_op_fuse_tail_slots",
     "tsnet_forward_u8", "tsnet_set_sources_u8", "tsnet_forward_target_u8", "tsnet_bank_put_u8", "tsnet_forward_bank_u8",
     "tsnet_op_pack_input_u8", "tsnet_prepare_frames_u8",
+    "tsnet_paste_frames",
 )
 
 
@@ -141,6 +142,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.tsnet_forward_bank_u8.argtypes = [_vp, _ip, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]
         lib.tsnet_op_pack_input_u8.argtypes = [pp, pp, pp] + [C.c_int] * 8 + [_fp, _fp, _vp, _vp, _vp, _vp]
         lib.tsnet_prepare_frames_u8.argtypes = [_vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_vp, _vp]
+    if hasattr(lib, "tsnet_paste_frames"):       # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_paste_frames.argtypes = [_vp, _vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] + [C.c_int] * 6 + [_vp]
     return lib
 
 

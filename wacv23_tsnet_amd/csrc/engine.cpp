@@ -42,6 +42,7 @@
 #include "face_adapt.hpp"
 #include "flow_warp.hpp"
 #include "frames.hpp"
+#include "paste.hpp"
 #include "head_conv.hpp"
 #include "norm_elementwise.hpp"
 #include "pack_weights.hpp"
@@ -2315,6 +2316,39 @@ int tsnet_prepare_frames_u8(const unsigned char* frames, int F, int h, int w, in
     OP_BEGIN
     prepare_frames_any(frames, F, h, w, x0, y0, x1, y1, xfirst, xcount, xcoef, xtaps, yfirst, ycount, ycoef, ytaps, oh, ow, pad_top, pad_left, OH, OW,
                        nullptr, out, true, stream);
+    OP_END
+}
+
+int tsnet_paste_frames(const unsigned char* gen, const unsigned char* mask, int F, int GH, int GW, int sx0, int sy0, int sx1, int sy1,
+                       const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
+                       const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
+                       unsigned char* frames, int h, int w, int x0, int y0, int x1, int y1, void* stream) {
+    OP_BEGIN
+    if (!gen || !frames) throw ArgError("paste_frames: null tensor");
+    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("paste_frames: bad frame shape");
+    if (GH < 1 || GW < 1 || (double)GH * GW * 3 >= 2147483647.0) throw ArgError("paste_frames: bad shape of the generated frames");
+    if (sx0 < 0 || sy0 < 0 || sx1 <= sx0 || sy1 <= sy0 || sx1 > GW || sy1 > GH) throw ArgError("paste_frames: the source rectangle is empty or not inside the generated frame");
+    if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000 || x0 > 1000000 || y0 > 1000000)
+        throw ArgError("paste_frames: empty or absurd box");
+    const int cw = sx1 - sx0, ch = sy1 - sy0, ow = x1 - x0, oh = y1 - y0;
+    if (ow != cw && (!xfirst || !xcount || !xcoef)) throw ArgError("paste_frames: the horizontal pass needs its tables");
+    if (oh != ch && (!yfirst || !ycount || !ycoef)) throw ArgError("paste_frames: the vertical pass needs its tables");
+    if (ow != cw && xtaps != bicubic_taps(cw, ow)) throw ArgError("paste_frames: xtaps is not tsnet_bicubic_taps(sx1 - sx0, x1 - x0)");
+    if (oh != ch && ytaps != bicubic_taps(ch, oh)) throw ArgError("paste_frames: ytaps is not tsnet_bicubic_taps(sy1 - sy0, y1 - y0)");
+    // the rows of the horizontal pass a tile keeps: frames_row_span's bound, and never more than the source rectangle has
+    auto span = [&](int t) { const int s = frames_row_span(ch, oh, t); return s > ch ? ch : s; };
+    int th = kFrTileH;
+    while (th > 1 && span(th) > kFrRows) th >>= 1;
+    if (span(th) > kFrRows) throw ArgError("paste_frames: vertical reduction too steep (more than 112 source rows under one output row)");
+    const int rx0 = x0 < 0 ? 0 : x0, ry0 = y0 < 0 ? 0 : y0, rx1 = x1 > w ? w : x1, ry1 = y1 > h ? h : y1;
+    if (rx0 >= rx1 || ry0 >= ry1) return TSNET_OK;                   // Image.paste: a box outside the frame writes nothing
+    const int gy = (ry1 - ry0 + th - 1) / th;
+    if (gy > 65535) throw ArgError("paste_frames: region too tall");
+    PasteArgs a{gen, mask, frames, xfirst, xcount, xcoef, yfirst, ycount, ycoef, GH, GW, sx0, sy0, cw, ch, h, w, x0, y0, ow, oh, rx0, ry0, rx1, ry1, xtaps, ytaps, th};
+    const dim3 grid((rx1 - rx0 + kFrTileW - 1) / kFrTileW, gy, F);
+    if (mask) hipLaunchKernelGGL(paste_frames_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(paste_frames_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    check_launch("paste_frames");
     OP_END
 }
 

@@ -139,7 +139,9 @@ class ClipRunner:
         in slots 0 .. K-1 of the engine's source bank (`tsnet_bank_put`, `tsnet_forward_bank`) and re-encodes slot i alone;
       * sources and driving frames may be COMPACT (uint8: image bytes before the mean subtraction, class maps, 0 / 1 masks; `img_mean` is what the
         float32 images have subtracted) -- per call, either form, the same bytes out: the engine widens them on load (`tsnet_*_u8`);
-      * the three-panel strips and the GIF are written with PIL.
+      * the three-panel strips and the GIF are written with PIL;
+      * `run(..., paste_into=frames, paste_box=...)` resizes every generated frame to the crop box it came from and pastes it into the full
+        video frame on the device (`FrameLoader.paste`), and returns / writes the full frames.
     model: a wacv23_tsnet_amd.model.TSNet on the GPU.
 
     The runner OWNS an engine -- a second copy of the packed weights (~350 MB for the 67 M-parameter net) plus an arena for `batch` frames on the device.
@@ -246,10 +248,37 @@ class ClipRunner:
         """one driving frame (1,L,H,W), (1,H,W) -> (H,W,3) uint8 RGB on the device"""
         return self.frames(tar_lbl, tar_bbox)[0]
 
-    def run(self, tar_lbls: torch.Tensor, tar_bboxs: torch.Tensor, out_dir: str = None, tar_imgs: torch.Tensor = None, name: str = "clip"):
-        """tar_lbls (F,L,H,W), tar_bboxs (F,H,W); returns the generated frames (F,H,W,3) uint8 (host).  With out_dir: strips + GIF."""
+    def run(self, tar_lbls: torch.Tensor, tar_bboxs: torch.Tensor, out_dir: str = None, tar_imgs: torch.Tensor = None, name: str = "clip",
+            paste_into=None, paste_box=None, paste_src_box=None, paste_mask=None):
+        """tar_lbls (F,L,H,W), tar_bboxs (F,H,W); returns the generated frames (F,H,W,3) uint8 (host).  With out_dir: strips + GIF.
+        paste_into: (F,h,w,3) uint8 video frames, tensor or array -- every group's bytes are resized to paste_box = (x0, y0, x1, y1) (the crop box
+        the clip was loaded with; it may leave the frame) and pasted into its frames on the device (`FrameLoader.paste`: Pillow's resize + paste,
+        byte for byte); paste_src_box: the part of a generated frame that holds picture (pose: (64, 0, 192, 256)), None = all of it; paste_mask:
+        (F,H,W) uint8, None = plain paste.  `run` then returns the full frames (F,h,w,3) uint8 (host), a copy -- paste_into is left as it is --
+        and out_dir also gets them as "{i:06d}_{name}_full.png"; strips and GIF are written from the generated bytes as without it."""
         import os
-        groups = [self.frames(tar_lbls[i:i + self.batch], tar_bboxs[i:i + self.batch]) for i in range(0, tar_lbls.shape[0], self.batch)]
+        n = tar_lbls.shape[0]
+        full = None
+        if paste_into is not None:
+            from .frames import FrameLoader
+            if paste_box is None:
+                raise ValueError("paste_into needs paste_box")
+            dev = self.src_img[0].device
+            ld = FrameLoader(dev, lib=self.eng.lib)
+            full = ld._u8(paste_into, "frames to paste into", 4)
+            if full.shape[0] != n or (paste_mask is not None and paste_mask.shape[0] != n):
+                raise ValueError(f"{n} driving frames, {full.shape[0]} frames to paste into")
+            host = full
+            full = host.to(dev).contiguous()
+            if full.data_ptr() == host.data_ptr():                  # already on the device: paste into a copy
+                full = full.clone()
+        groups = []
+        for i in range(0, n, self.batch):
+            g = self.frames(tar_lbls[i:i + self.batch], tar_bboxs[i:i + self.batch])
+            if full is not None:
+                ld.paste(g, full[i:i + self.batch], paste_box, src_box=paste_src_box,
+                         mask=None if paste_mask is None else paste_mask[i:i + self.batch], inplace=True)
+            groups.append(g)
         out = torch.cat(groups).cpu().numpy()
         if out_dir:
             os.makedirs(out_dir, exist_ok=True)
@@ -264,4 +293,11 @@ class ClipRunner:
                     tar_rgb = np.repeat(m[:, :, None], 3, axis=2)
                 strips.append(save_strip(src_rgb, tar_rgb, out[i], os.path.join(out_dir, f"{i:06d}_{name}.png")))
             save_gif(strips, os.path.join(out_dir, f"{name}.gif"))
-        return out
+        if full is None:
+            return out
+        full = full.cpu().numpy()
+        if out_dir:
+            from PIL import Image
+            for i in range(full.shape[0]):
+                Image.fromarray(full[i], "RGB").save(os.path.join(out_dir, f"{i:06d}_{name}_full.png"))
+        return full

@@ -7,6 +7,10 @@ uint8 frames go to the device once (3 bytes per pixel) and one kernel (csrc/fram
 resampler is integer arithmetic on coefficient tables; the tables are built on the host in Pillow's operation order (`bicubic_table`, a few hundred
 doubles per axis), so the tensors EQUAL the reference's, byte for byte before the mean subtraction (tests/test_frames.py).
 
+The way back is here too: `FrameLoader.paste` resizes generated frames (the bytes `DemoPostprocessor` returns) to the crop box they came from and
+pastes them into the full frames (csrc/paste.hpp, `tsnet_paste_frames`) -- Pillow's `crop().resize()` + `Image.paste()`, mask included, byte
+for byte (tests/test_paste_frames.py).
+
 Decoding PNG / JPEG files stays with PIL on the host; the training loaders' random crop / scale / flip are out of scope."""
 from __future__ import annotations
 
@@ -143,6 +147,71 @@ class FrameLoader:
     def pose(self, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """The pose loader's image: crop = (xs, ys, xe, ye) as raster.pose_crop_coords returns it; 128 x 256, then padded to 256 x 256."""
         return self.prepare(frames, crop, img_size, square=True, mean=mean, as_bytes=as_bytes)
+
+    # ------------------------------------------------------------------------------------------------------------------ the way back
+    def _u8(self, t, what: str, ndim: int) -> torch.Tensor:
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(t))
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != ndim or (ndim == 4 and t.shape[3] != 3):
+            want = "(F,h,w,3)" if ndim == 4 else "(F,h,w)"
+            raise ValueError(f"expected uint8 {what} of shape {want}, got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+        return t
+
+    def paste(self, gen, frames, box: Sequence[int], src_box: Optional[Sequence[int]] = None, mask=None, inplace: bool = False) -> torch.Tensor:
+        """Generated frames back into the video (`tsnet_paste_frames`, csrc/paste.hpp): per frame f, byte for byte,
+            g = Image.fromarray(gen[f]).crop(src_box).resize((x1 - x0, y1 - y0)); frame_f.paste(g, (x0, y0), m)
+        with m the mask through the same crop and resize, or None.  gen: (F,GH,GW,3) uint8 RGB as `DemoPostprocessor` returns it; frames:
+        (F,h,w,3) uint8 RGB; box: (x0, y0, x1, y1) in frame coordinates, it may leave the frame (Pillow clips the paste; outside, nothing is
+        written); src_box: the part of gen that holds picture, None = all of it; mask: (F,GH,GW) uint8, 255 = gen, 0 = frame (Pillow's
+        paste_mask_L blend in between).  Tensors or arrays; what is on the host is uploaded.  Returns the frames on the device: a clone, or with
+        inplace=True `frames` itself when it already is a contiguous tensor on the device.  gen / mask must not share memory with frames."""
+        g = self._u8(gen, "generated frames", 4)
+        fr = self._u8(frames, "frames", 4)
+        m = None if mask is None else self._u8(mask, "mask", 3)
+        F, GH, GW, _ = g.shape
+        if fr.shape[0] != F:
+            raise ValueError(f"{F} generated frames, {fr.shape[0]} frames to paste into")
+        if m is not None and tuple(m.shape) != (F, GH, GW):
+            raise ValueError(f"mask of shape {tuple(m.shape)}, generated frames {tuple(g.shape)}")
+        x0, y0, x1, y1 = (int(v) for v in box)
+        sx0, sy0, sx1, sy1 = (0, 0, GW, GH) if src_box is None else (int(v) for v in src_box)
+        if x1 <= x0 or y1 <= y0:
+            raise ValueError(f"empty box {tuple(box)}")
+        if not (0 <= sx0 < sx1 <= GW and 0 <= sy0 < sy1 <= GH):
+            raise ValueError(f"source rectangle {(sx0, sy0, sx1, sy1)} is empty or not inside the {GW} x {GH} generated frames")
+        g = g.to(self.device).contiguous()
+        m = None if m is None else m.to(self.device).contiguous()
+        out = fr.to(self.device).contiguous()
+        if not inplace and out.data_ptr() == fr.data_ptr():
+            out = out.clone()
+        h, w = out.shape[1], out.shape[2]
+        ow, oh = x1 - x0, y1 - y0
+        xt, xtaps = self._axis(sx1 - sx0, ow)
+        yt, ytaps = self._axis(sy1 - sy0, oh)
+        p = lambda t, off: t.data_ptr() + 4 * off
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        with ctx:
+            rc = self.lib.tsnet_paste_frames(g.data_ptr(), None if m is None else m.data_ptr(), F, GH, GW, sx0, sy0, sx1, sy1,
+                                             p(xt, 0), p(xt, ow), p(xt, 2 * ow), xtaps, p(yt, 0), p(yt, oh), p(yt, 2 * oh), ytaps,
+                                             out.data_ptr(), h, w, x0, y0, x1, y1, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tsnet_paste_frames failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep = [g, m]                                          # alive until the stream has consumed them
+        return out
+
+    def paste_face(self, gen, frames, crop: Sequence[int], mask=None, inplace: bool = False) -> torch.Tensor:
+        """The inverse of `face`: crop = [min_y, max_y, min_x, max_x]; the whole generated image goes back into that box."""
+        min_y, max_y, min_x, max_x = crop
+        return self.paste(gen, frames, (min_x, min_y, max_x, max_y), mask=mask, inplace=inplace)
+
+    def paste_pose(self, gen, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mask=None, inplace: bool = False) -> torch.Tensor:
+        """The inverse of `pose`: crop = (xs, ys, xe, ye); the img_size picture between resize_square's bars goes back into that box."""
+        gh, gw = (gen.shape[1], gen.shape[2]) if hasattr(gen, "shape") and len(gen.shape) == 4 else (0, 0)
+        S = max(int(img_size[0]), int(img_size[1]))
+        if (gh, gw) != (S, S):
+            raise ValueError(f"expected generated frames of {S} x {S} (img_size {tuple(img_size)} padded square), got {gw} x {gh}")
+        px, py = (S - int(img_size[0])) // 2, (S - int(img_size[1])) // 2
+        return self.paste(gen, frames, crop, src_box=(px, py, px + int(img_size[0]), py + int(img_size[1])), mask=mask, inplace=inplace)
 
 
 class _Null:
