@@ -18,7 +18,7 @@
  * tsnet_bank_put, tsnet_forward_bank -- the source bank; tsnet_op_flow_k_slots, tsnet_op_warp_k_slots, tsnet_op_add_stats_slots,
  * tsnet_op_fuse_tail_slots -- its kernels one at a time; tsnet_forward_u8, tsnet_set_sources_u8, tsnet_forward_target_u8, tsnet_bank_put_u8,
  * tsnet_forward_bank_u8, tsnet_op_pack_input_u8, tsnet_prepare_frames_u8 -- compact (byte) inputs; tsnet_paste_frames -- generated frames
- * back into the video frames.
+ * back into the video frames; tsnet_prepare_frames_boxes, tsnet_prepare_frames_boxes_u8, tsnet_paste_frames_boxes -- the same with a box per frame.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -476,6 +476,38 @@ int tsnet_paste_frames(const unsigned char* gen, const unsigned char* mask, int 
                        const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
                        const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
                        unsigned char* frames, int h, int w, int x0, int y0, int x1, int y1, void* stream);
+
+/* A box per frame: the reference's FaceDatasetTest(fix_crop_pos=False) crops every frame by the box of its own landmarks
+ * (dataset/dataset_video_face.py:303-308, 317-320, 348-353, 390-393).  The three entries are the siblings of tsnet_prepare_frames,
+ * tsnet_prepare_frames_u8 and tsnet_paste_frames with the same semantics per frame -- frame f of a call has the bytes of the single-box entry
+ * called on frame f alone with box f -- and with the box, and so the coefficient tables, belonging to the frame.  Fixed per call: the output
+ * geometry of the prepare (oh, ow, pad_top, pad_left, OH, OW) and the source rectangle of the paste.
+ *   boxes: (F, 8) ints, row f = {x0, y0, x1, y1, xoff, xtaps, yoff, ytaps}.  xoff / yoff: the offset, in ints, of that axis' table inside `pool`,
+ *          where a table lies as first[n_out] | count[n_out] | coef[n_out * taps] (tsnet_bicubic_table's three outputs one after the other);
+ *          xtaps / ytaps its row stride.  An axis that keeps its size is skipped: its offset (-1 by convention) and taps are not looked at.
+ *          For the prepare the x table is that of (x1 - x0 -> ow), the y table of (y1 - y0 -> oh); for the paste those of
+ *          (sx1 - sx0 -> x1 - x0) and (sy1 - sy0 -> y1 - y0).
+ *   boxes_host / boxes_dev: the same (F, 8) ints twice.  The HOST copy is validated and sizes the grid; the DEVICE copy, which the caller
+ *          uploaded, is what the kernel reads.  The device copy is trusted as the tables are: the kernel range-checks what it takes from it
+ *          (pool offsets against pool_len, frame reads and paste stores against h, w), so a device copy that differs gives wrong pixels, never
+ *          an access outside the tensors.
+ *   pool, pool_len: DEVICE ints and their number; may be NULL / 0 when every axis of every frame is skipped.
+ * One kernel on `stream` for all F frames: no allocation, no synchronisation.  The tile height is one per launch, the smallest any frame of the
+ * call needs (integer arithmetic: the tile shape changes no byte).  The paste's grid covers the largest box ∩ frame of the call; a frame whose
+ * box lies outside is left as it is while the others are pasted, and when every box is outside nothing is launched and 0 returned.
+ * TSNET_ERR_ARG, all checked on the host copy before anything is launched, so that nothing is written for ANY frame; the message names the frame
+ * ("... frame 3: ..."): an empty box, or one beyond the single-box entry's bounds; taps that are not tsnet_bicubic_taps of that frame's size
+ * pair; an offset of -1 on an axis that does not keep its size; a table that ends beyond the pool; a vertical reduction too steep for the
+ * 112-row buffer.  Without a frame to name: F < 1, a NULL tensor or descriptor, and the per-call geometry errors of the single-box entries. */
+int tsnet_prepare_frames_boxes(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev,
+                               const int* pool, int pool_len, int oh, int ow, int pad_top, int pad_left, int OH, int OW,
+                               const float* mean_bgr, float* out, void* stream);
+int tsnet_prepare_frames_boxes_u8(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev,
+                                  const int* pool, int pool_len, int oh, int ow, int pad_top, int pad_left, int OH, int OW,
+                                  unsigned char* out, void* stream);
+int tsnet_paste_frames_boxes(const unsigned char* gen, const unsigned char* mask, int F, int GH, int GW, int sx0, int sy0, int sx1, int sy1,
+                             const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len,
+                             unsigned char* frames, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,11 @@ bytes and less) -- and must write the same files, byte for byte.
 `--paste-back` also puts every generated frame back into the full video frame at the clip's crop box on the device (FrameLoader.paste_face) and
 writes "<i>_<name>_full.png".  The goldens hold key points and the cropped source regions only, no driving frames, so the frames pasted into are
 synthetic (a gradient of the clip's frame size); the tool says so.
+
+`--track-crop` crops every frame by the box of its own landmarks, as the reference's FaceDatasetTest(fix_crop_pos=False) does: source and driving
+labels are drawn at each frame's own crop (raster.crop_coords_clip, FaceRasteriser.clip_labels(crop=(F,4))), with `--drive` the driving key points
+are made relative to their own crops before adaptation and smoothing (face_driving_keypoints(fix_crop_pos=False)), and with `--paste-back` every
+generated frame goes back at its own box (ClipRunner.run(paste_boxes=...), one launch per group).  It composes with --drive, --compact and --batch.
 """
 import argparse
 import os
@@ -81,11 +86,16 @@ def clip_keypoints(clip: str):
     return kp, meta
 
 
-def crossid_labels(rs, subject_kps, driving_kps, size=(256, 256), compact=False):
+def crossid_labels(rs, subject_kps, driving_kps, size=(256, 256), compact=False, track_crop=False):
     """Driving labels of a cross-identity pair, the reference loader's way (dataset/dataset_video_face.py:335-398): the driving clip's key points
     adapted to the subject's face and smoothed (host code of the library), drawn at the driving crop's resolution from the fractional points,
     resized, one-hot.  rs: a raster.FaceRasteriser (its device and library are used throughout).  Key points in frame coordinates.
-    Returns (labels (F,2,H,W), bbox (F,H,W), driving crop, bw); compact: the class map (F,H,W) and the mask as uint8."""
+    Returns (labels (F,2,H,W), bbox (F,H,W), driving crop, bw); compact: the class map (F,H,W) and the mask as uint8.
+    track_crop: every frame by its own crop (fix_crop_pos=False); the driving crop returned is then (F,4)."""
+    if track_crop:
+        pts, crops, bw = raster.face_driving_keypoints(subject_kps, driving_kps, lib=rs.lib, fix_crop_pos=False)
+        lbl, box, _ = rs.clip_labels(list(pts), size, crop=crops, relative=True, compact=compact, bw=bw)
+        return lbl, box, crops, bw
     pts, crop, bw = raster.face_driving_keypoints(subject_kps, driving_kps, lib=rs.lib)
     edges, bbox, _, _ = rs.rasterise(list(pts), crop, relative=True)
     cls, box = demo.resize_label(edges, size, lib=rs.lib), demo.resize_label(bbox, size, lib=rs.lib)
@@ -111,6 +121,8 @@ def main():
                     "(tsnet_*_u8); the files written equal those of a run without the flag")
     ap.add_argument("--paste-back", action="store_true", help="paste every generated frame into a full video frame at the clip's crop box on the "
                     "device and write <i>_<name>_full.png; the frames pasted into are synthetic (no driving frames are stored with the goldens)")
+    ap.add_argument("--track-crop", action="store_true", help="a crop per frame from that frame's own landmarks (the reference's fix_crop_pos=False) "
+                    "for source and driving labels; with --paste-back, a paste box per frame")
     args = ap.parse_args()
     if args.drive and not args.clip:
         ap.error("--drive needs --clip (the subject)")
@@ -161,6 +173,12 @@ def main():
         td = time.perf_counter()
         t_steps = {"fit (host) + draw (device)": tb - ta, "resize 2 maps": tc - tb, "one-hot": td - tc}
     assert torch.equal(e2, edges) and torch.equal(b2, bbox)
+    tcrops = None
+    if args.track_crop:                                          # the labels again, every frame at its own crop
+        tcrops = raster.crop_coords_clip(kp)
+        lbl, box, _ = rs.clip_labels(list(kp), crop=tcrops, compact=args.compact)
+        print(f"[demo_clip] --track-crop: {len(tcrops)} crops of {sorted({int(c[1] - c[0]) for c in tcrops})} pixels, "
+              f"corners moving by up to {int(np.abs(tcrops - tcrops[0]).max())} pixels")
     if args.clip:
         # the real source frames: the cropped regions of the clip's demo images (tests/golden/g11_frames_<clip>.npz) through the device frame
         # loader, and the labels of the SAME frame indices, so that pixels and labels belong together
@@ -169,10 +187,17 @@ def main():
         fmeta = json.loads(str(zf["meta"]))
         x0, y0, x1, y1 = fmeta["box"]
         assert [y0, y1, x0, x1] == list(crop)
-        img = frames_mod.FrameLoader(dev).face(zf["crops"], [0, y1 - y0, 0, x1 - x0], as_bytes=args.compact)
+        src_kp = kp_all[[int(i) for i in fmeta["frames"]][:K]]
+        if args.track_crop:
+            # each source frame by its own crop; the stored pixels are the clip-crop's region only, so what a frame's crop has outside it reads 0
+            scrops = raster.crop_coords_clip(src_kp)
+            img = frames_mod.FrameLoader(dev).face(zf["crops"][:K], scrops - np.array([y0, y0, x0, x0]), as_bytes=args.compact)
+            src_lbl, src_box, _ = rs.clip_labels(list(src_kp), crop=scrops, compact=args.compact)
+        else:
+            img = frames_mod.FrameLoader(dev).face(zf["crops"], [0, y1 - y0, 0, x1 - x0], as_bytes=args.compact)
+            se, sb, _, _ = rs.rasterise(list(src_kp), crop)
+            src_lbl, src_box = onehot(demo.resize_label(se)), mask(demo.resize_label(sb))
         src_img = [img[i:i + 1] for i in range(K)]
-        se, sb, _, _ = rs.rasterise(list(kp_all[[int(i) for i in fmeta["frames"]][:K]]), crop)
-        src_lbl, src_box = onehot(demo.resize_label(se)), mask(demo.resize_label(sb))
     else:
         # noise frames of BYTE values, as every decoded frame is: the float form is byte - IMG_MEAN, the compact form the byte
         g = torch.Generator().manual_seed(1)
@@ -183,10 +208,10 @@ def main():
     if args.drive:
         # the whole driving clip is prepared (the moving average runs over the clip), then the first F frames drive
         t0 = time.perf_counter()
-        tar_lbl, tar_box, dcrop, dbw = crossid_labels(rs, kp_all, clip_keypoints(args.drive)[0], compact=args.compact)
+        tar_lbl, tar_box, dcrop, dbw = crossid_labels(rs, kp_all, clip_keypoints(args.drive)[0], compact=args.compact, track_crop=args.track_crop)
         torch.cuda.synchronize()
         F = min(F, tar_lbl.shape[0])
-        print(f"[demo_clip] driving labels of {args.drive} adapted to {args.clip}: {tar_lbl.shape[0]} frames (crop {dcrop}, brush {dbw}) in {(time.perf_counter() - t0) * 1e3:.2f} ms")
+        print(f"[demo_clip] driving labels of {args.drive} adapted to {args.clip}: {tar_lbl.shape[0]} frames (crop {'per frame' if args.track_crop else dcrop}, brush {dbw}) in {(time.perf_counter() - t0) * 1e3:.2f} ms")
         tar_lbl, tar_box, name = tar_lbl[:F], tar_box[:F], f"{args.clip}_by_{args.drive}"
     runner = demo.ClipRunner(model, src_img, [src_lbl[i:i + 1] for i in range(K)], [src_box[i:i + 1] for i in range(K)], batch=args.batch)
     paste = {}
@@ -194,7 +219,11 @@ def main():
         fw, fh = tuple(fmeta["frame_size"]) if args.clip else (640, 480)
         min_y, max_y, min_x, max_x = (int(v) for v in crop)
         paste = dict(paste_into=synthetic_frames(F, fh, fw), paste_box=(min_x, min_y, max_x, max_y))
-        print(f"[demo_clip] --paste-back: pasting into SYNTHETIC {fw} x {fh} frames (a gradient; only key points are at hand) at box {paste['paste_box']}")
+        if args.track_crop:                                      # the driving frames' own crops, (x0, y0, x1, y1)
+            pcrops = np.asarray(dcrop if args.drive else tcrops[K:])[:F]
+            paste = dict(paste_into=paste["paste_into"], paste_boxes=pcrops[:, [2, 0, 3, 1]])
+        print(f"[demo_clip] --paste-back: pasting into SYNTHETIC {fw} x {fh} frames (a gradient; only key points are at hand) at "
+              + (f"{F} boxes, one per frame, from {tuple(int(v) for v in paste['paste_boxes'][0])}" if args.track_crop else f"box {paste['paste_box']}"))
     frames = runner.run(tar_lbl, tar_box, out_dir=args.out, name=name, **paste)
     print(f"[demo_clip] {demo.RESIZE_NOTE}")
     print(f"[demo_clip] {frames.shape[0]} {'full ' if args.paste_back else ''}frames written to {args.out} (crop {crop}, brush {bw}); rasterisation of {F + K} frames: {t_raster * 1e3:.2f} ms on the first call; "

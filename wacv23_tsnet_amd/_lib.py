@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "tsnet_forward_u8", "tsnet_set_sources_u8", "tsnet_forward_target_u8", "tsnet_bank_put_u8", "tsnet_forward_bank_u8",
     "tsnet_op_pack_input_u8", "tsnet_prepare_frames_u8",
     "tsnet_paste_frames",
+    "tsnet_prepare_frames_boxes", "tsnet_prepare_frames_boxes_u8", "tsnet_paste_frames_boxes",
 )
 
 
@@ -144,6 +145,10 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.tsnet_prepare_frames_u8.argtypes = [_vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_vp, _vp]
     if hasattr(lib, "tsnet_paste_frames"):       # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
         lib.tsnet_paste_frames.argtypes = [_vp, _vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] + [C.c_int] * 6 + [_vp]
+    if hasattr(lib, "tsnet_paste_frames_boxes"): # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_prepare_frames_boxes.argtypes = [_vp] + [C.c_int] * 3 + [_vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_fp, _vp, _vp]
+        lib.tsnet_prepare_frames_boxes_u8.argtypes = [_vp] + [C.c_int] * 3 + [_vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_vp, _vp]
+        lib.tsnet_paste_frames_boxes.argtypes = [_vp, _vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int] + [_vp, C.c_int, C.c_int, _vp]
     return lib
 
 

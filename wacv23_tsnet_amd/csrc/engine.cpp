@@ -2352,4 +2352,100 @@ int tsnet_paste_frames(const unsigned char* gen, const unsigned char* mask, int 
     OP_END
 }
 
+// ---- a box per frame: HOST descriptors {x0, y0, x1, y1, xoff, xtaps, yoff, ytaps} are checked here, all of them before anything is launched
+static std::string box_frame(const char* who, int f) { return std::string(who) + ": frame " + std::to_string(f) + ": "; }
+
+// one axis of frame f: n_in -> n_out with its table at `off` in a pool of pool_len ints
+static void check_box_axis(const char* who, int f, const char* axis, int n_in, int n_out, int off, int taps, const int* pool, int pool_len) {
+    if (n_in == n_out) return;                                       // skipped: off and taps are not looked at
+    if (off < 0) throw ArgError(box_frame(who, f) + "the " + axis + " pass needs its table (offset " + std::to_string(off) + ")");
+    if (taps != bicubic_taps(n_in, n_out))
+        throw ArgError(box_frame(who, f) + axis + " taps are not tsnet_bicubic_taps(" + std::to_string(n_in) + ", " + std::to_string(n_out) + ")");
+    if (!pool || (long long)off + (long long)n_out * (2 + (long long)taps) > (long long)pool_len)
+        throw ArgError(box_frame(who, f) + "the " + axis + " table at offset " + std::to_string(off) + " ends beyond the pool of " + std::to_string(pool_len) + " ints");
+}
+
+static void prepare_frames_boxes_any(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev, const int* pool,
+                                     int pool_len, int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, void* out, bool u8,
+                                     void* stream) {
+    const char* who = "prepare_frames_boxes";
+    if (!frames || !out || (!u8 && !mean_bgr) || !boxes_host || !boxes_dev) throw ArgError("prepare_frames_boxes: null tensor");
+    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("prepare_frames_boxes: bad frame shape");
+    if (pool_len < 0) throw ArgError("prepare_frames_boxes: negative pool length");
+    if (oh < 1 || ow < 1 || pad_top < 0 || pad_left < 0 || pad_top + oh > OH || pad_left + ow > OW || (double)OH * OW >= 2147483647.0 / 4)
+        throw ArgError("prepare_frames_boxes: the resized image and its padding do not fit the output");
+    int th = kFrTileH;                                               // one tile height per launch: the smallest any frame needs
+    for (int f = 0; f < F; ++f) {
+        const int* d = boxes_host + (size_t)f * kFrDesc;
+        const int x0 = d[0], y0 = d[1], x1 = d[2], y1 = d[3];
+        if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000)
+            throw ArgError(box_frame(who, f) + "empty or absurd crop box");
+        const int cw = x1 - x0, ch = y1 - y0;
+        check_box_axis(who, f, "horizontal", cw, ow, d[4], d[5], pool, pool_len);
+        check_box_axis(who, f, "vertical", ch, oh, d[6], d[7], pool, pool_len);
+        while (th > 1 && frames_row_span(ch, oh, th) > kFrRows) th >>= 1;
+        if (frames_row_span(ch, oh, th) > kFrRows) throw ArgError(box_frame(who, f) + "vertical reduction too steep (more than 112 taps)");
+    }
+    const int gy = (OH + th - 1) / th;
+    if (gy > 65535) throw ArgError("prepare_frames_boxes: output too tall");
+    FrameBoxArgs b{{frames, static_cast<float*>(out), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h, w, 0, 0, 0, 0, ow, oh, 0, 0, pad_top, pad_left, OH, OW, th,
+                    {u8 ? 0.f : mean_bgr[0], u8 ? 0.f : mean_bgr[1], u8 ? 0.f : mean_bgr[2]}}, boxes_dev, pool, pool_len};
+    const dim3 grid((OW + kFrTileW - 1) / kFrTileW, gy, F);
+    if (u8) hipLaunchKernelGGL(prepare_frames_boxes_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
+    else hipLaunchKernelGGL(prepare_frames_boxes_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
+    check_launch("prepare_frames_boxes");
+}
+
+int tsnet_prepare_frames_boxes(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len,
+                               int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream) {
+    OP_BEGIN
+    prepare_frames_boxes_any(frames, F, h, w, boxes_host, boxes_dev, pool, pool_len, oh, ow, pad_top, pad_left, OH, OW, mean_bgr, out, false, stream);
+    OP_END
+}
+
+int tsnet_prepare_frames_boxes_u8(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len,
+                                  int oh, int ow, int pad_top, int pad_left, int OH, int OW, unsigned char* out, void* stream) {
+    OP_BEGIN
+    prepare_frames_boxes_any(frames, F, h, w, boxes_host, boxes_dev, pool, pool_len, oh, ow, pad_top, pad_left, OH, OW, nullptr, out, true, stream);
+    OP_END
+}
+
+int tsnet_paste_frames_boxes(const unsigned char* gen, const unsigned char* mask, int F, int GH, int GW, int sx0, int sy0, int sx1, int sy1,
+                             const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len, unsigned char* frames, int h, int w, void* stream) {
+    OP_BEGIN
+    const char* who = "paste_frames_boxes";
+    if (!gen || !frames || !boxes_host || !boxes_dev) throw ArgError("paste_frames_boxes: null tensor");
+    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("paste_frames_boxes: bad frame shape");
+    if (GH < 1 || GW < 1 || (double)GH * GW * 3 >= 2147483647.0) throw ArgError("paste_frames_boxes: bad shape of the generated frames");
+    if (sx0 < 0 || sy0 < 0 || sx1 <= sx0 || sy1 <= sy0 || sx1 > GW || sy1 > GH)
+        throw ArgError("paste_frames_boxes: the source rectangle is empty or not inside the generated frame");
+    if (pool_len < 0) throw ArgError("paste_frames_boxes: negative pool length");
+    const int cw = sx1 - sx0, ch = sy1 - sy0;
+    int th = kFrTileH, rw = 0, rh = 0;                               // one tile height per launch; the largest box ∩ frame
+    for (int f = 0; f < F; ++f) {
+        const int* d = boxes_host + (size_t)f * kFrDesc;
+        const int x0 = d[0], y0 = d[1], x1 = d[2], y1 = d[3];
+        if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000 || x0 > 1000000 || y0 > 1000000)
+            throw ArgError(box_frame(who, f) + "empty or absurd box");
+        const int ow = x1 - x0, oh = y1 - y0;
+        check_box_axis(who, f, "horizontal", cw, ow, d[4], d[5], pool, pool_len);
+        check_box_axis(who, f, "vertical", ch, oh, d[6], d[7], pool, pool_len);
+        auto span = [&](int t) { const int s = frames_row_span(ch, oh, t); return s > ch ? ch : s; };
+        while (th > 1 && span(th) > kFrRows) th >>= 1;
+        if (span(th) > kFrRows) throw ArgError(box_frame(who, f) + "vertical reduction too steep (more than 112 source rows under one output row)");
+        const int rx0 = x0 < 0 ? 0 : x0, ry0 = y0 < 0 ? 0 : y0, rx1 = x1 > w ? w : x1, ry1 = y1 > h ? h : y1;
+        if (rx0 < rx1 && ry0 < ry1) { rw = rx1 - rx0 > rw ? rx1 - rx0 : rw; rh = ry1 - ry0 > rh ? ry1 - ry0 : rh; }
+    }
+    if (rw == 0) return TSNET_OK;                                    // Image.paste: every box is outside its frame, nothing is written
+    const int gy = (rh + th - 1) / th;
+    if (gy > 65535) throw ArgError("paste_frames_boxes: region too tall");
+    PasteBoxArgs b{{gen, mask, frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, GH, GW, sx0, sy0, cw, ch, h, w, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, th},
+                   boxes_dev, pool, pool_len};
+    const dim3 grid((rw + kFrTileW - 1) / kFrTileW, gy, F);
+    if (mask) hipLaunchKernelGGL(paste_frames_boxes_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
+    else hipLaunchKernelGGL(paste_frames_boxes_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
+    check_launch("paste_frames_boxes");
+    OP_END
+}
+
 }  // extern "C"

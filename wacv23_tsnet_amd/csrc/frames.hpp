@@ -90,8 +90,10 @@ __device__ __forceinline__ int fr_clip8(int acc) { const int v = acc >> kBicubic
 // between the passes never reaches memory.  Every index that comes from a table is range-checked: a bad table gives wrong pixels, not a fault.
 // U8: store the resized byte itself (a.out holds bytes, a.mean is not read) -- the compact image of pack_input_u8_kernel, which subtracts the mean
 // on load: (float)byte - mean is then the float store below, bit for bit.
+// mean: a.mean where the kernel's arguments hold it (the per-frame-box kernels run the body on a copy of theirs, and a plane-indexed array in a
+// copy would live in scratch).
 template <bool U8>
-__device__ __forceinline__ void prepare_frames_body(const FrameArgs& a) {
+__device__ __forceinline__ void prepare_frames_body(const FrameArgs& a, const float* mean) {
     __shared__ unsigned char hbuf[kFrRows * kFrRowBytes];
     const int tid = threadIdx.x;
     const int X0 = blockIdx.x * kFrTileW, Y0 = blockIdx.y * a.th, f = blockIdx.z;
@@ -166,11 +168,59 @@ __device__ __forceinline__ void prepare_frames_body(const FrameArgs& a) {
         const int p = 2 - c;                                      // RGB -> BGR
         const size_t o = (((size_t)f * 3 + p) * a.OH + Y) * a.OW + X;
         if (U8) reinterpret_cast<unsigned char*>(a.out)[o] = (unsigned char)v;
-        else a.out[o] = (float)v - a.mean[p];
+        else a.out[o] = (float)v - mean[p];
     }
 }
 
-__global__ __launch_bounds__(256) void prepare_frames_kernel(FrameArgs a) { prepare_frames_body<false>(a); }
-__global__ __launch_bounds__(256) void prepare_frames_u8_kernel(FrameArgs a) { prepare_frames_body<true>(a); }
+__global__ __launch_bounds__(256) void prepare_frames_kernel(FrameArgs a) { prepare_frames_body<false>(a, a.mean); }
+__global__ __launch_bounds__(256) void prepare_frames_u8_kernel(FrameArgs a) { prepare_frames_body<true>(a, a.mean); }
+
+// ---------------------------------------------------------------------------------------------------------------- a box per frame
+// FaceDatasetTest(fix_crop_pos=False) crops every frame by the box of its own landmarks (dataset/dataset_video_face.py:303-308, 317-320).  The box,
+// and with it the coefficient tables, then belongs to the frame: a launch takes (F, 8) ints, one row per frame,
+//   {x0, y0, x1, y1, xoff, xtaps, yoff, ytaps}
+// and one POOL of tables; xoff / yoff are the offsets, in ints, of that axis' table inside the pool, where it lies as
+// first[n_out] | count[n_out] | coef[n_out * taps] (-1: the axis keeps its size, no table).  The table of a size pair is the single-box table of
+// that pair and the passes are the body above, so frame f of a launch has the bytes of the single-box kernel on frame f with box f.
+constexpr int kFrDesc = 8;               // ints of a frame's descriptor
+constexpr int kFrBoxMax = 1 << 24;       // what the kernels accept as a box size or (paste) corner; the launchers stop at 10^6
+
+// The three tables of an axis from its pool offset, or false when they do not lie inside the pool.
+__device__ __forceinline__ bool fr_pool_axis(const int* pool, int pool_len, int off, int n_out, int taps, const int*& first, const int*& count, const int*& coef) {
+    if (off < 0 || taps < 1 || (long long)off + (long long)n_out * (2 + (long long)taps) > (long long)pool_len) return false;
+    first = pool + off; count = first + n_out; coef = count + n_out;
+    return true;
+}
+
+struct FrameBoxArgs {
+    FrameArgs g;                         // what a launch fixes: frames, out, the output geometry, th, mean; its tables and box are not read
+    const int* desc;                     // (F, kFrDesc) DEVICE
+    const int* pool;
+    int pool_len;
+};
+
+// The grid and the body of prepare_frames_body; the frame's descriptor is read once, through an address that depends on blockIdx.z alone (scalar
+// loads), and everything taken from it is range-checked before the body sees it: a bad descriptor gives a black frame, not an access outside the
+// pool or the frames (the body checks every frame read against h, w).
+template <bool U8>
+__device__ __forceinline__ void prepare_frames_boxes_body(const FrameBoxArgs& b) {
+    const int* d = b.desc + (size_t)blockIdx.z * kFrDesc;
+    FrameArgs a = b.g;
+    const int x0 = d[0], y0 = d[1];
+    a.cw = (int)((unsigned)d[2] - (unsigned)x0); a.ch = (int)((unsigned)d[3] - (unsigned)y0);
+    // a box that starts below -2^24 (it is at most 2^24 wide) or beyond 2^30 (h * w * 3 < 2^31) lies outside the frame: clamped, it reads the
+    // same zeros, and bx0 + cx cannot overflow
+    a.bx0 = x0 < -kFrBoxMax ? -kFrBoxMax : (x0 > (1 << 30) ? (1 << 30) : x0);
+    a.by0 = y0 < -kFrBoxMax ? -kFrBoxMax : (y0 > (1 << 30) ? (1 << 30) : y0);
+    a.xtaps = d[5]; a.ytaps = d[7];
+    bool ok = a.cw >= 1 && a.ch >= 1 && a.cw <= kFrBoxMax && a.ch <= kFrBoxMax;
+    if (ok && a.ow != a.cw) ok = fr_pool_axis(b.pool, b.pool_len, d[4], a.ow, a.xtaps, a.xfirst, a.xcount, a.xcoef);
+    if (ok && a.oh != a.ch) ok = fr_pool_axis(b.pool, b.pool_len, d[6], a.oh, a.ytaps, a.yfirst, a.ycount, a.ycoef);
+    if (!ok) { a.ow = 0; a.oh = 0; }                              // no content: the body stores byte 0 everywhere and reads no table
+    prepare_frames_body<U8>(a, b.g.mean);
+}
+
+__global__ __launch_bounds__(256) void prepare_frames_boxes_kernel(FrameBoxArgs b) { prepare_frames_boxes_body<false>(b); }
+__global__ __launch_bounds__(256) void prepare_frames_boxes_u8_kernel(FrameBoxArgs b) { prepare_frames_boxes_body<true>(b); }
 
 }  // namespace tsnet

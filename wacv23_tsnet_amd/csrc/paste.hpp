@@ -125,4 +125,39 @@ __device__ __forceinline__ void paste_frames_body(const PasteArgs& a) {
 __global__ __launch_bounds__(256) void paste_frames_kernel(PasteArgs a) { paste_frames_body<false>(a); }
 __global__ __launch_bounds__(256) void paste_frames_mask_kernel(PasteArgs a) { paste_frames_body<true>(a); }
 
+// ---------------------------------------------------------------------------------------------------------------- a box per frame
+// The way back of prepare_frames_boxes_kernel: frame f is pasted at ITS box, descriptor row f of frames.hpp's layout {x0, y0, x1, y1, xoff, xtaps,
+// yoff, ytaps} with the tables of (source rectangle -> box size) in the pool.  The source rectangle is the launch's.
+struct PasteBoxArgs {
+    PasteArgs g;                         // what a launch fixes: gen, mask, frames, GH, GW, the source rectangle, h, w, th; tables, box and region not read
+    const int* desc;                     // (F, kFrDesc) DEVICE
+    const int* pool;
+    int pool_len;
+};
+
+// grid = (ceil(W / 64), ceil(H / th), F) with W x H the LARGEST box ∩ frame of the launch.  The descriptor is read once, through an address that
+// depends on blockIdx.z alone (scalar loads); the frame's region is computed here from the box and h, w.  A workgroup outside its frame's region
+// -- a smaller region than the grid's, a box outside the frame, or a descriptor that fails a range check -- leaves through the body's first
+// test, which is uniform over the workgroup and comes before the barrier.  A bad descriptor gives wrong (or no) pixels: pool offsets are checked
+// against the pool's length here, every store against h, w in the body.
+template <bool MASK>
+__device__ __forceinline__ void paste_frames_boxes_body(const PasteBoxArgs& b) {
+    const int* d = b.desc + (size_t)blockIdx.z * kFrDesc;
+    PasteArgs a = b.g;
+    a.x0 = d[0]; a.y0 = d[1];
+    a.ow = (int)((unsigned)d[2] - (unsigned)a.x0); a.oh = (int)((unsigned)d[3] - (unsigned)a.y0);
+    a.xtaps = d[5]; a.ytaps = d[7];
+    bool ok = a.ow >= 1 && a.oh >= 1 && a.ow <= kFrBoxMax && a.oh <= kFrBoxMax && a.x0 >= -kFrBoxMax && a.x0 <= kFrBoxMax && a.y0 >= -kFrBoxMax && a.y0 <= kFrBoxMax;
+    if (ok && a.ow != a.cw) ok = fr_pool_axis(b.pool, b.pool_len, d[4], a.ow, a.xtaps, a.xfirst, a.xcount, a.xcoef);
+    if (ok && a.oh != a.ch) ok = fr_pool_axis(b.pool, b.pool_len, d[6], a.oh, a.ytaps, a.yfirst, a.ycount, a.ycoef);
+    if (!ok) { a.x0 = a.y0 = 0; a.ow = a.oh = 0; }                    // an empty region
+    a.rx0 = a.x0 < 0 ? 0 : a.x0; a.ry0 = a.y0 < 0 ? 0 : a.y0;
+    a.rx1 = a.x0 + a.ow > a.w ? a.w : a.x0 + a.ow;
+    a.ry1 = a.y0 + a.oh > a.h ? a.h : a.y0 + a.oh;
+    paste_frames_body<MASK>(a);
+}
+
+__global__ __launch_bounds__(256) void paste_frames_boxes_kernel(PasteBoxArgs b) { paste_frames_boxes_body<false>(b); }
+__global__ __launch_bounds__(256) void paste_frames_boxes_mask_kernel(PasteBoxArgs b) { paste_frames_boxes_body<true>(b); }
+
 }  // namespace tsnet

@@ -141,7 +141,7 @@ class ClipRunner:
         float32 images have subtracted) -- per call, either form, the same bytes out: the engine widens them on load (`tsnet_*_u8`);
       * the three-panel strips and the GIF are written with PIL;
       * `run(..., paste_into=frames, paste_box=...)` resizes every generated frame to the crop box it came from and pastes it into the full
-        video frame on the device (`FrameLoader.paste`), and returns / writes the full frames.
+        video frame on the device (`FrameLoader.paste`), and returns / writes the full frames; `paste_boxes=` (F,4) gives every frame its own box.
     model: a wacv23_tsnet_amd.model.TSNet on the GPU.
 
     The runner OWNS an engine -- a second copy of the packed weights (~350 MB for the 67 M-parameter net) plus an arena for `batch` frames on the device.
@@ -249,20 +249,26 @@ class ClipRunner:
         return self.frames(tar_lbl, tar_bbox)[0]
 
     def run(self, tar_lbls: torch.Tensor, tar_bboxs: torch.Tensor, out_dir: str = None, tar_imgs: torch.Tensor = None, name: str = "clip",
-            paste_into=None, paste_box=None, paste_src_box=None, paste_mask=None):
+            paste_into=None, paste_box=None, paste_src_box=None, paste_mask=None, paste_boxes=None):
         """tar_lbls (F,L,H,W), tar_bboxs (F,H,W); returns the generated frames (F,H,W,3) uint8 (host).  With out_dir: strips + GIF.
         paste_into: (F,h,w,3) uint8 video frames, tensor or array -- every group's bytes are resized to paste_box = (x0, y0, x1, y1) (the crop box
         the clip was loaded with; it may leave the frame) and pasted into its frames on the device (`FrameLoader.paste`: Pillow's resize + paste,
         byte for byte); paste_src_box: the part of a generated frame that holds picture (pose: (64, 0, 192, 256)), None = all of it; paste_mask:
         (F,H,W) uint8, None = plain paste.  `run` then returns the full frames (F,h,w,3) uint8 (host), a copy -- paste_into is left as it is --
-        and out_dir also gets them as "{i:06d}_{name}_full.png"; strips and GIF are written from the generated bytes as without it."""
+        and out_dir also gets them as "{i:06d}_{name}_full.png"; strips and GIF are written from the generated bytes as without it.
+        paste_boxes: (F,4) instead of paste_box, a box per frame (tracking crops, raster.crop_coords_clip in x0, y0, x1, y1 order): every group
+        pastes with its slice of boxes, still one launch per group (`tsnet_paste_frames_boxes`)."""
         import os
         n = tar_lbls.shape[0]
         full = None
+        if paste_box is not None and paste_boxes is not None:
+            raise ValueError("paste_box and paste_boxes: one box for the clip or one per frame, not both")
         if paste_into is not None:
             from .frames import FrameLoader
-            if paste_box is None:
-                raise ValueError("paste_into needs paste_box")
+            if paste_box is None and paste_boxes is None:
+                raise ValueError("paste_into needs paste_box or paste_boxes")
+            if paste_boxes is not None:
+                paste_boxes = FrameLoader._boxes(paste_boxes, n)
             dev = self.src_img[0].device
             ld = FrameLoader(dev, lib=self.eng.lib)
             full = ld._u8(paste_into, "frames to paste into", 4)
@@ -276,7 +282,7 @@ class ClipRunner:
         for i in range(0, n, self.batch):
             g = self.frames(tar_lbls[i:i + self.batch], tar_bboxs[i:i + self.batch])
             if full is not None:
-                ld.paste(g, full[i:i + self.batch], paste_box, src_box=paste_src_box,
+                ld.paste(g, full[i:i + self.batch], paste_box if paste_boxes is None else paste_boxes[i:i + self.batch], src_box=paste_src_box,
                          mask=None if paste_mask is None else paste_mask[i:i + self.batch], inplace=True)
             groups.append(g)
         out = torch.cat(groups).cpu().numpy()

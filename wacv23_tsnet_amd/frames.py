@@ -88,6 +88,10 @@ class FrameLoader:
         self.device = torch.device(device)
         self._tables = {}
         self._keep = []
+        self._pool_host = np.zeros(0, np.int32)                      # the tables of the per-frame-box calls, one after the other
+        self._pool_at = {}                                           # (n_in, n_out) -> (offset in ints, taps)
+        self._pool = None                                            # the device copy; replaced (never written) when the pool grows
+        self._pool_prev = None
 
     def _stream(self) -> Optional[int]:
         return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
@@ -101,12 +105,111 @@ class FrameLoader:
             self._tables[key] = (flat, coef.shape[1])
         return self._tables[key]
 
+    # ------------------------------------------------------------------------------------------------------------------ a box per frame
+    def _pool_axis(self, n_in: int, n_out: int) -> Tuple[int, int]:
+        """(offset, taps) of an axis' table in the pool, appended on first sight; (-1, 0) for an axis that keeps its size"""
+        if n_in == n_out:
+            return -1, 0
+        key = (n_in, n_out)
+        if key not in self._pool_at:
+            first, count, coef = bicubic_table_c(self.lib, n_in, n_out)
+            self._pool_at[key] = (len(self._pool_host), coef.shape[1])
+            self._pool_host = np.concatenate([self._pool_host, first, count, coef.ravel()])
+            self._pool = None
+        return self._pool_at[key]
+
+    def _descriptors(self, boxes: np.ndarray, sizes):
+        """boxes (F,4) x0, y0, x1, y1; sizes(box) -> ((x n_in, x n_out), (y n_in, y n_out)).  Returns (host (F,8) int32, its device copy, the
+        device pool, the pool it replaced or None): rows {x0, y0, x1, y1, xoff, xtaps, yoff, ytaps} as tsnet_*_frames_boxes take them."""
+        rows, at = [], self._pool_at
+        for f, b in enumerate(boxes.tolist()):                       # plain ints: this loop is per frame and per call
+            if b[2] <= b[0] or b[3] <= b[1]:
+                raise ValueError(f"frame {f}: empty box {tuple(b)}")
+            (xi, xo), (yi, yo) = sizes(b)
+            x = (-1, 0) if xi == xo else (at.get((xi, xo)) or self._pool_axis(xi, xo))
+            y = (-1, 0) if yi == yo else (at.get((yi, yo)) or self._pool_axis(yi, yo))
+            rows.append((b[0], b[1], b[2], b[3], x[0], x[1], y[0], y[1]))
+        desc = np.array(rows, dtype=np.int32).reshape(-1, 8)
+        old = None
+        if self._pool is None:                                       # grown: a new device copy; the old one may still be read by an enqueued kernel
+            old, self._pool = self._pool_prev, torch.from_numpy(self._pool_host.copy()).to(self.device)
+            self._pool_prev = self._pool
+        return desc, torch.from_numpy(desc).to(self.device), self._pool, old
+
+    @staticmethod
+    def _boxes(boxes, F: int, order=(0, 1, 2, 3)) -> np.ndarray:
+        b = np.asarray(boxes.cpu() if isinstance(boxes, torch.Tensor) else boxes)
+        if b.ndim != 2 or b.shape[1] != 4:
+            raise ValueError(f"expected (F,4) boxes, got shape {b.shape}")
+        if b.shape[0] != F:
+            raise ValueError(f"{b.shape[0]} boxes for {F} frames")
+        return b.astype(np.int64)[:, list(order)]
+
+    def _prepare_boxes(self, frames, boxes, size, square, mean, as_bytes) -> torch.Tensor:
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
+            raise ValueError(f"expected uint8 frames of shape (F,h,w,3), got {tuple(frames.shape)} {frames.dtype}")
+        fr = frames.to(self.device).contiguous()
+        F, h, w, _ = fr.shape
+        ow, oh = int(size[0]), int(size[1])
+        S = max(ow, oh)
+        OH, OW = (S, S) if square else (oh, ow)
+        pad_top, pad_left = (OH - oh) // 2, (OW - ow) // 2
+        desc, desc_d, pool, old = self._descriptors(self._boxes(boxes, F), lambda b: ((int(b[2] - b[0]), ow), (int(b[3] - b[1]), oh)))
+        m = np.asarray(mean, dtype=np.float32)
+        mean_c = (C.c_float * 3)(float(m[0]), float(m[1]), float(m[2]))
+        out = torch.empty((F, 3, OH, OW), dtype=torch.uint8 if as_bytes else torch.float32, device=self.device)
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        geom = (fr.data_ptr(), F, h, w, desc.ctypes.data, desc_d.data_ptr(), pool.data_ptr(), pool.numel(), oh, ow, pad_top, pad_left, OH, OW)
+        with ctx:
+            if as_bytes:
+                rc = self.lib.tsnet_prepare_frames_boxes_u8(*geom, out.data_ptr(), self._stream())
+            else:
+                rc = self.lib.tsnet_prepare_frames_boxes(*geom, mean_c, out.data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tsnet_prepare_frames_boxes{'_u8' if as_bytes else ''} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep = [fr, desc_d, pool, old]                         # alive until the stream has consumed them
+        return out
+
+    def _paste_boxes(self, gen, frames, boxes, src_box, mask, inplace) -> torch.Tensor:
+        g = self._u8(gen, "generated frames", 4)
+        fr = self._u8(frames, "frames", 4)
+        m = None if mask is None else self._u8(mask, "mask", 3)
+        F, GH, GW, _ = g.shape
+        if fr.shape[0] != F:
+            raise ValueError(f"{F} generated frames, {fr.shape[0]} frames to paste into")
+        if m is not None and tuple(m.shape) != (F, GH, GW):
+            raise ValueError(f"mask of shape {tuple(m.shape)}, generated frames {tuple(g.shape)}")
+        sx0, sy0, sx1, sy1 = (0, 0, GW, GH) if src_box is None else (int(v) for v in src_box)
+        if not (0 <= sx0 < sx1 <= GW and 0 <= sy0 < sy1 <= GH):
+            raise ValueError(f"source rectangle {(sx0, sy0, sx1, sy1)} is empty or not inside the {GW} x {GH} generated frames")
+        desc, desc_d, pool, old = self._descriptors(self._boxes(boxes, F), lambda b: ((sx1 - sx0, int(b[2] - b[0])), (sy1 - sy0, int(b[3] - b[1]))))
+        g = g.to(self.device).contiguous()
+        m = None if m is None else m.to(self.device).contiguous()
+        out = fr.to(self.device).contiguous()
+        if not inplace and out.data_ptr() == fr.data_ptr():
+            out = out.clone()
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        with ctx:
+            rc = self.lib.tsnet_paste_frames_boxes(g.data_ptr(), None if m is None else m.data_ptr(), F, GH, GW, sx0, sy0, sx1, sy1,
+                                                   desc.ctypes.data, desc_d.data_ptr(), pool.data_ptr(), pool.numel(),
+                                                   out.data_ptr(), out.shape[1], out.shape[2], self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tsnet_paste_frames_boxes failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep = [g, m, desc_d, pool, old]                       # alive until the stream has consumed them
+        return out
+
     def prepare(self, frames, box: Sequence[int], size: Tuple[int, int], square: bool = False, mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """frames: (F,h,w,3) uint8 RGB, tensor or array (uploaded once when on the host).  box: (x0, y0, x1, y1) in PIL order; it may leave the
         frame (Image.crop: zeros there).  size: (ow, oh) as Image.resize takes it.  square: resize_square's centred padding with byte 0 to
         max(ow, oh).  Returns (F,3,H,W) float32 on the device: BGR planes of frame.crop(box).resize(size) minus `mean` (B, G, R).
         as_bytes=True (`tsnet_prepare_frames_u8`): the resized bytes themselves, (F,3,H,W) uint8, `mean` not applied -- the image of a compact
-        call (Engine.forward(..., mean=)), a quarter of the size; bytes.float() - mean is the float32 result, bit for bit."""
+        call (Engine.forward(..., mean=)), a quarter of the size; bytes.float() - mean is the float32 result, bit for bit.
+        box may be an (F,4) array-like, one box per frame (`tsnet_prepare_frames_boxes`, still one kernel): frame f then has the bytes of
+        prepare(frames[f:f+1], box[f], ...)."""
+        if np.ndim(box) == 2:
+            return self._prepare_boxes(frames, box, size, square, mean, as_bytes)
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
@@ -141,6 +244,8 @@ class FrameLoader:
 
     def face(self, frames, crop: Sequence[int], size: Tuple[int, int] = (256, 256), mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """The face loader's image: crop = [min_y, max_y, min_x, max_x] as raster.crop_coords returns it (get_crop_coords, not clipped to the frame)."""
+        if np.ndim(crop) == 2:                                       # (F,4): a crop per frame, as raster.crop_coords_clip returns them
+            return self.prepare(frames, self._boxes(crop, len(frames), (2, 0, 3, 1)), size, square=False, mean=mean, as_bytes=as_bytes)
         min_y, max_y, min_x, max_x = crop
         return self.prepare(frames, (min_x, min_y, max_x, max_y), size, square=False, mean=mean, as_bytes=as_bytes)
 
@@ -164,7 +269,10 @@ class FrameLoader:
         (F,h,w,3) uint8 RGB; box: (x0, y0, x1, y1) in frame coordinates, it may leave the frame (Pillow clips the paste; outside, nothing is
         written); src_box: the part of gen that holds picture, None = all of it; mask: (F,GH,GW) uint8, 255 = gen, 0 = frame (Pillow's
         paste_mask_L blend in between).  Tensors or arrays; what is on the host is uploaded.  Returns the frames on the device: a clone, or with
-        inplace=True `frames` itself when it already is a contiguous tensor on the device.  gen / mask must not share memory with frames."""
+        inplace=True `frames` itself when it already is a contiguous tensor on the device.  gen / mask must not share memory with frames.
+        box may be an (F,4) array-like, one box per frame (`tsnet_paste_frames_boxes`, still one kernel); src_box stays one per call."""
+        if np.ndim(box) == 2:
+            return self._paste_boxes(gen, frames, box, src_box, mask, inplace)
         g = self._u8(gen, "generated frames", 4)
         fr = self._u8(frames, "frames", 4)
         m = None if mask is None else self._u8(mask, "mask", 3)
@@ -201,6 +309,8 @@ class FrameLoader:
 
     def paste_face(self, gen, frames, crop: Sequence[int], mask=None, inplace: bool = False) -> torch.Tensor:
         """The inverse of `face`: crop = [min_y, max_y, min_x, max_x]; the whole generated image goes back into that box."""
+        if np.ndim(crop) == 2:
+            return self.paste(gen, frames, self._boxes(crop, len(frames), (2, 0, 3, 1)), mask=mask, inplace=inplace)
         min_y, max_y, min_x, max_x = crop
         return self.paste(gen, frames, (min_x, min_y, max_x, max_y), mask=mask, inplace=inplace)
 

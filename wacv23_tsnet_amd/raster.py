@@ -40,6 +40,12 @@ def crop_coords(keypoints: np.ndarray) -> Tuple[int, int, int, int]:
     return int(y0), int(y0 + side * 2), int(x0), int(x0 + side * 2)
 
 
+def crop_coords_clip(keypoints: Sequence[np.ndarray]) -> np.ndarray:
+    """`crop_coords` of every frame -> (F,4) int64 rows (min_y, max_y, min_x, max_x): the crops of FaceDatasetTest(fix_crop_pos=False)
+    (:303-305, :348-350).  The reference does not smooth them over time, and neither does this."""
+    return np.array([crop_coords(np.asarray(k)) for k in keypoints], dtype=np.int64).reshape(-1, 4)
+
+
 class FaceRasteriser:
     """Edge maps / bounding-box masks of a clip at crop resolution, and one-hot labels, on `device`.
 
@@ -52,16 +58,23 @@ class FaceRasteriser:
     def _stream(self) -> Optional[int]:
         return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
 
-    def rasterise(self, keypoints: Sequence[np.ndarray], crop: Optional[Tuple[int, int, int, int]] = None, relative: bool = False):
+    def rasterise(self, keypoints: Sequence[np.ndarray], crop: Optional[Tuple[int, int, int, int]] = None, relative: bool = False,
+                  bw: Optional[int] = None):
         """keypoints: F arrays (68,2) in frame coordinates.  crop: (min_y, max_y, min_x, max_x); default = crop_coords of the first
         frame (fix_crop_pos=True, :294-299).  relative=True: the points are already relative to `crop` (which must be given) and go to the
         fit untouched -- the way for fractional points such as face_driving_keypoints', where (a + c) - c is not a.
-        Returns (edges (F,h,w) uint8, bbox (F,h,w) uint8, crop, bw)."""
+        bw: the brush width, default max(1, h // 256) of the crop.
+        Returns (edges (F,h,w) uint8, bbox (F,h,w) uint8, crop, bw).
+        crop may be an (F,4) array, a crop per frame (fix_crop_pos=False, `crop_coords_clip`): every frame is drawn at its own crop's size and the
+        result is (edges, bbox, crops, bw) with edges / bbox LISTS of F tensors (h_f, w_f).  bw then defaults to that of the FIRST frame's crop:
+        the reference computes the brush once per clip (:302, :347).  Frames of equal size share one call of the kernels."""
         kp = np.stack([np.asarray(k, dtype=np.float64) for k in keypoints])
         if kp.ndim != 3 or kp.shape[1:] != (68, 2):
             raise ValueError(f"expected F x 68 x 2 key points, got {kp.shape}")
         if relative and crop is None:
             raise ValueError("relative=True: key points relative to a crop need that crop")
+        if crop is not None and np.ndim(crop) == 2:
+            return self._rasterise_crops(kp, crop, relative, bw)
         if crop is None:
             crop = crop_coords(kp[0])
         kp = kp.copy()
@@ -69,7 +82,8 @@ class FaceRasteriser:
             kp[:, :, 0] -= crop[2]                                 # read_keypoints (:497-505)
             kp[:, :, 1] -= crop[0]
         h, w = crop[1] - crop[0], crop[3] - crop[2]
-        bw = max(1, h // 256)                                      # :295
+        if bw is None:
+            bw = max(1, h // 256)                                  # :295
         F = kp.shape[0]
         kp = np.ascontiguousarray(kp)
         # interp_points' Levenberg-Marquardt fits run on the host (34 per frame, microseconds each; csrc/lmfit.hpp reproduces scipy's
@@ -90,6 +104,35 @@ class FaceRasteriser:
         self._keep = (kd, cd)
         return edges, bbox, crop, bw
 
+    @staticmethod
+    def _size_groups(crops: np.ndarray):
+        """{(h, w): [frame indices]} of (F,4) crops, in order of first appearance"""
+        groups = {}
+        for f, c in enumerate(crops):
+            groups.setdefault((int(c[1] - c[0]), int(c[3] - c[2])), []).append(f)
+        return groups
+
+    def _rasterise_crops(self, kp: np.ndarray, crops, relative: bool, bw: Optional[int]):
+        """a crop per frame: the frames of every size go through `rasterise` together and back into frame order"""
+        crops = np.asarray(crops).astype(np.int64)
+        F = kp.shape[0]
+        if crops.shape != (F, 4):
+            raise ValueError(f"expected ({F},4) crops for {F} frames, got {crops.shape}")
+        if bw is None:
+            bw = max(1, int(crops[0, 1] - crops[0, 0]) // 256)      # the first frame's, for the whole clip (:302, :347)
+        kp = kp.copy()
+        if not relative:
+            kp[:, :, 0] -= crops[:, 2, None]                        # read_keypoints(path, None) (:499-507): each frame by its own crop
+            kp[:, :, 1] -= crops[:, 0, None]
+        edges, bbox, keep = [None] * F, [None] * F, []
+        for (h, w), idx in self._size_groups(crops).items():
+            e, b, _, _ = self.rasterise(kp[idx], (0, h, 0, w), relative=True, bw=bw)
+            keep.append(self._keep)
+            for j, f in enumerate(idx):
+                edges[f], bbox[f] = e[j], b[j]
+        self._keep = keep
+        return edges, bbox, crops, bw
+
     def vl2ch(self, labels: torch.Tensor, num_classes: int) -> torch.Tensor:
         """utils/misc.py vl2ch (:50-67): (B,H,W) class indices -> (B,num_classes,H,W) one-hot float32."""
         lab = labels.to(self.device, dtype=torch.float32).contiguous()
@@ -104,14 +147,23 @@ class FaceRasteriser:
         return out
 
     def clip_labels(self, keypoints: Sequence[np.ndarray], size: Tuple[int, int] = (256, 256), crop=None, relative: bool = False,
-                    compact: bool = False):
+                    compact: bool = False, bw: Optional[int] = None):
         """The label tensors of a clip as the model takes them: rasterise, then the loader's resize to `size` (demo.resize_label).
         compact=False: one-hot labels (F,2,H,W) float32 (vl2ch) and masks (F,H,W) float32 0/1.  compact=True: the class map (F,H,W) and the
         mask (F,H,W) as uint8 -- what Engine.forward_target / ClipRunner take as a compact call; no vl2ch, the stem's packing kernel makes
-        the one-hot planes on load.  Returns (labels, masks, crop)."""
+        the one-hot planes on load.  Returns (labels, masks, crop).
+        crop may be an (F,4) array, a crop per frame (see `rasterise`); bw: the brush width, as `rasterise` takes it.  The tensors are the same
+        (F, ...) ones: every frame is resized from its own crop's size, the frames of equal size in one call."""
         from .demo import resize_label
-        edges, bbox, crop, _ = self.rasterise(keypoints, crop, relative)
-        cls, box = resize_label(edges, size, lib=self.lib), resize_label(bbox, size, lib=self.lib)
+        edges, bbox, crop, _ = self.rasterise(keypoints, crop, relative, bw)
+        if isinstance(edges, list):
+            cls = torch.empty((len(edges),) + tuple(size), dtype=torch.float32, device=self.device)
+            box = torch.empty_like(cls)
+            for idx in self._size_groups(crop).values():
+                cls[idx] = resize_label(torch.stack([edges[f] for f in idx]), size, lib=self.lib)
+                box[idx] = resize_label(torch.stack([bbox[f] for f in idx]), size, lib=self.lib)
+        else:
+            cls, box = resize_label(edges, size, lib=self.lib), resize_label(bbox, size, lib=self.lib)
         if compact:
             return cls.to(torch.uint8), box.to(torch.uint8), crop          # exact: the maps hold 0 / 1
         return self.vl2ch(cls, 2), box, crop
@@ -178,14 +230,23 @@ def smooth_keypoints(kps, lib=None) -> np.ndarray:
     return out
 
 
-def face_driving_keypoints(subject_kps, driving_kps, lib=None):
+def face_driving_keypoints(subject_kps, driving_kps, lib=None, fix_crop_pos: bool = True):
     """The driving key points of a cross-identity pair in the order FaceDatasetTest.__getitem__ prepares them (fix_crop_pos=True, as the demo
     runs): each clip is cropped by the crop of its own first frame (:299-308, :344-353), the driving clip is adapted to the subject's face
     proportions (:335, :355) and then smoothed over its frames (:357-379); the subject clip is neither adapted nor smoothed.
     subject_kps, driving_kps: F arrays (68,2) in frame coordinates, as `read_keypoints` returns them.
     Returns (points (F,68,2) float64 relative to the driving crop, driving crop (min_y, max_y, min_x, max_x), bw): what
-    `FaceRasteriser.rasterise(points, crop, relative=True)` takes."""
+    `FaceRasteriser.rasterise(points, crop, relative=True)` takes.
+    fix_crop_pos=False: every frame of each clip is made relative to its OWN crop (read_keypoints(path, None), :306-308, :351-353, :499-507);
+    adaptation and smoothing then run as above.  Returns (points, crops (F,4) of the driving frames, bw of the FIRST driving frame (:347))."""
     sub, drv = _clip_array(subject_kps, "subject").copy(), _clip_array(driving_kps, "driving").copy()
+    if not fix_crop_pos:
+        crops = crop_coords_clip(drv)
+        for kp, c in ((sub, crop_coords_clip(sub)), (drv, crops)):
+            kp[:, :, 0] -= c[:, 2, None]
+            kp[:, :, 1] -= c[:, 0, None]
+        points = smooth_keypoints(FaceAdapter(lib).fit(sub).apply(drv), lib)
+        return points, crops, max(1, int(crops[0, 1] - crops[0, 0]) // 256)
     sub_crop, crop = crop_coords(sub[0]), crop_coords(drv[0])
     for kp, c in ((sub, sub_crop), (drv, crop)):
         kp[:, :, 0] -= c[2]                                        # read_keypoints (:497-505)
