@@ -18,7 +18,8 @@
  * tsnet_bank_put, tsnet_forward_bank -- the source bank; tsnet_op_flow_k_slots, tsnet_op_warp_k_slots, tsnet_op_add_stats_slots,
  * tsnet_op_fuse_tail_slots -- its kernels one at a time; tsnet_forward_u8, tsnet_set_sources_u8, tsnet_forward_target_u8, tsnet_bank_put_u8,
  * tsnet_forward_bank_u8, tsnet_op_pack_input_u8, tsnet_prepare_frames_u8 -- compact (byte) inputs; tsnet_paste_frames -- generated frames
- * back into the video frames; tsnet_prepare_frames_boxes, tsnet_prepare_frames_boxes_u8, tsnet_paste_frames_boxes -- the same with a box per frame.
+ * back into the video frames; tsnet_prepare_frames_boxes, tsnet_prepare_frames_boxes_u8, tsnet_paste_frames_boxes -- the same with a box per frame;
+ * tsnet_face_labels_boxes, tsnet_face_labels_boxes_u8 -- the face labels of a clip with a crop per frame, frames of different sizes in one pass.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -508,6 +509,39 @@ int tsnet_prepare_frames_boxes_u8(const unsigned char* frames, int F, int h, int
 int tsnet_paste_frames_boxes(const unsigned char* gen, const unsigned char* mask, int F, int GH, int GW, int sx0, int sy0, int sx1, int sy1,
                              const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len,
                              unsigned char* frames, int h, int w, void* stream);
+
+/* The face labels of a clip with a crop per frame in one pass over frames of different sizes: what tsnet_raster_face followed by
+ * tsnet_resize_label (once for the edge map, once for the mask) give for frame f alone at its own crop's size, for all F frames at once --
+ * the same operations per pixel in the same order, so frame f has the bits of the single-size entries.  tsnet_face_labels_boxes writes
+ * float32 outputs, tsnet_face_labels_boxes_u8 bytes; both hold 0 / 1.
+ *   keypoints (F,68,2) DEVICE doubles, relative to each frame's crop; curves (F,34,8) DEVICE doubles from tsnet_fit_face_curves on those points.
+ *   labels, masks: (F,OH,OW) DEVICE, the class map (the resized edge map) and the resized bounding-box mask.  Either may be NULL, as in
+ *          tsnet_raster_face; keypoints are needed by the mask only, curves by the class map only.
+ *   bw: the brush, one per call (the reference computes it once per clip).
+ *   desc: (F, 8) ints, row f = {h, w, off, lw_rows, woff_rows, lw_cols, woff_cols, 0}.  h, w: the frame's crop.  off: the byte offset of the
+ *          frame's region of 4 h w bytes in the workspace.  lw_*: the half width of that axis' anti-aliasing Gaussian, -1 when the axis does
+ *          not shrink (h <= OH, w <= OW: no pass), else int(4 sigma + 0.5) with sigma = (in / out - 1) / 2; woff_*: the offset, in doubles, of
+ *          its lw + 1 weights (centre first, scipy's gaussian_filter1d) inside `pool`.  lw = 0 is the single weight 1.0: the pass is skipped.
+ *   desc_host / desc_dev: the same (F, 8) ints twice, the convention of tsnet_prepare_frames_boxes.  The HOST copy is validated and sizes the
+ *          grids; the kernels read the DEVICE copy and range-check what they take from it against workspace_len, pool_len and OH, OW: a device
+ *          copy that differs gives wrong pixels (an unusable row an all-zero frame), never an access outside the tensors.
+ *   pool, pool_len: DEVICE doubles and their number; may be NULL / 0 when no axis of any frame has lw >= 0.
+ *   workspace, workspace_len: DEVICE bytes, 4-byte aligned, the caller's; contents need not be initialised and are not kept between calls.
+ *          [0, 16 F): the 2F {min, max} int pairs of the images; frame f's region at off_f: edge map A | mask A | edge map B | mask B of
+ *          h w bytes each (the rasteriser draws into A, the two Gaussian passes go A -> B -> A).  Regions may lie anywhere behind the pairs.
+ * At most six kernels on `stream` whatever F and however many sizes (fill, edges, rows pass, columns pass, min / max, resize; a pass that no
+ * frame takes is not launched): no allocation, no memset, no copy, no synchronisation.
+ * TSNET_ERR_ARG, all checked on the host copy before anything is enqueued, so that nothing is written for ANY frame.  Without a frame to name:
+ * F < 1 or 2 F > 65535 (the grid's y); both outputs NULL, or a NULL input that an output needs, NULL descriptors or workspace; bw < 1;
+ * OH or OW < 1; a workspace that is misaligned or shorter than the pairs.  Naming the frame ("... frame 3: ..."): h or w < 1 (or > 32767);
+ * lw outside -1 .. 63; lw >= 0 on an axis that does not shrink, or lw that is not int(4 sigma + 0.5) of that size pair; a half-kernel that
+ * ends beyond the pool; a region that overlaps the pairs or another frame's region, or ends beyond the workspace. */
+int tsnet_face_labels_boxes(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev,
+                            const double* pool, int pool_len, int bw, void* workspace, long long workspace_len, int OH, int OW,
+                            float* labels, float* masks, void* stream);
+int tsnet_face_labels_boxes_u8(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev,
+                               const double* pool, int pool_len, int bw, void* workspace, long long workspace_len, int OH, int OW,
+                               unsigned char* labels, unsigned char* masks, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ ABI_SYMBOLS = (
     "tsnet_op_pack_input_u8", "tsnet_prepare_frames_u8",
     "tsnet_paste_frames",
     "tsnet_prepare_frames_boxes", "tsnet_prepare_frames_boxes_u8", "tsnet_paste_frames_boxes",
+    "tsnet_face_labels_boxes", "tsnet_face_labels_boxes_u8",
 )
 
 
@@ -149,6 +150,9 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.tsnet_prepare_frames_boxes.argtypes = [_vp] + [C.c_int] * 3 + [_vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_fp, _vp, _vp]
         lib.tsnet_prepare_frames_boxes_u8.argtypes = [_vp] + [C.c_int] * 3 + [_vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_vp, _vp]
         lib.tsnet_paste_frames_boxes.argtypes = [_vp, _vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int] + [_vp, C.c_int, C.c_int, _vp]
+    if hasattr(lib, "tsnet_face_labels_boxes"):  # absent from an older build opened beside this one (tools/track_labels_bench.py --lib2)
+        for fn in (lib.tsnet_face_labels_boxes, lib.tsnet_face_labels_boxes_u8):
+            fn.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, C.c_int, _vp, _vp, _vp]
     return lib
 
 

@@ -48,6 +48,7 @@
 #include "pack_weights.hpp"
 #include "postproc.hpp"
 #include "raster.hpp"
+#include "track_labels.hpp"
 #include "train_extras.hpp"
 
 using namespace tsnet;
@@ -2445,6 +2446,92 @@ int tsnet_paste_frames_boxes(const unsigned char* gen, const unsigned char* mask
     if (mask) hipLaunchKernelGGL(paste_frames_boxes_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
     else hipLaunchKernelGGL(paste_frames_boxes_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
     check_launch("paste_frames_boxes");
+    OP_END
+}
+
+
+// ---- face labels with a crop per frame (track_labels.hpp): HOST descriptors {h, w, off, lw_rows, woff_rows, lw_cols, woff_cols, 0}, all of them
+// checked here before anything is enqueued
+static void check_label_axis(const char* who, int f, const char* axis, int n_in, int n_out, int lw, int woff, const double* pool, int pool_len) {
+    if (lw < -1 || lw > kTlMaxLw) throw ArgError(box_frame(who, f) + axis + " lw " + std::to_string(lw) + " is outside -1 .. 63");
+    const double sigma = std::max(0.0, ((double)n_in / (double)n_out - 1.0) / 2.0);         // skimage's anti-aliasing sigma (demo._aa_kernel)
+    if (sigma <= 1e-15) {
+        if (lw >= 0) throw ArgError(box_frame(who, f) + "the " + axis + " do not shrink (" + std::to_string(n_in) + " -> " + std::to_string(n_out) + "): lw must be -1");
+        return;
+    }
+    if (lw != (int)(4.0 * sigma + 0.5))
+        throw ArgError(box_frame(who, f) + axis + " lw " + std::to_string(lw) + " is not int(4 sigma + 0.5) of " + std::to_string(n_in) + " -> " + std::to_string(n_out));
+    if (woff < 0 || !pool || (long long)woff + lw + 1 > (long long)pool_len)
+        throw ArgError(box_frame(who, f) + "the " + axis + " half-kernel at offset " + std::to_string(woff) + " ends beyond the pool of " + std::to_string(pool_len) + " doubles");
+}
+
+static void face_labels_boxes_any(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev, const double* pool,
+                                  int pool_len, int bw, void* workspace, long long ws_len, int OH, int OW, void* cls, void* box, bool u8, void* stream) {
+    const char* who = "face_labels_boxes";
+    if ((!cls && !box) || (cls && !curves) || (box && !keypoints) || !desc_host || !desc_dev || !workspace) throw ArgError("face_labels_boxes: null tensor");
+    if (F < 1 || 2 * (long long)F > 65535) throw ArgError("face_labels_boxes: F must be 1 .. 32767 (two images per frame along the grid's y)");
+    if (bw < 1) throw ArgError("face_labels_boxes: bw must be at least 1");
+    if (OH < 1 || OW < 1 || (double)OH * OW >= 2147483647.0 / 4) throw ArgError("face_labels_boxes: bad output shape");
+    if (pool_len < 0 || ws_len < 0) throw ArgError("face_labels_boxes: negative pool or workspace length");
+    if (((uintptr_t)workspace & 3) != 0) throw ArgError("face_labels_boxes: the workspace must be 4-byte aligned");
+    if (16ll * F > ws_len) throw ArgError("face_labels_boxes: the workspace of " + std::to_string(ws_len) + " bytes cannot hold the " + std::to_string(2 * F) + " min / max pairs");
+    std::vector<std::pair<long long, int>> starts((size_t)F);         // (offset, frame)
+    int max_hw = 0;
+    bool pass[2] = {false, false};
+    for (int f = 0; f < F; ++f) {
+        const int* d = desc_host + (size_t)f * kTlDesc;
+        const int h = d[0], w = d[1];
+        if (h < 1 || w < 1 || h > kTlMaxSide || w > kTlMaxSide) throw ArgError(box_frame(who, f) + "crop of " + std::to_string(h) + " x " + std::to_string(w) + " (h x w): sides must be 1 .. 32767");
+        check_label_axis(who, f, "rows", h, OH, d[3], d[4], pool, pool_len);
+        check_label_axis(who, f, "columns", w, OW, d[5], d[6], pool, pool_len);
+        const long long off = d[2], end = off + 4ll * h * w;
+        if (off < 16ll * F) throw ArgError(box_frame(who, f) + "its workspace region at offset " + std::to_string(off) + " overlaps the " + std::to_string(2 * F) + " min / max pairs");
+        if (end > ws_len) throw ArgError(box_frame(who, f) + "its workspace region ends at " + std::to_string(end) + ", beyond the workspace of " + std::to_string(ws_len) + " bytes");
+        starts[(size_t)f] = {off, f};
+        max_hw = std::max(max_hw, h * w);
+        pass[0] = pass[0] || d[3] > 0; pass[1] = pass[1] || d[5] > 0;
+    }
+    std::sort(starts.begin(), starts.end());
+    for (int i = 1; i < F; ++i) {
+        const int p = starts[(size_t)i - 1].second, f = starts[(size_t)i].second;
+        const int* dp = desc_host + (size_t)p * kTlDesc;
+        if (starts[(size_t)i - 1].first + 4ll * dp[0] * dp[1] > starts[(size_t)i].first)
+            throw ArgError(box_frame(who, std::max(p, f)) + "its workspace region overlaps that of frame " + std::to_string(std::min(p, f)));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    TrackLabelArgs a{keypoints, curves, desc_dev, pool, static_cast<unsigned char*>(workspace), ws_len, pool_len, F, bw, OH, OW,
+                     cls ? 0 : 1, (cls ? 1 : 0) + (box ? 1 : 0), {cls, box}};
+    const unsigned px = (unsigned)((max_hw + 255) / 256), images = (unsigned)(a.nmaps * F);
+    hipLaunchKernelGGL(track_fill_kernel, dim3((max_hw + 1023) / 1024, F), dim3(256), 0, s, a);
+    check_launch("track_fill");
+    if (cls) {
+        hipLaunchKernelGGL(track_edges_kernel, dim3(kFaceSubEdges, F), dim3(64), 0, s, a);
+        check_launch("track_edges");
+    }
+    for (int axis = 0; axis < 2; ++axis) {
+        if (!pass[axis]) continue;                                   // no frame of the call takes this pass
+        hipLaunchKernelGGL(track_gauss_kernel, dim3(px, images), dim3(256), 0, s, a, axis);
+        check_launch("track_gauss");
+    }
+    hipLaunchKernelGGL(track_minmax_kernel, dim3(std::min(64u, px), images), dim3(256), 0, s, a);
+    check_launch("track_minmax");
+    const dim3 grid((OH * OW + 255) / 256, images);
+    if (u8) hipLaunchKernelGGL(track_resize_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(track_resize_kernel<false>, grid, dim3(256), 0, s, a);
+    check_launch("track_resize");
+}
+
+int tsnet_face_labels_boxes(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev, const double* pool, int pool_len,
+                            int bw, void* workspace, long long workspace_len, int OH, int OW, float* labels, float* masks, void* stream) {
+    OP_BEGIN
+    face_labels_boxes_any(keypoints, curves, F, desc_host, desc_dev, pool, pool_len, bw, workspace, workspace_len, OH, OW, labels, masks, false, stream);
+    OP_END
+}
+
+int tsnet_face_labels_boxes_u8(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev, const double* pool, int pool_len,
+                               int bw, void* workspace, long long workspace_len, int OH, int OW, unsigned char* labels, unsigned char* masks, void* stream) {
+    OP_BEGIN
+    face_labels_boxes_any(keypoints, curves, F, desc_host, desc_dev, pool, pool_len, bw, workspace, workspace_len, OH, OW, labels, masks, true, stream);
     OP_END
 }
 

@@ -1,7 +1,8 @@
 """Host side of the device rasterisation: key-point files of a clip -> the label tensors
 `set_test_input` takes.  The reference does this per frame on the CPU in its data loader
 (dataset/dataset_video_face.py:283-330, FaceDatasetTest.__getitem__); here the key points of a whole clip go to the device once
-and three kernels (csrc/raster.hpp) produce every frame's edge map, bounding-box mask and one-hot label.
+and three kernels (csrc/raster.hpp) produce every frame's edge map, bounding-box mask and one-hot label.  With a crop per frame
+(fix_crop_pos=False) the frames have different sizes; their labels at the model's resolution are still one call (csrc/track_labels.hpp).
 
 Only the crop arithmetic (a handful of integer operations per clip, dataset_video_face.py:507-518) stays on the host, and for a
 cross-identity pair the loader's key-point preparation of the driving clip (`FaceAdapter`, `smooth_keypoints`, `face_driving_keypoints`:
@@ -54,6 +55,11 @@ class FaceRasteriser:
     def __init__(self, device, lib=None):
         self.lib = lib if lib is not None else _lib.load()
         self.device = torch.device(device)
+        self._wpool_host = np.zeros(0, np.float64)                   # the Gaussian half-kernels of the per-frame-crop labels, one after the other
+        self._wpool_at = {}                                          # (n_in, n_out) -> (lw, offset in doubles)
+        self._wpool = None                                           # the device copy; replaced (never written) when the pool grows
+        self._ws = None                                              # the workspace of tsnet_face_labels_boxes; replaced when a clip needs more
+        self._keep_t = []
 
     def _stream(self) -> Optional[int]:
         return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
@@ -153,20 +159,101 @@ class FaceRasteriser:
         mask (F,H,W) as uint8 -- what Engine.forward_target / ClipRunner take as a compact call; no vl2ch, the stem's packing kernel makes
         the one-hot planes on load.  Returns (labels, masks, crop).
         crop may be an (F,4) array, a crop per frame (see `rasterise`); bw: the brush width, as `rasterise` takes it.  The tensors are the same
-        (F, ...) ones: every frame is resized from its own crop's size, the frames of equal size in one call."""
+        (F, ...) ones, every frame drawn and resized at its own crop's size, and frame f has the bits of this method called on frame f alone with
+        crop f and the clip's bw.  That form is ONE call of the library (`tsnet_face_labels_boxes[_u8]`, csrc/track_labels.hpp) however many
+        sizes the clip has -- a clip of a single size, F = 1 included, goes the same way (measured no slower than the single-size entries:
+        profiles/track_labels.txt).  Once a clip's sizes have been seen a call is one upload on the current stream (key points, fitted curves
+        and descriptors in one buffer, from pageable memory as FrameLoader's descriptors are) and at most six kernels, with no allocation and
+        no synchronisation inside the library; the weight pool and the workspace live on the rasteriser and are replaced when a clip needs
+        more.  One stream at a time per rasteriser."""
         from .demo import resize_label
+        if crop is not None and np.ndim(crop) == 2:
+            return self._clip_labels_crops(keypoints, size, crop, relative, compact, bw)
         edges, bbox, crop, _ = self.rasterise(keypoints, crop, relative, bw)
-        if isinstance(edges, list):
-            cls = torch.empty((len(edges),) + tuple(size), dtype=torch.float32, device=self.device)
-            box = torch.empty_like(cls)
-            for idx in self._size_groups(crop).values():
-                cls[idx] = resize_label(torch.stack([edges[f] for f in idx]), size, lib=self.lib)
-                box[idx] = resize_label(torch.stack([bbox[f] for f in idx]), size, lib=self.lib)
-        else:
-            cls, box = resize_label(edges, size, lib=self.lib), resize_label(bbox, size, lib=self.lib)
+        cls, box = resize_label(edges, size, lib=self.lib), resize_label(bbox, size, lib=self.lib)
         if compact:
             return cls.to(torch.uint8), box.to(torch.uint8), crop          # exact: the maps hold 0 / 1
         return self.vl2ch(cls, 2), box, crop
+
+    def _aa_axis(self, n_in: int, n_out: int) -> Tuple[int, int]:
+        """(lw, offset in doubles) of an axis' Gaussian half-kernel (demo._aa_kernel) in the pool, appended on first sight; (-1, 0) for an axis
+        that does not shrink"""
+        key = (n_in, n_out)
+        if key not in self._wpool_at:
+            from .demo import _aa_kernel
+            lw, w = _aa_kernel(n_in, n_out)
+            if lw < 0:
+                self._wpool_at[key] = (-1, 0)
+            else:
+                self._wpool_at[key] = (lw, len(self._wpool_host))
+                self._wpool_host = np.concatenate([self._wpool_host, w])
+                self._wpool = None
+        return self._wpool_at[key]
+
+    def _label_descriptors(self, crops: np.ndarray, size: Tuple[int, int]):
+        """(host (F,8) int32 rows {h, w, off, lw_rows, woff_rows, lw_cols, woff_cols, 0}, workspace bytes) as tsnet_face_labels_boxes takes them:
+        the 2F min / max pairs, then a region of 4 h w bytes per frame, each on a 64-byte boundary"""
+        OH, OW = int(size[0]), int(size[1])
+        F = len(crops)
+        rows, off = [], (16 * F + 63) // 64 * 64
+        for f, c in enumerate(crops.tolist()):                       # plain ints: this loop is per frame and per call
+            h, w = c[1] - c[0], c[3] - c[2]
+            if h < 1 or w < 1:
+                raise ValueError(f"frame {f}: empty crop {tuple(c)}")
+            (lr, wr), (lc, wc) = self._aa_axis(h, OH), self._aa_axis(w, OW)
+            rows.append((h, w, off, lr, wr, lc, wc, 0))
+            off += (4 * h * w + 63) // 64 * 64
+            if off >= 2 ** 31:
+                raise ValueError(f"frame {f}: the clip's crops need more than 2 GiB of workspace in one call; split the clip")
+        return np.array(rows, dtype=np.int32).reshape(-1, 8), off
+
+    def _clip_labels_crops(self, keypoints, size, crops, relative: bool, compact: bool, bw: Optional[int]):
+        """clip_labels with a crop per frame: one call of tsnet_face_labels_boxes[_u8]"""
+        kp = np.stack([np.asarray(k, dtype=np.float64) for k in keypoints])
+        if kp.ndim != 3 or kp.shape[1:] != (68, 2):
+            raise ValueError(f"expected F x 68 x 2 key points, got {kp.shape}")
+        crops = np.asarray(crops).astype(np.int64)
+        F = kp.shape[0]
+        if crops.shape != (F, 4):
+            raise ValueError(f"expected ({F},4) crops for {F} frames, got {crops.shape}")
+        if bw is None:
+            bw = max(1, int(crops[0, 1] - crops[0, 0]) // 256)      # the first frame's, for the whole clip (:302, :347)
+        kp = kp.copy()
+        if not relative:
+            kp[:, :, 0] -= crops[:, 2, None]                        # read_keypoints(path, None) (:499-507): each frame by its own crop
+            kp[:, :, 1] -= crops[:, 0, None]
+        kp = np.ascontiguousarray(kp)
+        desc, ws_len = self._label_descriptors(crops, size)
+        curves = np.empty((F, 34, 8), dtype=np.float64)              # the fits stay on the host, as in `rasterise`
+        rc = self.lib.tsnet_fit_face_curves(kp.ctypes.data, F, curves.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"tsnet_fit_face_curves failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        # one upload: key points | curves | descriptors (multiples of 8 bytes, so each part is aligned for its type)
+        up = torch.from_numpy(np.concatenate([kp.reshape(-1).view(np.uint8), curves.reshape(-1).view(np.uint8), desc.reshape(-1).view(np.uint8)])).to(self.device)
+        kd = up.data_ptr()
+        cd, dd = kd + kp.nbytes, kd + kp.nbytes + curves.nbytes
+        old = []
+        if self._wpool is None:                                      # grown: a new device copy; the old one may still be read by an enqueued kernel
+            old.append(self._keep_t[1] if self._keep_t else None)
+            self._wpool = torch.from_numpy(self._wpool_host.copy()).to(self.device)
+        if self._ws is None or self._ws.numel() < ws_len:
+            old.append(self._ws)
+            self._ws = torch.empty(ws_len, dtype=torch.uint8, device=self.device)
+        OH, OW = int(size[0]), int(size[1])
+        dtype = torch.uint8 if compact else torch.float32
+        cls = torch.empty((F, OH, OW), dtype=dtype, device=self.device)
+        box = torch.empty((F, OH, OW), dtype=dtype, device=self.device)
+        fn = self.lib.tsnet_face_labels_boxes_u8 if compact else self.lib.tsnet_face_labels_boxes
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        with ctx:
+            rc = fn(kd, cd, F, desc.ctypes.data, dd, self._wpool.data_ptr() if self._wpool.numel() else None, self._wpool.numel(), int(bw),
+                    self._ws.data_ptr(), self._ws.numel(), OH, OW, cls.data_ptr(), box.data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tsnet_face_labels_boxes{'_u8' if compact else ''} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep_t = [up, self._wpool, self._ws] + old            # alive until the stream has consumed them
+        if compact:
+            return cls, box, crops
+        return self.vl2ch(cls, 2), box, crops
 
 
 # ------------------------------------------------------------------------------------------------- cross-identity face pairs
