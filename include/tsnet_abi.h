@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8); 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
+#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8), tsnet_op_upconv2d; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
 #define TSNET_MAX_SOURCES 8
 
 enum {
@@ -229,6 +229,13 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  *   All one-group tiles of one kernel produce identical bits, and so do the two two-group tiles among themselves (tested); the two-group
  *   tiles, and patch vs general kernels, sum K in another association / order: agreement to fp32 rounding.  Any other kernel or tile value,
  *   or a code the layer's kernel has no tile for, returns TSNET_ERR_ARG (csrc/conv_plan.hpp decode_tile_code, plan_conv).
+ * tsnet_op_upconv2d <- nn.Upsample(scale_factor=2, bilinear, align_corners=False) + nn.ReflectionPad2d(1) + nn.Conv2d(3 x 3) (TSNet.py:145-147), as the
+ *   decoder runs its up-convolutions: x (N,H,W,Cin) is the LOW-resolution map, y (N,2H,2W,Cout); the other arguments are tsnet_op_conv2d's, for a
+ *   3 x 3 / stride-1 / pad-1 layer with reflection padding and nprod = 3; in_alpha / in_beta / in_relu apply to x (NULL: the raw map, no ReLU).
+ *   kernel: 0 = the fused form (conv_h2.hpp: the patch kernel forms the upsampled patch from a low-resolution patch while it stages it; the
+ *   upsampled tensor never exists), 1 = tsnet_op_upsample2x into a scratch tensor, then tsnet_op_conv2d with the same tile -- the same bits
+ *   (tested).  tile: 0, 64 or 128.  2H and 2W must split into 4 x 32 tiles.  Zero padding, another kernel size or stride, nprod != 3, or a
+ *   frame / tile the fused form is not built for return TSNET_ERR_ARG on BOTH routes, with nothing launched.
  * tsnet_op_conv2d_cat <- the same on torch.cat((x, x2), channel axis) formed on load (dec.map_conv on cat(pg, sg), TSNet.py:163):
  *   x (N,H,W,C1), x2 (x2_nmod,H,W,C2) read at image n % x2_nmod; C1 a multiple of 16.  No input transform.
  * tsnet_op_head <- the decoder's RGB head: ReflectionPad2d(3) + Conv2d(C -> 3, 7x7) + bias + Tanh (TSNet.py:151-152) on relu(alpha*x+beta),
@@ -288,6 +295,10 @@ int tsnet_op_conv2d(const float* x, int N, int H, int W, int Cin,
                     const float* w_oihw, const float* bias, int Cout, int ksize, int stride, int pad, int pad_mode,
                     const float* in_alpha, const float* in_beta, int in_relu, float bound, int nprod, int kernel, int tile,
                     float* y, void* stream);
+int tsnet_op_upconv2d(const float* x, int N, int H, int W, int Cin,
+                      const float* w_oihw, const float* bias, int Cout, int ksize, int stride, int pad, int pad_mode,
+                      const float* in_alpha, const float* in_beta, int in_relu, float bound, int nprod, int kernel, int tile,
+                      float* y, void* stream);
 int tsnet_op_conv2d_cat(const float* x, const float* x2, int N, int H, int W, int C1, int C2, int x2_nmod,
                         const float* w_oihw, const float* bias, int Cout, int ksize, int stride, int pad, int pad_mode,
                         float bound, int nprod, float* y, void* stream);

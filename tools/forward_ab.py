@@ -1,5 +1,6 @@
 """GPU box: same-box, same-process A/B of the whole forward under a tools-build knob (tsnet_tools_set; the product library has no knobs).
 Interleaved rounds, medians.  knob 0 = largest conv_w1 chunk the launcher may choose (3 = product behaviour, 1 = one tile per workgroup).
+knob 1 = the decoder never takes the fused upsample (0 = product behaviour, 1 = upsample2x + convolution on every up-convolution): --knob 1 --values 0,1.
     python tools/forward_ab.py [--batch 4] [--n-blocks 0] [--rounds 7] [--iters 20] [--knob 0] [--values 3,1]
 --lib2 PATH: A/B of two BUILDS instead (this tree's tools library against another .so of the same ABI, e.g. the previous commit's, built
 into wacv23_tsnet_amd/lib/libtsnet_tools_prev.so): one engine per library, interleaved rounds in one process on one box.

@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "tsnet_paste_frames",
     "tsnet_prepare_frames_boxes", "tsnet_prepare_frames_boxes_u8", "tsnet_paste_frames_boxes",
     "tsnet_face_labels_boxes", "tsnet_face_labels_boxes_u8",
+    "tsnet_op_upconv2d",
 )
 
 
@@ -153,6 +154,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "tsnet_face_labels_boxes"):  # absent from an older build opened beside this one (tools/track_labels_bench.py --lib2)
         for fn in (lib.tsnet_face_labels_boxes, lib.tsnet_face_labels_boxes_u8):
             fn.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, C.c_int, _vp, _vp, _vp]
+    if hasattr(lib, "tsnet_op_upconv2d"):        # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_op_upconv2d.argtypes = lib.tsnet_op_conv2d.argtypes
     return lib
 
 

@@ -321,6 +321,30 @@ __device__ __forceinline__ void transform_octet(const F4 (&sx)[2], const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Bilinear x2 upsample (nn.Upsample, align_corners = False) in ONE spelling: upsample2x_kernel (norm_elementwise.hpp) and the fused patch
+// staging of the up-convolutions (conv_h2.hpp, UP2) both evaluate these three functions, so a sample has the same bits on either route.
+// Source coordinate of output index o on an axis of n inputs: src = (o + 0.5) / 2 - 0.5 clamped at 0, neighbour index clamped at n - 1.
+__device__ __forceinline__ void up2_source(int o, int n, int& i0, int& i1, float& w0, float& w1) {
+    float s = (o + 0.5f) * 0.5f - 0.5f; if (s < 0.f) s = 0.f;
+    i0 = (int)s;
+    i1 = i0 + (i0 < n - 1 ? 1 : 0);
+    w1 = s - i0; w0 = 1.f - w1;
+}
+// a tap on load: the producer's InstanceNorm (x * alpha + beta, one FMA) and ReLU
+__device__ __forceinline__ float up2_tap(float v, float al, float be, bool norm, bool relu) {
+    if (norm) v = __builtin_fmaf(v, al, be);
+    if (relu) v = v > 0.f ? v : 0.f;
+    return v;
+}
+// one lerp: two products and their sum (built with -ffp-contract=off: never an FMA)
+__device__ __forceinline__ float up2_lerp(float a, float b, float w0, float w1) { return w0 * a + w1 * b; }
+// horizontal lerps first, then the vertical one (ATen's separable order): wy0 * (wx0 * v00 + wx1 * v01) + wy1 * (wx0 * v10 + wx1 * v11).
+// The fused staging evaluates the three lerps itself -- two vertical neighbours share the horizontal pair.
+__device__ __forceinline__ float up2_blend(float v00, float v01, float v10, float v11, float wx0, float wx1, float wy0, float wy1) {
+    return up2_lerp(up2_lerp(v00, v01, wx0, wx1), up2_lerp(v10, v11, wx0, wx1), wy0, wy1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Shared epilogue: bias, optional per-pixel addend, fp64 InstanceNorm partial sums of the tile (fixed order: deterministic), fp32 store (last).
 // m_of(l) maps the local row l of the tile to the output position m (or -1: a row past the end of the image).
 // STAT_WAVE: the wave that reduces the tile's statistics partials and hands them off (BN <= 64: one wave does it alone).  conv_w1 names a

@@ -37,7 +37,21 @@ namespace tsnet {
 // bit 5 = weight fragments five steps ahead (six register sets).
 // HABL (tools/h2_variants.py; non-zero computes garbage): bit0 no patch staging in the loop, bit1 weight fragments loaded once, bit2 A
 // fragments read once, bit3 no fold, bit4 no slab barrier.
-template <int PR, int BN, int WARPS_M, int WARPS_N, int NPROD, bool AFFINE, int HABL = 0, int OPT = 0>
+// UP2 (the decoder's up-convolutions): a.x is the HALF-resolution map (N, H/2, W/2, Cin) and the patch is upsample2x(relu(alpha x + beta)) of it,
+// formed while it is staged -- the upsampled tensor never exists.  The 6 x 34 patch of a 4 x 32 tile comes from a 4 x 18 low-res patch (rows
+// oy0/2 - 1 .. oy0/2 + 2, columns ox0/2 - 1 .. ox0/2 + 16; the reflection of the hi-res border stays inside it):
+//   stage 1: 144 lanes (72 pixels x 2 octets) fetch it once per slab, apply IN + ReLU once per pixel (up2_tap) and write fp32 to one of two
+//            low-res buffers in LDS ([channel quad][pixel], 16-byte entries: neighbouring lanes read neighbouring entries) -- fetched at
+//            step 6, written at step 8 of the slab TWO ahead of the one it feeds;
+//   stage 2: a lane takes a VERTICAL PAIR of patch pixels (patch rows 2j, 2j + 1 of one column: 3 x 34 pairs x 2 octets = 204 lanes, the
+//            other 52 repeat a neighbour's pair) -- the two share their low-res rows, hence the four taps and the two horizontal lerps per
+//            channel: 13 VALU operations per two values where two separate blends take 18, half the LDS reads.  (At the bottom border the
+//            upper pixel's rows are (H/2 - 1, H/2 - 1) where the reflected lower one's are (H/2 - 2, H/2 - 1): one select per value.)  The
+//            arithmetic is upsample2x_kernel's (up2_lerp), the same bits.  Then scale + split and the planes, as the direct staging
+//            writes them -- one channel quad at step 1, the other at step 4 of the slab ahead, nothing carried between the two.
+// With the low-res buffer two slabs ahead of the MFMAs the slab still has ONE barrier.  Everything after the patch is in LDS -- K order,
+// chains, fold points, epilogue, statistics -- is the direct form's.  fp16 x 2 operands, reflection padding, one K group, plain schedule.
+template <int PR, int BN, int WARPS_M, int WARPS_N, int NPROD, bool AFFINE, int HABL = 0, int OPT = 0, bool UP2 = false>
 __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_raw, const int tile_m, const int n0) {
     constexpr int BM = PR * kPatchCols;
     constexpr int NW = WARPS_M * WARPS_N;
@@ -63,7 +77,11 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
     constexpr int PLANE_P = 2 * REGION, PATCH_BYTES = NPL * PLANE_P;
     constexpr int OFF_SINK = 2 * 2 * PLANE_P;                        // 2 KiB sink for a wave whose second pixel block does not exist (branch-free staging)
     constexpr int GROUP_BYTES = OFF_SINK + 2048;                     // stages + sink of one K group
-    constexpr int OFF_TAB = KG * GROUP_BYTES;                        // (alpha*s, beta*s) table of the image: 2 x Cin floats (fixed offset in both modes)
+    constexpr int LPC = kPatchCols / 2 + 2, LPP = (PR / 2 + 2) * LPC;    // UP2: the low-res patch, 18 columns x 4 rows = 72 pixels
+    constexpr int LQ = LPP * 16, LBUF = 4 * LQ;                      // one channel quad of it (16-byte entries); one buffer = the slab's four quads
+    constexpr int OFF_LOW = KG * GROUP_BYTES;                        // UP2: the two low-res buffers
+    constexpr int OFF_TAB = OFF_LOW + (UP2 ? 2 * LBUF : 0);          // (alpha*s, beta*s) table of the image: 2 x Cin floats (UP2: alpha, beta -- the scale follows the blend)
+    static_assert(!UP2 || (PR == 4 && NPROD == 3 && KG == 1 && !DEEP && !ZPAD_KEEP && HABL == 0), "fused upsample: fp16 x 2 operands, four-row tiles, plain schedule, reflection");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -86,7 +104,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
 
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
     const bool xb16 = NPROD == 1 && a.x_bf16;                        // bf16 storage: the input tensor holds bf16 (conv_common.hpp load_x_octet)
-    const tsnet_brsrc_t rsx = tsnet_make_brsrc(a.x, (unsigned)((size_t)a.N * a.H * a.W * a.Cin * (xb16 ? 2 : 4)));
+    const tsnet_brsrc_t rsx = tsnet_make_brsrc(a.x, (unsigned)((size_t)a.N * (UP2 ? (a.H >> 1) * (a.W >> 1) : a.H * a.W) * a.Cin * (xb16 ? 2 : 4)));
     tsnet_brsrc_t rsw[NPL];
 #pragma unroll
     for (int p = 0; p < NPL; ++p) rsw[p] = tsnet_make_brsrc(a.w + p * planew, (unsigned)(planew * 2));
@@ -114,11 +132,47 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         vP[r] = ok ? (unsigned)(((img * a.H * a.W + pix) * a.Cin + oct * 8) * 4) : kOOB;
         vM[r] = ok ? 1.f : 0.f;
     }
+    // UP2, stage 1: thread -> (low-res patch pixel tid % 72, octet tid / 72); threads 144 .. 255 fetch zeros and write the sink
+    unsigned vL = kOOB;
+    int oL = -1;
+    const int octL = tid < LPP ? 0 : 1;
+    if (UP2) {
+        const int lp = tid < LPP ? tid : tid - LPP;
+        const int ly = (oy0 >> 1) - 1 + lp / LPC, lx = (ox0 >> 1) - 1 + lp % LPC;
+        const int Hl = a.H >> 1, Wl = a.W >> 1;
+        if (tid < 2 * LPP) {
+            oL = (2 * octL * LPP + lp) * 16;
+            if (ly >= 0 && ly < Hl && lx >= 0 && lx < Wl) vL = (unsigned)(((img * Hl * Wl + ly * Wl + lx) * a.Cin + octL * 8) * 4);      // (pixels outside the map: zeros, never read)
+        }
+    }
+    // UP2, stage 2: thread -> (pair tid % 128 = j * 34 + column, octet tid / 128); lanes past the 102 pairs repeat pair - 64 (same values to the
+    // same addresses).  A = patch row 2j, B = row 2j + 1; the pair reads B's low-res rows (r0, r0 + 1) -- A's too, but for the bottom border.
+    int uA = 0, uDx = 0, uDst = 0;                                   // byte offset of tap (r0, x0) in a low-res buffer, to its right neighbour; of A's slot in a plane
+    float uWx = 0.f, uWyA = 0.f, uWyB = 0.f;                         // weights of the right tap and of the lower row for A and B (0, 0.25 or 0.75)
+    bool uSelA = false;                                              // A's upper row is the pair's LOWER one (bottom border)
+    if (UP2) {
+        const int octU = tid >> 7;
+        int idx = tid & 127;
+        idx = idx < 3 * PC ? idx : idx - 64;
+        const int j = idx / PC, pc = idx - j * PC;
+        auto refl = [](int i, int n) { i = i < 0 ? -i : i; return i >= n ? 2 * (n - 1) - i : i; };
+        const int ix = refl(ox0 - 1 + pc, a.W), iyA = refl(oy0 - 1 + 2 * j, a.H), iyB = refl(oy0 + 2 * j, a.H);
+        int x0, x1, r0, r1, a0, a1;
+        float w0;
+        up2_source(ix, a.W >> 1, x0, x1, w0, uWx);
+        up2_source(iyB, a.H >> 1, r0, r1, w0, uWyB);                 // r1 = r0 + 1: an even row's upper tap is never the last row
+        up2_source(iyA, a.H >> 1, a0, a1, w0, uWyA);                 // a1 = r1
+        uSelA = a0 != r0;
+        uA = (2 * octU * LPP + (r0 - ((oy0 >> 1) - 1)) * LPC + x0 - ((ox0 >> 1) - 1)) * 16;
+        uDx = (x1 - x0) * 16;
+        uDst = octU * REGION + (2 * j * PC + pc) * 16;
+    }
     float* tab = reinterpret_cast<float*>(smem_raw + OFF_TAB);       // [Cin] alpha*s, then [Cin] beta*s
     if (AFFINE) {
+        const float ts = UP2 ? 1.f : in_scale;
         for (int c = tid; c < a.Cin; c += 256 * KG) {
-            tab[c] = a.in_alpha[(size_t)img * a.Cin + c] * in_scale;
-            tab[a.Cin + c] = a.in_beta[(size_t)img * a.Cin + c] * in_scale;
+            tab[c] = a.in_alpha[(size_t)img * a.Cin + c] * ts;
+            tab[a.Cin + c] = a.in_beta[(size_t)img * a.Cin + c] * ts;
         }
         __syncthreads();
     }
@@ -150,6 +204,51 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
             *reinterpret_cast<F4*>(dst) = Hh;
             *reinterpret_cast<F4*>(dst + (b < PBLK ? PLANE_P : 1024)) = Ll;
         }
+    };
+
+    // UP2 stage 1: the lane's low-res octet of slab cn -> registers; IN + ReLU, fp32 -> low-res buffer lb
+    F4 sl[2][2];                                                     // [set][half octet]: the second set serves the prologue alone
+    auto low_load = [&](int cn, int set) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) sl[set][q] = TSNET_BUF_LOAD16(rsx, vL, (unsigned)(cn * 64 + q * 16));
+    };
+    auto low_store = [&](int cn, int set, int lb) __attribute__((always_inline)) {
+        const float* ta = tab + (cn < ncc ? cn * 16 : 0) + octL * 8;     // past the last slab: any valid entry (result unused)
+        F4 t[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            F4 al = sl[set][q], be = sl[set][q];                     // (raw input: not used)
+            if (AFFINE) { al = *reinterpret_cast<const F4*>(ta + q * 4); be = *reinterpret_cast<const F4*>(ta + a.Cin + q * 4); }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[q].v[e] = up2_tap(sl[set][q].v[e], al.v[e], be.v[e], AFFINE, AFFINE && a.in_relu);
+        }
+        unsigned char* dst = smem_raw + (oL >= 0 ? OFF_LOW + lb * LBUF + oL : OFF_SINK + lane * 16);
+        *reinterpret_cast<F4*>(dst) = t[0];
+        *reinterpret_cast<F4*>(dst + (oL >= 0 ? LQ : 0)) = t[1];
+    };
+    // UP2 stage 2: channel quad h of the lane's pixel pair, blended from low-res buffer lb, scaled, split and written to the planes of stage par
+    auto up_pair = [&](int lb, int par, int h) __attribute__((always_inline)) {
+        const unsigned char* p = smem_raw + OFF_LOW + lb * LBUF + h * LQ + uA;
+        const F4 v00 = *reinterpret_cast<const F4*>(p), v01 = *reinterpret_cast<const F4*>(p + uDx);
+        const F4 v10 = *reinterpret_cast<const F4*>(p + LPC * 16), v11 = *reinterpret_cast<const F4*>(p + LPC * 16 + uDx);
+        const float wx0 = 1.f - uWx, wa0 = 1.f - uWyA, wb0 = 1.f - uWyB;
+        float oa[4], ob[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float h0 = up2_lerp(v00.v[e], v01.v[e], wx0, uWx), h1 = up2_lerp(v10.v[e], v11.v[e], wx0, uWx);
+            oa[e] = up2_lerp(uSelA ? h1 : h0, h1, wa0, uWyA);
+            ob[e] = up2_lerp(h0, h1, wb0, uWyB);
+        }
+        // what the direct staging does with the upsampled tensor as its raw input: x * 2^sa, split (one instruction form for both: conv_common.hpp)
+        unsigned ha[2], la[2], hb[2], lb2[2];
+        TSNET_SPLIT_2PAIRS_SCALED(oa[0], oa[1], oa[2], oa[3], in_scale, ha[0], la[0], ha[1], la[1]);
+        TSNET_SPLIT_2PAIRS_SCALED(ob[0], ob[1], ob[2], ob[3], in_scale, hb[0], lb2[0], hb[1], lb2[1]);
+        unsigned char* dst = gbase + par * PATCH_BYTES + uDst + h * 8;
+        struct alignas(8) U2 { unsigned v[2]; };
+        *reinterpret_cast<U2*>(dst) = U2{{ha[0], ha[1]}};
+        *reinterpret_cast<U2*>(dst + PLANE_P) = U2{{la[0], la[1]}};
+        *reinterpret_cast<U2*>(dst + PC * 16) = U2{{hb[0], hb[1]}};
+        *reinterpret_cast<U2*>(dst + PC * 16 + PLANE_P) = U2{{lb2[0], lb2[1]}};
     };
 
     // ---- fragments.  Weights: lane (li, lh) takes the 16 bytes of column wn0 + j*32 + li, logical octet lh.
@@ -229,8 +328,12 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         // staging of slab cc+1: round 0 fetched at step 0 and written at step 2, round 1 fetched at step 3 and written at step 5 (DEEP: fetched
         // at steps 0 and 1, written at steps 5 and 7).  Past the last slab the loads run into the next pixel's channels or return zeros:
         // written to the idle stage, never read.
-        if (s == 0 && !(HABL & 1)) stage_load_x(cc + 1, 0);
-        if (s == (DEEP ? 1 : 3) && !(HABL & 1)) stage_load_x(cc + 1, 1);
+        if (UP2) {                                                   // slab cc+1's patch from low-res buffer par ^ 1, slab cc+2's low-res patch into buffer par
+            if (s == 6) low_load(cc + 2, 0);
+        } else {
+            if (s == 0 && !(HABL & 1)) stage_load_x(cc + 1, 0);
+            if (s == (DEEP ? 1 : 3) && !(HABL & 1)) stage_load_x(cc + 1, 1);
+        }
         const int SB = (par * 9 + s) % BD;
         if (ONEP) {
             product(kx, ky, SB, 0, 0, fresh);                        // the one plane
@@ -240,8 +343,14 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
             product(kx, ky, SB, 0, NPL - 1, false);                  // hi * lo
             product(kx, ky, SB, 0, 0, false);                        // hi * hi
         }
-        if (s == (DEEP ? 5 : 2) && !(HABL & 1)) stage_store(cc + 1, par ^ 1, 0);
-        if (s == (DEEP ? 7 : 5) && !(HABL & 1)) stage_store(cc + 1, par ^ 1, 1);
+        if (UP2) {
+            if (s == 1) up_pair(par ^ 1, par ^ 1, 0);
+            if (s == 4) up_pair(par ^ 1, par ^ 1, 1);
+            if (s == 8) low_store(cc + 2, 0, par);
+        } else {
+            if (s == (DEEP ? 5 : 2) && !(HABL & 1)) stage_store(cc + 1, par ^ 1, 0);
+            if (s == (DEEP ? 7 : 5) && !(HABL & 1)) stage_store(cc + 1, par ^ 1, 1);
+        }
         // Nothing crosses a step boundary in the scheduler: the loads above stay ONE step (weights: BD - 1 steps) ahead of their first use.
         // Left free, the scheduler sinks every load to its use to save registers (127 VGPRs, s_waitcnt vmcnt(0) before each MFMA group,
         // 181 us on the ResnetBlock layer instead of 160).
@@ -268,10 +377,20 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
     };
 
     // prologue: patch of slab 0, weight fragments of the first BD - 1 steps
-    stage_load_x(0, 0); stage_load_x(0, 1);
+    if (UP2) {                                                       // ... from the low-res patches of slabs 0 and 1 (buffers 0 and 1)
+        low_load(0, 0); low_load(1, 1);
 #pragma unroll
-    for (int i = 0; i < BD - 1; ++i) load_b(i, 0, i);
-    stage_store(0, 0, 0); stage_store(0, 0, 1);
+        for (int i = 0; i < BD - 1; ++i) load_b(i, 0, i);
+        low_store(0, 0, 0); low_store(1, 1, 1);
+        __syncthreads();
+#pragma unroll
+        for (int h = 0; h < 2; ++h) up_pair(0, 0, h);
+    } else {
+        stage_load_x(0, 0); stage_load_x(0, 1);
+#pragma unroll
+        for (int i = 0; i < BD - 1; ++i) load_b(i, 0, i);
+        stage_store(0, 0, 0); stage_store(0, 0, 1);
+    }
     if (HABL & 2) load_b(2, 0, 2);
     if (HABL & 4) {
         __syncthreads();
@@ -335,7 +454,10 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
 }
 
 // LDS bytes of an h2 tile: two stages x two planes x two octet regions + the sink + the transform table (two-plane offsets in every mode)
-constexpr int h2_lds_bytes(int PR, int Cin, int KG = 1) { return KG * (2 * 2 * 2 * (((PR + 2) * (kPatchCols + 2) + 31) / 32) * 512 + 2048) + 2 * Cin * 4; }
+// (+ UP2: the two low-res buffers of (PR / 2 + 2) x 18 pixels x 16 channels of fp32)
+constexpr int h2_lds_bytes(int PR, int Cin, int KG = 1, bool up2 = false) {
+    return KG * (2 * 2 * 2 * (((PR + 2) * (kPatchCols + 2) + 31) / 32) * 512 + 2048) + (up2 ? 2 * (PR / 2 + 2) * (kPatchCols / 2 + 2) * 64 : 0) + 2 * Cin * 4;
+}
 
 // workgroups per CU the tile is built for
 template <int PR, int BN, int WARPS_M, int WARPS_N, int NPROD, int OPT>
@@ -348,6 +470,16 @@ void conv_h2_kernel(ConvArgs a) {
     int tile_m, tile_n;
     tile_of_block(blockIdx.x, a.tiles_m, a.tiles_n, a.xcd_gn, tile_m, tile_n);
     h2_tile<PR, BN, WARPS_M, WARPS_N, NPROD, AFFINE, HABL, OPT>(a, smem_raw, tile_m, tile_n * BN);
+}
+
+// the same tile on the half-resolution input (UP2): its own kernel name, the direct form's occupancy
+template <int PR, int BN, int WARPS_M, int WARPS_N, int NPROD, bool AFFINE>
+__global__ __launch_bounds__(256, (h2_wgs_per_cu<PR, BN, WARPS_M, WARPS_N, NPROD, 0>()))
+void conv_h2u_kernel(ConvArgs a) {
+    HIP_DYNAMIC_SHARED(__attribute__((aligned(16))) unsigned char, smem_raw)
+    int tile_m, tile_n;
+    tile_of_block(blockIdx.x, a.tiles_m, a.tiles_n, a.xcd_gn, tile_m, tile_n);
+    h2_tile<PR, BN, WARPS_M, WARPS_N, NPROD, AFFINE, 0, 0, true>(a, smem_raw, tile_m, tile_n * BN);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -42,6 +42,14 @@ void go_h2(const ConvArgs& a, hipStream_t s) {
     else go_h2_k<PR, BN, WM, WN, NPROD, true, HABL, OPT | 1>(a, lds, 256 * KG, s);
 }
 
+// the fused-upsample form (conv_h2.hpp UP2; conv_plan.hpp plans it for reflection padding, fp16 x 2 operands, the plain 4 x 64 and 4 x 128 tiles)
+template <int BN>
+void go_h2u(const ConvArgs& a, hipStream_t s) {
+    const size_t lds = (size_t)h2_lds_bytes(4, a.Cin, 1, true);
+    if (a.in_alpha) launch_tiles(conv_h2u_kernel<4, BN, 2, 2, 3, true>, 256, lds, a, s);
+    else launch_tiles(conv_h2u_kernel<4, BN, 2, 2, 3, false>, 256, lds, a, s);
+}
+
 // the one-group tiles, one product (a bf16 or an fp16 plane) or three (conv_plan.hpp plan_conv, case H2, lists the same tiles)
 template <int NPROD>
 void go_h2_shape(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
@@ -65,6 +73,11 @@ void go_h2d(const ConvArgs& a, hipStream_t s) {
 
 void launch_conv_h2(const ConvArgs& a, const ConvPlan& p, int nprod, int abl, int opt, hipStream_t s) {
     const int pr = p.rows, bn = p.width;
+    if (p.up2) {
+        if (nprod == 3 && !abl && !opt && p.sched == ConvSched::Plain && !p.side_by_side && a.reflect && pr == 4 && bn == 64) return go_h2u<64>(a, s);
+        if (nprod == 3 && !abl && !opt && p.sched == ConvSched::Plain && !p.side_by_side && a.reflect && pr == 4 && bn == 128) return go_h2u<128>(a, s);
+        plan_not_built(p, nprod);
+    }
     if (p.sched == ConvSched::TwoGroups) {           // single-frame launches: deep prefetch + two K groups, eight waves (conv_h2.hpp); no experiment variants
         if (pr == 4 && bn == 32) return nprod == 3 ? go_h2<4, 32, 4, 1, 3, 0, 24>(a, s) : (nprod == kNprodF16 ? go_h2<4, 32, 4, 1, kNprodF16, 0, 24>(a, s) : go_h2<4, 32, 4, 1, 1, 0, 24>(a, s));
         if (pr == 4 && bn == 64) return nprod == 3 ? go_h2<4, 64, 2, 2, 3, 0, 24>(a, s) : (nprod == kNprodF16 ? go_h2<4, 64, 2, 2, kNprodF16, 0, 24>(a, s) : go_h2<4, 64, 2, 2, 1, 0, 24>(a, s));

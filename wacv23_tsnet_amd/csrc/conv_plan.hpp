@@ -39,6 +39,8 @@ struct ConvShape {
     bool f16 = false;            // nprod = 1: the plane holds fp16 of the scaled operand (fp16-operand mode) instead of bf16.  Every rule keyed on
                                  // nprod == 1 counts MFMA work per staged byte and holds for both kinds: an fp16 layer runs its bf16 twin's plan
     bool fin_counter = false;    // output statistics with arrival counters supplied: the in-kernel finalize is possible
+    bool up2 = false;            // the input tensor is the HALF-resolution map (N, H/2, W/2, cin): the kernel forms its bilinear x2 upsample while it
+                                 // stages the patch (conv_h2.hpp UP2); H and W stay the extent the convolution sees
     int ho() const { return (H + 2 * pad - ks) / stride + 1; }
     int wo() const { return (W + 2 * pad - ks) / stride + 1; }
 };
@@ -67,6 +69,7 @@ struct ConvPlan {
     int xcd_gn = 0;
     int tpi = 0, tiles_m = 0, tiles_n = 0;
     bool fin = false;            // the statistics are finalised by the convolution's last-arriving workgroups
+    bool up2 = false;            // conv_h2's fused-upsample form (ConvShape::up2)
 };
 
 // tsnet_op_conv2d's (kernel, tile) pair (include/tsnet_abi.h).  kernel 3 (the Winograd form) takes tile = tiles per workgroup.
@@ -235,6 +238,9 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         p.family = conv_class(s, r.rows == 2 ? 2 : kPlanTileRows, r.kernel == ConvKernel::Patch);
         if (r.kernel == ConvKernel::Patch && p.family == ConvFamily::H2R) throw std::invalid_argument("conv: this layer / frame size has no patch kernel");
     }
+    // the half-resolution input: the 3 x 3 / stride-1 patch kernel's reflection-padded fp16 x 2 form and nothing else (checked further in case H2)
+    if (s.up2 && (p.family != ConvFamily::H2 || !s.reflect || s.nprod != 3 || (s.H & 1) || (s.W & 1)))
+        throw std::invalid_argument("conv: a half-resolution input (fused x2 upsample) needs the 3x3 / stride-1 patch kernel, reflection padding, fp16 x 2 operands (three products) and an even frame");
     if (s.nprod != 1 && s.nprod != 3 && (s.nprod != 4 || p.family != ConvFamily::H2))
         throw std::invalid_argument("conv: 1 (bf16 operands), 16 (fp16 operands) or 3 products; four on the 3x3 / stride-1 patch kernel's plain 4x64 and 4x128 tiles");
     if (s.f16 && s.nprod != 1) throw std::invalid_argument("conv: fp16 operands (one fp16 plane) run one product");
@@ -289,6 +295,9 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
         if ((r.sched == ConvSched::TwoGroups || (r.opt & 16)) && (s.cin >> 4) % 2)       // (opt bit 4: the tools build's two-group experiments)
             throw std::invalid_argument("conv(h2): two K groups need an even number of 16-channel slabs");
         if (s.npad % bn) throw std::invalid_argument("conv(h2): the tile width must divide the padded output width");
+        if (s.up2 && (pr != 4 || bn == 32 || p.side_by_side || r.sched != ConvSched::Plain || r.abl || r.opt))
+            throw std::invalid_argument("conv(h2): the fused x2 upsample is built for the plain 4x64 and 4x128 tiles");
+        p.up2 = s.up2;
         p.rows = pr; p.width = bn; p.sched = r.sched;
         set_tiles(pr * kPlanTileCols, bn);
         p.xcd_gn = xcd_grid(s, r.xcd_gn, p.tiles_m, p.tiles_n, "conv(h2)");
@@ -357,6 +366,12 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
     }
     }
     return p;
+}
+
+// Does the layer take the fused-upsample form at this shape?  (The decoder asks before it decides whether the upsampled tensor has to exist.)
+inline bool plan_takes_up2(ConvShape s, int cus) {
+    s.up2 = true;
+    try { return plan_conv(s, ConvRequest{}, cus).up2; } catch (const std::invalid_argument&) { return false; }
 }
 
 // g_launch_counters[3] (tsnet_launch_counters: bench.py labels the roofline kernel with it): rows * 1000 + width of a 3 x 3 / stride-1 tile,

@@ -71,7 +71,7 @@ std::string g_create_error;
     } while (0)
 
 #ifdef TSNET_TOOLS
-int g_tools_knob[8] = {3, 0, 0, 0, 0, 0, 0, 0};     // tools build only (tsnet_tools_set): [0] largest conv_w1 chunk the launcher may choose
+int g_tools_knob[8] = {3, 0, 0, 0, 0, 0, 0, 0};     // tools build only (tsnet_tools_set): [0] largest conv_w1 chunk the launcher may choose; [1] != 0: the decoder never takes the fused upsample; [2] != 0 (read when an engine is created): its second up-convolution stays on the direct kernel
 #endif
 struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct WeightError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -231,6 +231,7 @@ struct ConvCall {
     int x_bf16 = 0, y_bf16 = 0; // bf16 storage mode (bf16-operand kernels only): the input / output tensor holds bf16
     int nprod = 3;              // products per k-group: 3 (4 adds lo*lo), 1 = bf16 operands, or TSNET_NPROD_F16 = one product on one fp16 plane
     int tclass = TSNET_T_CONV;
+    bool up2 = false;           // x is the half-resolution map (N, H/2, W/2, Cin): the kernel forms its x2 upsample while staging (conv_h2.hpp UP2); alpha / beta / relu apply to x
 };
 
 // power-of-two operand scale: |x| <= bound  ->  |x * 2^sa| <= 2^15 < 65504 (fp16 max).  lim: the largest |sa|.  24 keeps the residual plane of
@@ -247,6 +248,17 @@ inline int h2_scale_log2(float bound, int lim = 24) {
     return sa;
 }
 
+// the layer and the call as the planner sees them
+ConvShape conv_shape(const ConvLayer& L, const ConvCall& c) {
+    const bool f16 = c.nprod == TSNET_NPROD_F16;
+    ConvShape sh;
+    sh.ks = L.ks; sh.stride = L.stride; sh.pad = L.pad; sh.reflect = L.reflect; sh.cin = L.cin_pad; sh.cout = L.cout; sh.npad = L.npad; sh.kpad = L.kpad;
+    sh.form = L.form; sh.N = c.N; sh.H = c.H; sh.W = c.W; sh.csplit = c.x2 ? c.csplit : 0; sh.x2_nmod = c.x2_nmod > 0 ? c.x2_nmod : 1;
+    sh.transform = c.alpha != nullptr; sh.nprod = f16 ? 1 : c.nprod; sh.f16 = f16; sh.fin_counter = c.stat_part && c.fin_counter;
+    sh.up2 = c.up2;
+    return sh;
+}
+
 // What depends on pointers is checked here; the layer, the geometry and the request by plan_conv (conv_plan.hpp), before anything is launched.
 void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req = {}) {
     const bool bf16 = c.nprod == 1, f16 = c.nprod == TSNET_NPROD_F16;      // the two one-product kinds: unscaled bf16, or fp16 with the split path's scales
@@ -258,10 +270,8 @@ void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req =
 #ifdef TSNET_TOOLS
     req.chunk_cap = g_tools_knob[0];          // tools/forward_ab.py: the same forward with and without chunks, one process
 #endif
-    ConvShape sh;
-    sh.ks = L.ks; sh.stride = L.stride; sh.pad = L.pad; sh.reflect = L.reflect; sh.cin = L.cin_pad; sh.cout = L.cout; sh.npad = L.npad; sh.kpad = L.kpad;
-    sh.form = L.form; sh.N = c.N; sh.H = c.H; sh.W = c.W; sh.csplit = c.x2 ? c.csplit : 0; sh.x2_nmod = c.x2_nmod > 0 ? c.x2_nmod : 1;
-    sh.transform = c.alpha != nullptr; sh.nprod = f16 ? 1 : c.nprod; sh.f16 = f16; sh.fin_counter = c.stat_part && c.fin_counter;
+    if (c.up2 && (c.x_bf16 || c.y_bf16 || c.in_amax)) throw ArgError("conv: the fused x2 upsample takes fp32 tensors and an a-priori operand bound");
+    const ConvShape sh = conv_shape(L, c);
     ConvPlan p;
     try { p = plan_conv(sh, req, ctx.cus); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     ConvArgs g{};
@@ -769,7 +779,11 @@ void tsnet_engine::build_layers() {
     to_w1(fuse_c1_src, h, w); to_w1(fuse_c1_tar, h, w); to_w1(fuse_c2, h, w);
     for (auto& L : dec_res) to_w1(L, h, w);
     if (!dec_up.empty()) to_w1(dec_up[0], 2 * h, 2 * w);
-    if (dec_up.size() > 1) to_w1(dec_up[1], 4 * h, 4 * w);      // equal at B = 4 (102.7 against 103.4 us), 29.7 against 34 us for one frame; the third (256^2 x 128 -> 64) stays direct: 118 against 140 us
+    bool up1_w1 = true;
+#ifdef TSNET_TOOLS
+    up1_w1 = g_tools_knob[2] == 0;           // gpu A/B: the second up-convolution on the direct kernel (which then takes the fused upsample)
+#endif
+    if (dec_up.size() > 1 && up1_w1) to_w1(dec_up[1], 4 * h, 4 * w);      // equal at B = 4 (102.7 against 103.4 us), 29.7 against 34 us for one frame; the third (256^2 x 128 -> 64) stays direct: 118 against 140 us
     for (auto& L : img_enc) all_layers.push_back(&L);
     for (auto& L : lbl_enc) all_layers.push_back(&L);
     all_layers.push_back(&fuse_c1_src); all_layers.push_back(&fuse_c1_tar);
@@ -1146,12 +1160,25 @@ void tsnet_engine::forward_rest(Ctx& ctx, const TarIn& tar, float* out_rgb, floa
         // input of up-convolution i = bilinear x2 of relu(IN(previous)) -- a convex combination of InstanceNorm outputs, bounded by
         // sqrt(HW) of the low-resolution map; the first one upsamples the decoder stream itself: published max |D_0| + n_blocks sqrt(P)
         const float in_bound = std::sqrt((float)(hh * ww));
-        run_upsample(ctx, cur, cal, cbe, cal ? 1 : 0, B, hh, ww, cc, U[i], st16 && i > 0, st16);
+        // A direct 3 x 3 layer under IN + ReLU whose plan takes the fused form (conv_plan.hpp: fp16 x 2 operands, 4 x 32 tiles) reads the
+        // low-resolution map itself and blends while it stages its patch -- U[i] is never written (the last up-convolution of the headline:
+        // 134 MB written and read back).  The bound holds: the blend is a convex combination.  Same bits as the two launches.  The layers in
+        // the Winograd form keep them: their producers have neither the registers nor the LDS.
+        bool fused = false;
+        if (cal && !st16) {
+            ConvCall q; q.N = B; q.H = 2 * hh; q.W = 2 * ww; q.alpha = cal; q.nprod = f16 ? TSNET_NPROD_F16 : np;
+            fused = plan_takes_up2(conv_shape(dec_up[i], q), ctx.cus);
+        }
+#ifdef TSNET_TOOLS
+        if (g_tools_knob[1]) fused = false;      // tools/forward_ab.py: the same forward on the two-launch route, one process
+#endif
+        if (!fused) run_upsample(ctx, cur, cal, cbe, cal ? 1 : 0, B, hh, ww, cc, U[i], st16 && i > 0, st16);
         hh *= 2; ww *= 2;
         cc /= 2;
         auto st = next_ab(ctx);
         ConvCall a; a.x = U[i]; a.bound = in_bound; a.N = B; a.H = hh; a.W = ww; a.y = R[i];
         a.x_bf16 = st16; a.y_bf16 = st16;
+        if (fused) { a.x = cur; a.alpha = cal; a.beta = cbe; a.relu = 1; a.up2 = true; }
         if (!cal) { a.in_amax = amax_dec(); a.bound_add = (float)cfg.n_blocks * sqP; }
         conv_stats(ctx, dec_up[i], a, B, hh * ww, st.first, st.second);
         cur = R[i]; cal = st.first; cbe = st.second;
@@ -1651,6 +1678,36 @@ int tsnet_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w
     try { req = decode_tile_code(kernel, tile); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
     OpLayer op(w_oihw, bias, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, kernel == 3 ? 1 : 0);     // kernel 3: Winograd-along-x form (conv_w1.hpp)
     ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
+    run_conv(ctx, op.L, c, req);
+    HIP_TRY(hipStreamSynchronize(s));
+    OP_END
+}
+
+int tsnet_op_upconv2d(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout,
+                      int ksize, int stride, int pad, int pad_mode, const float* in_alpha, const float* in_beta, int in_relu,
+                      float bound, int nprod, int kernel, int tile, float* y, void* stream) {
+    OP_BEGIN
+    if (!x || !w_oihw || !y) throw ArgError("null tensor");
+    if (ksize != 3 || stride != 1 || pad != 1 || pad_mode != 1) throw ArgError("upconv2d op: a 3 x 3 / stride-1 / pad-1 layer with reflection padding");
+    if (nprod != 3) throw ArgError("upconv2d op: fp16 x 2 operands (nprod = 3) and fp32 tensors");
+    if (kernel != 0 && kernel != 1) throw ArgError("upconv2d op: kernel 0 (fused) or 1 (upsample2x, then the convolution)");
+    if (in_alpha && !in_beta) throw ArgError("upconv2d op: alpha without beta");
+    if (N < 1 || H < 1 || W < 1 || (double)N * H * W * 4 * Cin >= 536870912.0) throw ArgError("upconv2d op: empty or too large a tensor");
+    hipStream_t s = (hipStream_t)stream;
+    Ctx ctx(s, current_device_cus());
+    ConvRequest req;
+    try { req = decode_tile_code(0, tile); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    OpLayer op(w_oihw, bias, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s);
+    // both routes answer to the fused form's plan: what it refuses is refused before anything is launched
+    ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_alpha ? in_relu : 0; c.bound = bound; c.N = N; c.H = 2 * H; c.W = 2 * W; c.y = y; c.nprod = nprod;
+    c.up2 = true;
+    try { (void)plan_conv(conv_shape(op.L, c), req, ctx.cus); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    DevBufs mem;
+    if (kernel == 1) {
+        float* up = mem.alloc<float>((size_t)N * 2 * H * 2 * W * Cin * sizeof(float));
+        run_upsample(ctx, x, in_alpha, in_alpha ? in_beta : nullptr, c.relu, N, H, W, Cin, up);
+        c.x = up; c.alpha = nullptr; c.beta = nullptr; c.relu = 0; c.up2 = false;
+    }
     run_conv(ctx, op.L, c, req);
     HIP_TRY(hipStreamSynchronize(s));
     OP_END

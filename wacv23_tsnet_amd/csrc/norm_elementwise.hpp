@@ -319,15 +319,10 @@ __device__ __forceinline__ float4 ld4_f32_or_bf16(const float* base, size_t elem
                        __builtin_bit_cast(float, p.y << 16), __builtin_bit_cast(float, p.y & 0xFFFF0000u));
 }
 
+// the four channels of a tap on load (conv_common.hpp up2_tap)
 __device__ __forceinline__ float4 na4(float4 v, const float4& al, const float4& be, bool norm, bool relu) {
-    if (norm) {
-        v.x = __builtin_fmaf(v.x, al.x, be.x); v.y = __builtin_fmaf(v.y, al.y, be.y);
-        v.z = __builtin_fmaf(v.z, al.z, be.z); v.w = __builtin_fmaf(v.w, al.w, be.w);
-    }
-    if (relu) {
-        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-    }
+    v.x = up2_tap(v.x, al.x, be.x, norm, relu); v.y = up2_tap(v.y, al.y, be.y, norm, relu);
+    v.z = up2_tap(v.z, al.z, be.z, norm, relu); v.w = up2_tap(v.w, al.w, be.w, norm, relu);
     return v;
 }
 
@@ -341,11 +336,10 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(UpsampleArgs a) {
         const int ox = (int)(j / c4n);
         const int c = (int)(j - (unsigned)ox * c4n) * 4;
         const size_t i = ((size_t)n * Ho + oy) * row4 + j;
-        float sy = (oy + 0.5f) * 0.5f - 0.5f; if (sy < 0.f) sy = 0.f;
-        float sx = (ox + 0.5f) * 0.5f - 0.5f; if (sx < 0.f) sx = 0.f;
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = y0 + (y0 < a.H - 1 ? 1 : 0), x1 = x0 + (x0 < a.W - 1 ? 1 : 0);
-        const float wy1 = sy - y0, wy0 = 1.f - wy1, wx1 = sx - x0, wx0 = 1.f - wx1;
+        int y0, y1, x0, x1;
+        float wy0, wy1, wx0, wx1;
+        up2_source(oy, a.H, y0, y1, wy0, wy1);
+        up2_source(ox, a.W, x0, x1, wx0, wx1);
         const bool norm = a.alpha != nullptr;
         float4 al = make_float4(1.f, 1.f, 1.f, 1.f), be = make_float4(0.f, 0.f, 0.f, 0.f);
         if (norm) {
@@ -359,10 +353,10 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(UpsampleArgs a) {
         const float4 v10 = na4(ld4_f32_or_bf16(a.x, base + ((size_t)y1 * a.W + x0) * a.C, xb), al, be, norm, a.relu);
         const float4 v11 = na4(ld4_f32_or_bf16(a.x, base + ((size_t)y1 * a.W + x1) * a.C, xb), al, be, norm, a.relu);
         float4 o;
-        o.x = wy0 * (wx0 * v00.x + wx1 * v01.x) + wy1 * (wx0 * v10.x + wx1 * v11.x);
-        o.y = wy0 * (wx0 * v00.y + wx1 * v01.y) + wy1 * (wx0 * v10.y + wx1 * v11.y);
-        o.z = wy0 * (wx0 * v00.z + wx1 * v01.z) + wy1 * (wx0 * v10.z + wx1 * v11.z);
-        o.w = wy0 * (wx0 * v00.w + wx1 * v01.w) + wy1 * (wx0 * v10.w + wx1 * v11.w);
+        o.x = up2_blend(v00.x, v01.x, v10.x, v11.x, wx0, wx1, wy0, wy1);
+        o.y = up2_blend(v00.y, v01.y, v10.y, v11.y, wx0, wx1, wy0, wy1);
+        o.z = up2_blend(v00.z, v01.z, v10.z, v11.z, wx0, wx1, wy0, wy1);
+        o.w = up2_blend(v00.w, v01.w, v10.w, v11.w, wx0, wx1, wy0, wy1);
         if (a.y_bf16) {
             uint2 q;
             q.x = TSNET_CVT_PK_BF16(o.x, o.y);
