@@ -19,7 +19,9 @@
  * tsnet_op_fuse_tail_slots -- its kernels one at a time; tsnet_forward_u8, tsnet_set_sources_u8, tsnet_forward_target_u8, tsnet_bank_put_u8,
  * tsnet_forward_bank_u8, tsnet_op_pack_input_u8, tsnet_prepare_frames_u8 -- compact (byte) inputs; tsnet_paste_frames -- generated frames
  * back into the video frames; tsnet_prepare_frames_boxes, tsnet_prepare_frames_boxes_u8, tsnet_paste_frames_boxes -- the same with a box per frame;
- * tsnet_face_labels_boxes, tsnet_face_labels_boxes_u8 -- the face labels of a clip with a crop per frame, frames of different sizes in one pass.
+ * tsnet_face_labels_boxes, tsnet_face_labels_boxes_u8 -- the face labels of a clip with a crop per frame, frames of different sizes in one pass;
+ * tsnet_op_upconv2d -- the decoder's up-convolution as one operator; tsnet_op_conv2d_epi -- a convolution with its epilogue's statistics, addend,
+ * published maximum, device-derived operand scale and bf16 storage, as the forward calls it.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -31,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8), tsnet_op_upconv2d; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
+#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8), tsnet_op_upconv2d, tsnet_op_conv2d_epi; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
 #define TSNET_MAX_SOURCES 8
 
 enum {
@@ -236,6 +238,10 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  *   upsampled tensor never exists), 1 = tsnet_op_upsample2x into a scratch tensor, then tsnet_op_conv2d with the same tile -- the same bits
  *   (tested).  tile: 0, 64 or 128.  2H and 2W must split into 4 x 32 tiles.  Zero padding, another kernel size or stride, nprod != 3, or a
  *   frame / tile the fused form is not built for return TSNET_ERR_ARG on BOTH routes, with nothing launched.
+ * tsnet_op_conv2d_epi <- tsnet_op_conv2d with the epilogue's optional parts (struct tsnet_conv_epi, documented at its declaration below): the addend
+ *   of a split convolution, the fp64 InstanceNorm partials and alpha / beta on either finalize route, max |y| per image, the operand scale derived
+ *   on the device from a published max |x|, bf16 storage of x / y.  With every part off it is tsnet_op_conv2d; with any of them on, y has the
+ *   bits tsnet_op_conv2d gives on the same kernel and tile (plus the addend: one fp32 addition).
  * tsnet_op_conv2d_cat <- the same on torch.cat((x, x2), channel axis) formed on load (dec.map_conv on cat(pg, sg), TSNet.py:163):
  *   x (N,H,W,C1), x2 (x2_nmod,H,W,C2) read at image n % x2_nmod; C1 a multiple of 16.  No input transform.
  * tsnet_op_head <- the decoder's RGB head: ReflectionPad2d(3) + Conv2d(C -> 3, 7x7) + bias + Tanh (TSNet.py:151-152) on relu(alpha*x+beta),
@@ -299,6 +305,42 @@ int tsnet_op_upconv2d(const float* x, int N, int H, int W, int Cin,
                       const float* w_oihw, const float* bias, int Cout, int ksize, int stride, int pad, int pad_mode,
                       const float* in_alpha, const float* in_beta, int in_relu, float bound, int nprod, int kernel, int tile,
                       float* y, void* stream);
+/* tsnet_op_conv2d_epi: tsnet_op_conv2d as the forward calls it -- with what the convolutions' shared epilogue (csrc/conv_common.hpp conv_epilogue)
+ * does beside storing y.  Every pointer of the struct is a DEVICE pointer unless it says host; a null pointer switches its part off.  The plan
+ * is made first and every scratch size is checked against it before anything is launched; the call returns after the stream has drained. */
+#define TSNET_CONV_EPI_INFO 8
+typedef struct tsnet_conv_epi {
+    int stats;                     /* 0 = no statistics; 1 = fp64 partials per (tile, channel), then the finalize launch (in_finalize2); 2 = the arrival
+                                    * counters offered as the forward offers them: up to 32 tiles per image the last-arriving workgroup of an (image,
+                                    * channel tile) writes alpha / beta itself, above that the finalize launch runs as for 1 */
+    int repeat;                    /* >= 1 launches back to back on the same buffers; before EACH the op fills `part` with 0xFF bytes (every double a
+                                    * NaN) and zeroes amax_out, on the stream */
+    double* part;                  /* (N * tpi, Cout, 2): sum and sum of squares of y over the tile's positions; tpi = tiles per image of the plan */
+    long long part_capacity;       /* doubles `part` holds; N * tpi * Cout * 2 are needed */
+    float* alpha; float* beta;     /* out, (N * Cout) each: 1 / sqrt(var + 1e-5), -mean * alpha (tsnet_op_instnorm_stats' definition) */
+    int* counters;                 /* stats = 2: 65536 ints, ZERO on entry; the finalizing workgroups leave them zero */
+    int* counters_nonzero_out;     /* HOST int: counters that are not zero after the last launch has drained */
+    const float* addend;           /* (add_nmod, Ho, Wo, Cout): y += addend[image % add_nmod], one fp32 addition (the shared half of a split convolution) */
+    int add_nmod;                  /* must divide N */
+    unsigned int* amax_out;        /* (N): float bits of max |y| of each image */
+    const unsigned int* in_amax;   /* (N): float bits of max |x| per image; the operand scale of image n is derived on the device from */
+    float bound_add;               /*      in_amax[n] + bound_add, and `bound` is not used (nprod = 1 has no scale: ignored) */
+    int x_bf16, y_bf16;            /* bf16 storage (nprod = 1): x / y hold bf16 -- widened exactly on load; the fp32 value rounded to nearest even on
+                                    * store, the statistics and amax_out still taken from the fp32 values */
+    int* info_out;                 /* HOST, TSNET_CONV_EPI_INFO ints: the plan -- kernel family (csrc/conv_plan.hpp ConvFamily: 0 H2R, 1 G64, 2 H2, 3 H2S,
+                                    * 4 H2S32, 5 H2D, 6 W1), tiles per image, 1 if alpha / beta were written in the kernel, conv_w1's tiles per workgroup,
+                                    * 1 if its chunks may cross images, the tile's rows (patch families: rows of a rows x 32 pixel rectangle, tiles in
+                                    * row-major order inside an image; general kernels: consecutive output positions of an image), its width in
+                                    * channels, channel tiles */
+} tsnet_conv_epi;
+/* TSNET_ERR_ARG with a message, nothing of the convolution launched and y / part / alpha / beta untouched: what tsnet_op_conv2d refuses; part_capacity
+ * below N * tpi * Cout * 2; stats = 2 with more than 65536 (image, 32-channel group) pairs; stats != 0 without part, alpha or beta, stats = 2 without
+ * counters; add_nmod that does not divide N; repeat < 1; bf16 storage with nprod != 1; x_bf16 on a layer that runs the Winograd form or a 7 x 7 stem
+ * kernel (no bf16 load is built there). */
+int tsnet_op_conv2d_epi(const float* x, int N, int H, int W, int Cin,
+                        const float* w_oihw, const float* bias, int Cout, int ksize, int stride, int pad, int pad_mode,
+                        const float* in_alpha, const float* in_beta, int in_relu, float bound, int nprod, int kernel, int tile,
+                        float* y, const tsnet_conv_epi* epi, void* stream);
 int tsnet_op_conv2d_cat(const float* x, const float* x2, int N, int H, int W, int C1, int C2, int x2_nmod,
                         const float* w_oihw, const float* bias, int Cout, int ksize, int stride, int pad, int pad_mode,
                         float bound, int nprod, float* y, void* stream);

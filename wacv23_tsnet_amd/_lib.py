@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "tsnet_paste_frames",
     "tsnet_prepare_frames_boxes", "tsnet_prepare_frames_boxes_u8", "tsnet_paste_frames_boxes",
     "tsnet_face_labels_boxes", "tsnet_face_labels_boxes_u8",
-    "tsnet_op_upconv2d",
+    "tsnet_op_upconv2d", "tsnet_op_conv2d_epi",
 )
 
 
@@ -53,6 +53,16 @@ class TsnetCfg(C.Structure):
 
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
+CONV_EPI_INFO = 8
+
+
+class TsnetConvEpi(C.Structure):
+    """struct tsnet_conv_epi (include/tsnet_abi.h): the optional parts of tsnet_op_conv2d_epi; device pointers as integers."""
+    _fields_ = [
+        ("stats", C.c_int), ("repeat", C.c_int), ("part", _vp), ("part_capacity", C.c_longlong), ("alpha", _vp), ("beta", _vp),
+        ("counters", _vp), ("counters_nonzero_out", C.POINTER(C.c_int)), ("addend", _vp), ("add_nmod", C.c_int), ("amax_out", _vp),
+        ("in_amax", _vp), ("bound_add", C.c_float), ("x_bf16", C.c_int), ("y_bf16", C.c_int), ("info_out", C.POINTER(C.c_int)),
+    ]
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
@@ -156,6 +166,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
             fn.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, C.c_int, _vp, _vp, _vp]
     if hasattr(lib, "tsnet_op_upconv2d"):        # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
         lib.tsnet_op_upconv2d.argtypes = lib.tsnet_op_conv2d.argtypes
+    if hasattr(lib, "tsnet_op_conv2d_epi"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_op_conv2d_epi.argtypes = lib.tsnet_op_conv2d.argtypes[:-1] + [C.POINTER(TsnetConvEpi), _vp]
     return lib
 
 

@@ -41,6 +41,8 @@ struct ConvShape {
     bool fin_counter = false;    // output statistics with arrival counters supplied: the in-kernel finalize is possible
     bool up2 = false;            // the input tensor is the HALF-resolution map (N, H/2, W/2, cin): the kernel forms its bilinear x2 upsample while it
                                  // stages the patch (conv_h2.hpp UP2); H and W stay the extent the convolution sees
+    bool x_bf16 = false;         // bf16 storage: the input tensor holds bf16 (conv_common.hpp load_x_octet).  Built into conv_h2's 3 x 3 kernels
+                                 // (stride 1 and 2), conv_h2r and conv_g64; the Winograd form and the 7 x 7 stems load fp32 and nothing else
     int ho() const { return (H + 2 * pad - ks) / stride + 1; }
     int wo() const { return (W + 2 * pad - ks) / stride + 1; }
 };
@@ -241,6 +243,10 @@ inline ConvPlan plan_conv(const ConvShape& s, const ConvRequest& r, int cus) {
     // the half-resolution input: the 3 x 3 / stride-1 patch kernel's reflection-padded fp16 x 2 form and nothing else (checked further in case H2)
     if (s.up2 && (p.family != ConvFamily::H2 || !s.reflect || s.nprod != 3 || (s.H & 1) || (s.W & 1)))
         throw std::invalid_argument("conv: a half-resolution input (fused x2 upsample) needs the 3x3 / stride-1 patch kernel, reflection padding, fp16 x 2 operands (three products) and an even frame");
+    // a bf16-stored input: the families without a bf16 load would read an fp32 descriptor over bf16 bytes (these three never become another
+    // family below).  The forward never asks: its stems read the packed fp32 input and the bf16 modes keep the direct kernels.
+    if (s.x_bf16 && (p.family == ConvFamily::W1 || p.family == ConvFamily::H2S || p.family == ConvFamily::H2S32))
+        throw std::invalid_argument("conv: a bf16-stored input is not built for the Winograd form or the 7x7 stem kernels (they load fp32): the 3x3 patch kernels and the general kernels take it");
     if (s.nprod != 1 && s.nprod != 3 && (s.nprod != 4 || p.family != ConvFamily::H2))
         throw std::invalid_argument("conv: 1 (bf16 operands), 16 (fp16 operands) or 3 products; four on the 3x3 / stride-1 patch kernel's plain 4x64 and 4x128 tiles");
     if (s.f16 && s.nprod != 1) throw std::invalid_argument("conv: fp16 operands (one fp16 plane) run one product");

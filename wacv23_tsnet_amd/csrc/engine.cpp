@@ -255,7 +255,7 @@ ConvShape conv_shape(const ConvLayer& L, const ConvCall& c) {
     sh.ks = L.ks; sh.stride = L.stride; sh.pad = L.pad; sh.reflect = L.reflect; sh.cin = L.cin_pad; sh.cout = L.cout; sh.npad = L.npad; sh.kpad = L.kpad;
     sh.form = L.form; sh.N = c.N; sh.H = c.H; sh.W = c.W; sh.csplit = c.x2 ? c.csplit : 0; sh.x2_nmod = c.x2_nmod > 0 ? c.x2_nmod : 1;
     sh.transform = c.alpha != nullptr; sh.nprod = f16 ? 1 : c.nprod; sh.f16 = f16; sh.fin_counter = c.stat_part && c.fin_counter;
-    sh.up2 = c.up2;
+    sh.up2 = c.up2; sh.x_bf16 = c.x_bf16 != 0;
     return sh;
 }
 
@@ -1680,6 +1680,67 @@ int tsnet_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w
     ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
     run_conv(ctx, op.L, c, req);
     HIP_TRY(hipStreamSynchronize(s));
+    OP_END
+}
+
+// The convolution as the forward calls it: tsnet_op_conv2d plus what conv_epilogue does beside storing y.  Everything the launches index is
+// sized from the plan BEFORE the first one; a refusal leaves y, the partials and alpha / beta as they were.
+int tsnet_op_conv2d_epi(const float* x, int N, int H, int W, int Cin, const float* w_oihw, const float* bias, int Cout,
+                        int ksize, int stride, int pad, int pad_mode, const float* in_alpha, const float* in_beta, int in_relu,
+                        float bound, int nprod, int kernel, int tile, float* y, const tsnet_conv_epi* epi, void* stream) {
+    OP_BEGIN
+    if (!x || !w_oihw || !y || !epi) throw ArgError("null tensor");
+    if (nprod != 1 && nprod != 3 && nprod != 4 && nprod != TSNET_NPROD_F16) throw ArgError("conv2d op: nprod must be 1 (bf16 operands), 16 (fp16 operands: one fp16 plane), 3 or 4 products");
+    const tsnet_conv_epi& e = *epi;
+    if (e.stats < 0 || e.stats > 2) throw ArgError("conv2d_epi op: stats must be 0 (none), 1 (partials + finalize launch) or 2 (arrival counters offered)");
+    if (e.repeat < 1) throw ArgError("conv2d_epi op: repeat must be at least 1");
+    if (e.stats && (!e.part || !e.alpha || !e.beta)) throw ArgError("conv2d_epi op: statistics need part, alpha and beta");
+    if (e.stats == 2 && !e.counters) throw ArgError("conv2d_epi op: stats = 2 needs the arrival counters");
+    if (e.addend && (e.add_nmod < 1 || N % e.add_nmod)) throw ArgError("conv2d_epi op: add_nmod must divide N");
+    if ((e.x_bf16 || e.y_bf16) && nprod != 1) throw ArgError("conv: bf16 storage goes with bf16 operands");
+    hipStream_t s = (hipStream_t)stream;
+    Ctx ctx(s, current_device_cus());
+    ConvRequest req;
+    try { req = decode_tile_code(kernel, tile); } catch (const std::invalid_argument& ex) { throw ArgError(ex.what()); }
+    OpLayer op(w_oihw, bias, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, kernel == 3 ? 1 : 0);
+    ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
+    c.addend = e.addend; c.add_nmod = e.addend ? e.add_nmod : 1;
+    c.amax_out = e.amax_out; c.in_amax = e.in_amax; c.bound_add = e.bound_add; c.x_bf16 = e.x_bf16; c.y_bf16 = e.y_bf16;
+    if (e.stats) {                                      // tsnet_engine::conv_stats' request; stats = 1 withholds the counters
+        c.stat_part = e.part; c.fin_alpha = e.alpha; c.fin_beta = e.beta; c.fin_counter = e.stats == 2 ? e.counters : nullptr;
+    }
+    if (in_alpha && !in_beta) throw ArgError("conv: alpha without beta");
+    ConvPlan p;
+    try { p = plan_conv(conv_shape(op.L, c), req, ctx.cus); } catch (const std::invalid_argument& ex) { throw ArgError(ex.what()); }
+    const size_t part_n = stat_part_doubles((size_t)N, (size_t)p.tpi, (size_t)Cout);
+    if (e.stats && (e.part_capacity < 0 || part_n > (size_t)e.part_capacity))
+        throw ArgError("conv2d_epi op: part holds " + std::to_string(e.part_capacity) + " doubles, the plan writes N * tpi * Cout * 2 = " + std::to_string(part_n));
+    if (e.stats == 2 && (size_t)N * ((op.L.npad + 31) / 32) > kFinCounterInts)
+        throw ArgError("conv2d_epi op: more (image, 32-channel group) pairs than arrival counters");
+    const int hw = conv_shape(op.L, c).ho() * conv_shape(op.L, c).wo();
+    for (int it = 0; it < e.repeat; ++it) {
+        // every partial a NaN before each launch: an entry folded before its store is visible, or never written, shows in alpha / beta
+        if (e.stats) HIP_TRY(hipMemsetAsync(e.part, 0xFF, part_n * sizeof(double), s));
+        if (e.amax_out) HIP_TRY(hipMemsetAsync(e.amax_out, 0, (size_t)N * sizeof(unsigned), s));
+        run_conv(ctx, op.L, c, req);
+        if (c.stat_S > 0) {                             // not finalised in the kernel: conv_stats' launch
+            hipLaunchKernelGGL(in_finalize2_kernel, dim3((Cout + kFin2Ch - 1) / kFin2Ch, N), dim3(256), 0, s, e.part, e.alpha, e.beta, Cout, c.stat_S, hw, 1e-5f);
+            check_launch("in_finalize2");
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (e.counters && e.counters_nonzero_out) {
+        std::vector<int> hc(kFinCounterInts);
+        HIP_TRY(hipMemcpy(hc.data(), e.counters, kFinCounterInts * sizeof(int), hipMemcpyDefault));
+        int nz = 0;
+        for (int v : hc) nz += v != 0;
+        *e.counters_nonzero_out = nz;
+    }
+    if (e.info_out) {
+        int* o = e.info_out;
+        o[0] = (int)p.family; o[1] = p.tpi; o[2] = (e.stats && c.stat_S < 0) ? 1 : 0; o[3] = p.w1_chunk; o[4] = p.w1_tab2;
+        o[5] = p.rows; o[6] = p.width; o[7] = p.tiles_n;
+    }
     OP_END
 }
 
