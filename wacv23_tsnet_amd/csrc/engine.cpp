@@ -36,46 +36,27 @@
 #include <vector>
 
 #include "../../include/tsnet_abi.h"
+#include "entry_common.hpp"
 #include "conv_plan.hpp"
 #include "kernels.hpp"
-#include "lmfit.hpp"
-#include "face_adapt.hpp"
 #include "flow_warp.hpp"
-#include "frames.hpp"
-#include "paste.hpp"
 #include "head_conv.hpp"
 #include "norm_elementwise.hpp"
 #include "pack_weights.hpp"
 #include "postproc.hpp"
-#include "raster.hpp"
-#include "track_labels.hpp"
 #include "train_extras.hpp"
 
 using namespace tsnet;
 
 namespace {
 
-thread_local std::string g_op_error;
 int64_t g_launch_counters[4] = {0, 0, 0, 0};   // conv launches: [0] patch kernels (conv_h2.hpp), [1] general kernel (conv_h2r.hpp), [2] RGB head;
                                                // [3] = tile code (rows * 1000 + width, + 20000 two K groups) of the last ResnetBlock-class convolution launch
 std::string g_create_error;
 
-#define HIP_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e__ = (expr);                                                                    \
-        if (e__ != hipSuccess) {                                                                    \
-            char buf__[512];                                                                        \
-            snprintf(buf__, sizeof buf__, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            throw std::runtime_error(buf__);                                                        \
-        }                                                                                           \
-    } while (0)
-
 #ifdef TSNET_TOOLS
 int g_tools_knob[8] = {3, 0, 0, 0, 0, 0, 0, 0};     // tools build only (tsnet_tools_set): [0] largest conv_w1 chunk the launcher may choose; [1] != 0: the decoder never takes the fused upsample; [2] != 0 (read when an engine is created): its second up-convolution stays on the direct kernel
 #endif
-struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct WeightError : std::runtime_error { using std::runtime_error::runtime_error; };
-
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static_assert(kPlanTileRows == kPatchRows && kPlanTileCols == kPatchCols, "conv_plan.hpp's patch tile is conv_common.hpp's");
 // CUs of the current device (MI355X: 256 in 8 XCDs -- the XCD count is part of the kernels' block -> tile maps, conv_common.hpp; the CU count
@@ -160,18 +141,6 @@ struct TimeScope {
     TimeScope(Ctx& c_, int cls) : c(c_) { if (c.timing) c.timing->begin(cls, c.stream); }
     ~TimeScope() { if (c.timing) { try { c.timing->end(c.stream); } catch (...) {} } }
 };
-
-inline void check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + " launch failed: " + hipGetErrorString(e));
-}
-
-inline int ew_grid(size_t total, int block = 256) {
-    size_t g = (total + block - 1) / block;
-    if (g > 256 * 8) g = 256 * 8;    // grid-stride above ~8 blocks per CU
-    if (g < 1) g = 1;
-    return (int)g;
-}
 
 void launch_finalize_impl(const double* part, float* alpha, float* beta, int N, int C, int S, int HW, hipStream_t s);
 inline void launch_finalize(const double* part, float* alpha, float* beta, int N, int C, int S, int HW, hipStream_t s) { launch_finalize_impl(part, alpha, beta, N, C, S, HW, s); }
@@ -1622,12 +1591,6 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
 // single operators
 const char* tsnet_op_last_error(void) { return g_op_error.c_str(); }
 
-#define OP_BEGIN try {
-#define OP_END                                                                   \
-    } catch (const ArgError& e) { g_op_error = e.what(); return TSNET_ERR_ARG; }  \
-      catch (const std::exception& e) { g_op_error = e.what(); return TSNET_ERR_HIP; } \
-    return TSNET_OK;
-
 namespace {
 // one convolution layer with its own packed weights, for the operator entry points
 struct OpLayer {
@@ -2139,184 +2102,6 @@ int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta
     OP_END
 }
 
-int tsnet_frame_stats(const float* x, int B, int C, int HW, float div, float* mean, float* std_unbiased, void* stream) {
-    OP_BEGIN
-    if (!x || !mean || !std_unbiased) throw ArgError("frame_stats: null tensor");
-    if (B < 1 || C < 1 || HW < 1 || B > 65535 || !(div > 0.f)) throw ArgError("frame_stats: bad shape or divisor");
-    hipLaunchKernelGGL(frame_stats_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, C, HW, div, mean, std_unbiased);
-    check_launch("frame_stats");
-    OP_END
-}
-
-int tsnet_demo_postprocess(const float* rec, int B, int H, int W, const float* gen_mean, const float* gen_std,
-                           const float* ref_mean, const float* ref_std, const float* img_mean_over_255,
-                           unsigned char* out_rgb, void* stream) {
-    OP_BEGIN
-    if (!rec || !gen_mean || !gen_std || !ref_mean || !ref_std || !img_mean_over_255 || !out_rgb) throw ArgError("demo_postprocess: null tensor");
-    if (B < 1 || H < 1 || W < 1) throw ArgError("demo_postprocess: bad shape");
-    DemoPostArgs a{rec, gen_mean, gen_std, ref_mean, ref_std, {img_mean_over_255[0], img_mean_over_255[1], img_mean_over_255[2]},
-                   out_rgb, B, H * W};
-    hipLaunchKernelGGL(demo_post_kernel, dim3(ew_grid((size_t)B * H * W)), dim3(256), 0, (hipStream_t)stream, a);
-    check_launch("demo_post");
-    OP_END
-}
-
-int tsnet_fit_face_curves(const double* keypoints, int F, double* curves) {
-    OP_BEGIN
-    if (!keypoints || !curves || F < 1) throw ArgError("fit_face_curves: bad argument");
-    for (int f = 0; f < F; ++f)
-        for (int e = 0; e < kFaceSubEdges; ++e) {
-            double pts[6];
-            const int n = hFaceSubEdgeTable[e][2] < 0 ? 2 : 3;
-            for (int i = 0; i < n; ++i) {
-                const double* k = keypoints + ((size_t)f * kFaceKeypoints + hFaceSubEdgeTable[e][i]) * 2;
-                pts[2 * i] = k[0]; pts[2 * i + 1] = k[1];
-            }
-            lm::fit_piece(pts, n, curves + ((size_t)f * kFaceSubEdges + e) * kCurveRec);
-        }
-    OP_END
-}
-
-// key-point preparation of a cross-identity face pair (csrc/face_adapt.hpp): host arithmetic, no device work
-int tsnet_face_adapt_stats(const double* kp, int F, double* stats) {
-    OP_BEGIN
-    if (const char* err = face_adapt::stats(kp, F, stats)) throw ArgError(err);
-    OP_END
-}
-
-int tsnet_face_adapt_apply(const double* stats, double* kp, int F) {
-    OP_BEGIN
-    if (const char* err = face_adapt::apply(stats, kp, F)) throw ArgError(err);
-    OP_END
-}
-
-int tsnet_smooth_keypoints(const double* in, int F, int P, double* out) {
-    OP_BEGIN
-    if (const char* err = face_adapt::smooth(in, F, P, out)) throw ArgError(err);
-    OP_END
-}
-
-int tsnet_fit_pose_curves(const double* pts, int F, int flags, double* curves) {
-    OP_BEGIN
-    if (!pts || !curves || F < 1) throw ArgError("fit_pose_curves: bad argument");
-    for (int f = 0; f < F; ++f) {
-        const double* P = pts + (size_t)f * kPosePts * 2;
-        for (int e = 0; e < kPosePrims; ++e) {
-            double* rec = curves + ((size_t)f * kPosePrims + e) * kCurveRec;
-            for (int i = 0; i < kCurveRec; ++i) rec[i] = 0.0;
-            int ia = 0, ib = 0;
-            if (!pose_primitive_points(e, flags, ia, ib)) continue;
-            const double two[4] = {P[2 * ia], P[2 * ia + 1], P[2 * ib], P[2 * ib + 1]};
-            if (two[0] == 0.0 || two[2] == 0.0) continue;               // `0 not in x` (connect_keypoints): a missing point
-            lm::fit_piece(two, 2, rec);
-        }
-    }
-    OP_END
-}
-
-int tsnet_raster_face(const double* keypoints, const double* curves, int F, int h, int w, int bw, unsigned char* edges, unsigned char* bbox, void* stream) {
-    OP_BEGIN
-    if ((!edges && !bbox) || (edges && !curves) || (bbox && !keypoints)) throw ArgError("raster_face: null tensor");
-    if (F < 1 || F > 65535 || h < 1 || w < 1 || bw < 1 || (double)h * w >= 2147483647.0) throw ArgError("raster_face: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    if (edges) {
-        HIP_TRY(hipMemsetAsync(edges, 0, (size_t)F * h * w, s));
-        hipLaunchKernelGGL(face_edges_kernel, dim3(kFaceSubEdges, F), dim3(64), 0, s, curves, edges, h, w, bw);
-        check_launch("face_edges");
-    }
-    if (bbox) {
-        hipLaunchKernelGGL(face_bbox_kernel, dim3(F), dim3(256), 0, s, keypoints, bbox, h, w);
-        check_launch("face_bbox");
-    }
-    OP_END
-}
-
-int tsnet_raster_pose(const double* pts, const double* curves, int F, int h, int w, int win_x0, int win_y0, int win_x1, int win_y1, int flags,
-                      unsigned char* labels, void* stream) {
-    OP_BEGIN
-    if (!pts || !curves || !labels) throw ArgError("raster_pose: null tensor");
-    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w >= 2147483647.0) throw ArgError("raster_pose: bad shape");
-    if (win_x0 < 0 || win_y0 < 0 || win_x1 > w || win_y1 > h || win_x1 <= win_x0 || win_y1 <= win_y0) throw ArgError("raster_pose: window outside the frame");
-    if (((uintptr_t)labels & 3) != 0) throw ArgError("raster_pose: labels must be 4-byte aligned (and padded to a multiple of 4 bytes)");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n = (size_t)F * (win_y1 - win_y0) * (win_x1 - win_x0), n4 = (n + 3) / 4 * 4;
-    HIP_TRY(hipMemsetAsync(labels, 0, n4, s));
-    hipLaunchKernelGGL(pose_edges_kernel, dim3(kPosePrims, F), dim3(64), 0, s, pts, curves, labels, h, w, win_x0, win_y0, win_x1, win_y1, flags);
-    check_launch("pose_edges");
-    hipLaunchKernelGGL(pose_order_to_class_kernel, dim3(ew_grid(n)), dim3(256), 0, s, labels, n);
-    check_launch("pose_order_to_class");
-    OP_END
-}
-
-int tsnet_label_bbox(const unsigned char* labels, int F, int h, int w, unsigned char* bbox, void* stream) {
-    OP_BEGIN
-    if (!labels || !bbox) throw ArgError("label_bbox: null tensor");
-    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w >= 2147483647.0) throw ArgError("label_bbox: bad shape");
-    hipLaunchKernelGGL(label_bbox_kernel, dim3(F), dim3(256), 0, (hipStream_t)stream, labels, bbox, h, w);
-    check_launch("label_bbox");
-    OP_END
-}
-
-int tsnet_resize_pad(const unsigned char* in, int F, int h, int w, const int* ytab, const int* xtab, int oh, int ow,
-                     int pad_top, int pad_left, int OH, int OW, int binarise, float* out, void* stream) {
-    OP_BEGIN
-    if (!in || !ytab || !xtab || !out) throw ArgError("resize_pad: null tensor");
-    if (F < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || pad_top < 0 || pad_left < 0 || pad_top + oh > OH || pad_left + ow > OW)
-        throw ArgError("resize_pad: bad shape");
-    hipLaunchKernelGGL(gather_pad_kernel, dim3(ew_grid((size_t)F * OH * OW)), dim3(256), 0, (hipStream_t)stream, in, F, h, w, ytab, xtab, oh, ow,
-                       pad_top, pad_left, OH, OW, out, binarise);
-    check_launch("gather_pad");
-    OP_END
-}
-
-int tsnet_resize_label(const unsigned char* in, int F, int h, int w, int OH, int OW, const double* wts_rows, int lw_rows,
-                       const double* wts_cols, int lw_cols, float* out, void* stream) {
-    OP_BEGIN
-    if (!in || !out) throw ArgError("resize_label: null tensor");
-    if (F < 1 || h < 1 || w < 1 || OH < 1 || OW < 1) throw ArgError("resize_label: bad shape");
-    if (lw_rows < -1 || lw_cols < -1 || lw_rows > 63 || lw_cols > 63 || (lw_rows >= 0 && !wts_rows) || (lw_cols >= 0 && !wts_cols))
-        throw ArgError("resize_label: bad Gaussian kernel");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n = (size_t)F * h * w;
-    unsigned char *t0 = nullptr, *t1 = nullptr;
-    double* dw = nullptr;
-    int* mm = nullptr;
-    struct Guard { unsigned char*& a; unsigned char*& b; double*& c; int*& d; ~Guard() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); } } guard{t0, t1, dw, mm};
-    const unsigned char* cur = in;
-    // anti-aliasing passes: one per axis that shrinks (lw >= 0); the caller supplies the kernel halves (centre first) it computed in fp64
-    for (int axis = 0; axis < 2; ++axis) {
-        const int lw = axis ? lw_cols : lw_rows;
-        const double* wts = axis ? wts_cols : wts_rows;
-        if (lw < 0) continue;
-        unsigned char*& dst = (cur == t0) ? t1 : t0;
-        if (!dst) HIP_TRY(hipMalloc((void**)&dst, n));
-        if (!dw) HIP_TRY(hipMalloc((void**)&dw, 2 * 64 * sizeof(double)));
-        HIP_TRY(hipMemcpyAsync(dw + axis * 64, wts, (lw + 1) * sizeof(double), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(gauss1d_u8_kernel, dim3(ew_grid(n)), dim3(256), 0, s, cur, dst, F, h, w, axis, dw + axis * 64, lw);
-        check_launch("gauss1d_u8");
-        cur = dst;
-    }
-    HIP_TRY(hipMalloc((void**)&mm, (size_t)2 * F * sizeof(int)));
-    std::vector<int> init(2 * F);
-    for (int f = 0; f < F; ++f) { init[2 * f] = 255; init[2 * f + 1] = 0; }
-    HIP_TRY(hipMemcpyAsync(mm, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(u8_minmax_kernel, dim3(std::min(64, (h * w + 255) / 256), F), dim3(256), 0, s, cur, F, h * w, mm);
-    check_launch("u8_minmax");
-    hipLaunchKernelGGL(resize_label_kernel, dim3(ew_grid((size_t)F * OH * OW)), dim3(256), 0, s, cur, F, h, w, OH, OW, mm, out);
-    check_launch("resize_label");
-    HIP_TRY(hipStreamSynchronize(s));                                  // host temporaries (init, the caller's kernels) and device scratch end here
-    OP_END
-}
-
-int tsnet_vl2ch(const float* labels, int B, int HW, int num_classes, float* out, void* stream) {
-    OP_BEGIN
-    if (!labels || !out) throw ArgError("vl2ch: null tensor");
-    if (B < 1 || HW < 1 || num_classes < 1) throw ArgError("vl2ch: bad shape");
-    hipLaunchKernelGGL(onehot_kernel, dim3(ew_grid((size_t)B * num_classes * HW)), dim3(256), 0, (hipStream_t)stream, labels, out, B, HW, num_classes);
-    check_launch("onehot");
-    OP_END
-}
-
 int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int pad_mode, int norm,
                      int variant, int iters, float* ms_out, void* stream) {
     OP_BEGIN
@@ -2377,280 +2162,7 @@ void tsnet_debug_counters(int64_t out[4], int reset) {
 void tsnet_linspace(int n, float* out) { linspace_pm1(n, out); }
 void tsnet_coord_table(int H, int W, float* out) { coord_table(H, W, out); }
 
-int tsnet_bicubic_taps(int n_in, int n_out) {
-    if (n_in < 1 || n_out < 1) { g_op_error = "bicubic_taps: sizes must be positive"; return TSNET_ERR_ARG; }
-    return bicubic_taps(n_in, n_out);
-}
-
-int tsnet_bicubic_table(int n_in, int n_out, int* first, int* count, int* coef) {
-    OP_BEGIN
-    if (n_in < 1 || n_out < 1 || !first || !count || !coef) throw ArgError("bicubic_table: bad argument");
-    bicubic_table(n_in, n_out, first, count, coef);
-    OP_END
-}
-
-// mean_bgr null: the byte form (out holds (F,3,OH,OW) bytes)
-static void prepare_frames_any(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
-                               const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
-                               const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
-                               int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, void* out, bool u8, void* stream) {
-    if (!frames || !out || (!u8 && !mean_bgr)) throw ArgError("prepare_frames: null tensor");
-    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("prepare_frames: bad frame shape");
-    if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000) throw ArgError("prepare_frames: empty or absurd crop box");
-    if (oh < 1 || ow < 1 || pad_top < 0 || pad_left < 0 || pad_top + oh > OH || pad_left + ow > OW || (double)OH * OW >= 2147483647.0 / 4)
-        throw ArgError("prepare_frames: the resized image and its padding do not fit the output");
-    const int cw = x1 - x0, ch = y1 - y0;
-    if (ow != cw && (!xfirst || !xcount || !xcoef)) throw ArgError("prepare_frames: the horizontal pass needs its tables");
-    if (oh != ch && (!yfirst || !ycount || !ycoef)) throw ArgError("prepare_frames: the vertical pass needs its tables");
-    // a table row holds `taps` coefficients: fewer than the size ratio needs (count > taps) cannot be a table of tsnet_bicubic_table
-    if (ow != cw && xtaps != bicubic_taps(cw, ow)) throw ArgError("prepare_frames: xtaps is not tsnet_bicubic_taps(x1 - x0, ow)");
-    if (oh != ch && ytaps != bicubic_taps(ch, oh)) throw ArgError("prepare_frames: ytaps is not tsnet_bicubic_taps(y1 - y0, oh)");
-    int th = kFrTileH;
-    while (th > 1 && frames_row_span(ch, oh, th) > kFrRows) th >>= 1;
-    if (frames_row_span(ch, oh, th) > kFrRows) throw ArgError("prepare_frames: vertical reduction too steep (more than 112 taps)");
-    const int gy = (OH + th - 1) / th;
-    if (gy > 65535) throw ArgError("prepare_frames: output too tall");
-    FrameArgs a{frames, static_cast<float*>(out), xfirst, xcount, xcoef, yfirst, ycount, ycoef, h, w, x0, y0, cw, ch, ow, oh, xtaps, ytaps, pad_top, pad_left, OH, OW, th,
-                {u8 ? 0.f : mean_bgr[0], u8 ? 0.f : mean_bgr[1], u8 ? 0.f : mean_bgr[2]}};
-    const dim3 grid((OW + kFrTileW - 1) / kFrTileW, gy, F);
-    if (u8) hipLaunchKernelGGL(prepare_frames_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(prepare_frames_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    check_launch("prepare_frames");
-}
-
-int tsnet_prepare_frames(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
-                         const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
-                         const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
-                         int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream) {
-    OP_BEGIN
-    prepare_frames_any(frames, F, h, w, x0, y0, x1, y1, xfirst, xcount, xcoef, xtaps, yfirst, ycount, ycoef, ytaps, oh, ow, pad_top, pad_left, OH, OW,
-                       mean_bgr, out, false, stream);
-    OP_END
-}
-
-int tsnet_prepare_frames_u8(const unsigned char* frames, int F, int h, int w, int x0, int y0, int x1, int y1,
-                            const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
-                            const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
-                            int oh, int ow, int pad_top, int pad_left, int OH, int OW, unsigned char* out, void* stream) {
-    OP_BEGIN
-    prepare_frames_any(frames, F, h, w, x0, y0, x1, y1, xfirst, xcount, xcoef, xtaps, yfirst, ycount, ycoef, ytaps, oh, ow, pad_top, pad_left, OH, OW,
-                       nullptr, out, true, stream);
-    OP_END
-}
-
-int tsnet_paste_frames(const unsigned char* gen, const unsigned char* mask, int F, int GH, int GW, int sx0, int sy0, int sx1, int sy1,
-                       const int* xfirst, const int* xcount, const int* xcoef, int xtaps,
-                       const int* yfirst, const int* ycount, const int* ycoef, int ytaps,
-                       unsigned char* frames, int h, int w, int x0, int y0, int x1, int y1, void* stream) {
-    OP_BEGIN
-    if (!gen || !frames) throw ArgError("paste_frames: null tensor");
-    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("paste_frames: bad frame shape");
-    if (GH < 1 || GW < 1 || (double)GH * GW * 3 >= 2147483647.0) throw ArgError("paste_frames: bad shape of the generated frames");
-    if (sx0 < 0 || sy0 < 0 || sx1 <= sx0 || sy1 <= sy0 || sx1 > GW || sy1 > GH) throw ArgError("paste_frames: the source rectangle is empty or not inside the generated frame");
-    if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000 || x0 > 1000000 || y0 > 1000000)
-        throw ArgError("paste_frames: empty or absurd box");
-    const int cw = sx1 - sx0, ch = sy1 - sy0, ow = x1 - x0, oh = y1 - y0;
-    if (ow != cw && (!xfirst || !xcount || !xcoef)) throw ArgError("paste_frames: the horizontal pass needs its tables");
-    if (oh != ch && (!yfirst || !ycount || !ycoef)) throw ArgError("paste_frames: the vertical pass needs its tables");
-    if (ow != cw && xtaps != bicubic_taps(cw, ow)) throw ArgError("paste_frames: xtaps is not tsnet_bicubic_taps(sx1 - sx0, x1 - x0)");
-    if (oh != ch && ytaps != bicubic_taps(ch, oh)) throw ArgError("paste_frames: ytaps is not tsnet_bicubic_taps(sy1 - sy0, y1 - y0)");
-    // the rows of the horizontal pass a tile keeps: frames_row_span's bound, and never more than the source rectangle has
-    auto span = [&](int t) { const int s = frames_row_span(ch, oh, t); return s > ch ? ch : s; };
-    int th = kFrTileH;
-    while (th > 1 && span(th) > kFrRows) th >>= 1;
-    if (span(th) > kFrRows) throw ArgError("paste_frames: vertical reduction too steep (more than 112 source rows under one output row)");
-    const int rx0 = x0 < 0 ? 0 : x0, ry0 = y0 < 0 ? 0 : y0, rx1 = x1 > w ? w : x1, ry1 = y1 > h ? h : y1;
-    if (rx0 >= rx1 || ry0 >= ry1) return TSNET_OK;                   // Image.paste: a box outside the frame writes nothing
-    const int gy = (ry1 - ry0 + th - 1) / th;
-    if (gy > 65535) throw ArgError("paste_frames: region too tall");
-    PasteArgs a{gen, mask, frames, xfirst, xcount, xcoef, yfirst, ycount, ycoef, GH, GW, sx0, sy0, cw, ch, h, w, x0, y0, ow, oh, rx0, ry0, rx1, ry1, xtaps, ytaps, th};
-    const dim3 grid((rx1 - rx0 + kFrTileW - 1) / kFrTileW, gy, F);
-    if (mask) hipLaunchKernelGGL(paste_frames_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(paste_frames_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    check_launch("paste_frames");
-    OP_END
-}
-
-// ---- a box per frame: HOST descriptors {x0, y0, x1, y1, xoff, xtaps, yoff, ytaps} are checked here, all of them before anything is launched
-static std::string box_frame(const char* who, int f) { return std::string(who) + ": frame " + std::to_string(f) + ": "; }
-
-// one axis of frame f: n_in -> n_out with its table at `off` in a pool of pool_len ints
-static void check_box_axis(const char* who, int f, const char* axis, int n_in, int n_out, int off, int taps, const int* pool, int pool_len) {
-    if (n_in == n_out) return;                                       // skipped: off and taps are not looked at
-    if (off < 0) throw ArgError(box_frame(who, f) + "the " + axis + " pass needs its table (offset " + std::to_string(off) + ")");
-    if (taps != bicubic_taps(n_in, n_out))
-        throw ArgError(box_frame(who, f) + axis + " taps are not tsnet_bicubic_taps(" + std::to_string(n_in) + ", " + std::to_string(n_out) + ")");
-    if (!pool || (long long)off + (long long)n_out * (2 + (long long)taps) > (long long)pool_len)
-        throw ArgError(box_frame(who, f) + "the " + axis + " table at offset " + std::to_string(off) + " ends beyond the pool of " + std::to_string(pool_len) + " ints");
-}
-
-static void prepare_frames_boxes_any(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev, const int* pool,
-                                     int pool_len, int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, void* out, bool u8,
-                                     void* stream) {
-    const char* who = "prepare_frames_boxes";
-    if (!frames || !out || (!u8 && !mean_bgr) || !boxes_host || !boxes_dev) throw ArgError("prepare_frames_boxes: null tensor");
-    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("prepare_frames_boxes: bad frame shape");
-    if (pool_len < 0) throw ArgError("prepare_frames_boxes: negative pool length");
-    if (oh < 1 || ow < 1 || pad_top < 0 || pad_left < 0 || pad_top + oh > OH || pad_left + ow > OW || (double)OH * OW >= 2147483647.0 / 4)
-        throw ArgError("prepare_frames_boxes: the resized image and its padding do not fit the output");
-    int th = kFrTileH;                                               // one tile height per launch: the smallest any frame needs
-    for (int f = 0; f < F; ++f) {
-        const int* d = boxes_host + (size_t)f * kFrDesc;
-        const int x0 = d[0], y0 = d[1], x1 = d[2], y1 = d[3];
-        if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000)
-            throw ArgError(box_frame(who, f) + "empty or absurd crop box");
-        const int cw = x1 - x0, ch = y1 - y0;
-        check_box_axis(who, f, "horizontal", cw, ow, d[4], d[5], pool, pool_len);
-        check_box_axis(who, f, "vertical", ch, oh, d[6], d[7], pool, pool_len);
-        while (th > 1 && frames_row_span(ch, oh, th) > kFrRows) th >>= 1;
-        if (frames_row_span(ch, oh, th) > kFrRows) throw ArgError(box_frame(who, f) + "vertical reduction too steep (more than 112 taps)");
-    }
-    const int gy = (OH + th - 1) / th;
-    if (gy > 65535) throw ArgError("prepare_frames_boxes: output too tall");
-    FrameBoxArgs b{{frames, static_cast<float*>(out), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h, w, 0, 0, 0, 0, ow, oh, 0, 0, pad_top, pad_left, OH, OW, th,
-                    {u8 ? 0.f : mean_bgr[0], u8 ? 0.f : mean_bgr[1], u8 ? 0.f : mean_bgr[2]}}, boxes_dev, pool, pool_len};
-    const dim3 grid((OW + kFrTileW - 1) / kFrTileW, gy, F);
-    if (u8) hipLaunchKernelGGL(prepare_frames_boxes_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
-    else hipLaunchKernelGGL(prepare_frames_boxes_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
-    check_launch("prepare_frames_boxes");
-}
-
-int tsnet_prepare_frames_boxes(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len,
-                               int oh, int ow, int pad_top, int pad_left, int OH, int OW, const float* mean_bgr, float* out, void* stream) {
-    OP_BEGIN
-    prepare_frames_boxes_any(frames, F, h, w, boxes_host, boxes_dev, pool, pool_len, oh, ow, pad_top, pad_left, OH, OW, mean_bgr, out, false, stream);
-    OP_END
-}
-
-int tsnet_prepare_frames_boxes_u8(const unsigned char* frames, int F, int h, int w, const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len,
-                                  int oh, int ow, int pad_top, int pad_left, int OH, int OW, unsigned char* out, void* stream) {
-    OP_BEGIN
-    prepare_frames_boxes_any(frames, F, h, w, boxes_host, boxes_dev, pool, pool_len, oh, ow, pad_top, pad_left, OH, OW, nullptr, out, true, stream);
-    OP_END
-}
-
-int tsnet_paste_frames_boxes(const unsigned char* gen, const unsigned char* mask, int F, int GH, int GW, int sx0, int sy0, int sx1, int sy1,
-                             const int* boxes_host, const int* boxes_dev, const int* pool, int pool_len, unsigned char* frames, int h, int w, void* stream) {
-    OP_BEGIN
-    const char* who = "paste_frames_boxes";
-    if (!gen || !frames || !boxes_host || !boxes_dev) throw ArgError("paste_frames_boxes: null tensor");
-    if (F < 1 || F > 65535 || h < 1 || w < 1 || (double)h * w * 3 >= 2147483647.0) throw ArgError("paste_frames_boxes: bad frame shape");
-    if (GH < 1 || GW < 1 || (double)GH * GW * 3 >= 2147483647.0) throw ArgError("paste_frames_boxes: bad shape of the generated frames");
-    if (sx0 < 0 || sy0 < 0 || sx1 <= sx0 || sy1 <= sy0 || sx1 > GW || sy1 > GH)
-        throw ArgError("paste_frames_boxes: the source rectangle is empty or not inside the generated frame");
-    if (pool_len < 0) throw ArgError("paste_frames_boxes: negative pool length");
-    const int cw = sx1 - sx0, ch = sy1 - sy0;
-    int th = kFrTileH, rw = 0, rh = 0;                               // one tile height per launch; the largest box ∩ frame
-    for (int f = 0; f < F; ++f) {
-        const int* d = boxes_host + (size_t)f * kFrDesc;
-        const int x0 = d[0], y0 = d[1], x1 = d[2], y1 = d[3];
-        if (x1 <= x0 || y1 <= y0 || (double)x1 - x0 > 1e6 || (double)y1 - y0 > 1e6 || x0 < -1000000 || y0 < -1000000 || x0 > 1000000 || y0 > 1000000)
-            throw ArgError(box_frame(who, f) + "empty or absurd box");
-        const int ow = x1 - x0, oh = y1 - y0;
-        check_box_axis(who, f, "horizontal", cw, ow, d[4], d[5], pool, pool_len);
-        check_box_axis(who, f, "vertical", ch, oh, d[6], d[7], pool, pool_len);
-        auto span = [&](int t) { const int s = frames_row_span(ch, oh, t); return s > ch ? ch : s; };
-        while (th > 1 && span(th) > kFrRows) th >>= 1;
-        if (span(th) > kFrRows) throw ArgError(box_frame(who, f) + "vertical reduction too steep (more than 112 source rows under one output row)");
-        const int rx0 = x0 < 0 ? 0 : x0, ry0 = y0 < 0 ? 0 : y0, rx1 = x1 > w ? w : x1, ry1 = y1 > h ? h : y1;
-        if (rx0 < rx1 && ry0 < ry1) { rw = rx1 - rx0 > rw ? rx1 - rx0 : rw; rh = ry1 - ry0 > rh ? ry1 - ry0 : rh; }
-    }
-    if (rw == 0) return TSNET_OK;                                    // Image.paste: every box is outside its frame, nothing is written
-    const int gy = (rh + th - 1) / th;
-    if (gy > 65535) throw ArgError("paste_frames_boxes: region too tall");
-    PasteBoxArgs b{{gen, mask, frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, GH, GW, sx0, sy0, cw, ch, h, w, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, th},
-                   boxes_dev, pool, pool_len};
-    const dim3 grid((rw + kFrTileW - 1) / kFrTileW, gy, F);
-    if (mask) hipLaunchKernelGGL(paste_frames_boxes_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
-    else hipLaunchKernelGGL(paste_frames_boxes_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
-    check_launch("paste_frames_boxes");
-    OP_END
-}
-
-
-// ---- face labels with a crop per frame (track_labels.hpp): HOST descriptors {h, w, off, lw_rows, woff_rows, lw_cols, woff_cols, 0}, all of them
-// checked here before anything is enqueued
-static void check_label_axis(const char* who, int f, const char* axis, int n_in, int n_out, int lw, int woff, const double* pool, int pool_len) {
-    if (lw < -1 || lw > kTlMaxLw) throw ArgError(box_frame(who, f) + axis + " lw " + std::to_string(lw) + " is outside -1 .. 63");
-    const double sigma = std::max(0.0, ((double)n_in / (double)n_out - 1.0) / 2.0);         // skimage's anti-aliasing sigma (demo._aa_kernel)
-    if (sigma <= 1e-15) {
-        if (lw >= 0) throw ArgError(box_frame(who, f) + "the " + axis + " do not shrink (" + std::to_string(n_in) + " -> " + std::to_string(n_out) + "): lw must be -1");
-        return;
-    }
-    if (lw != (int)(4.0 * sigma + 0.5))
-        throw ArgError(box_frame(who, f) + axis + " lw " + std::to_string(lw) + " is not int(4 sigma + 0.5) of " + std::to_string(n_in) + " -> " + std::to_string(n_out));
-    if (woff < 0 || !pool || (long long)woff + lw + 1 > (long long)pool_len)
-        throw ArgError(box_frame(who, f) + "the " + axis + " half-kernel at offset " + std::to_string(woff) + " ends beyond the pool of " + std::to_string(pool_len) + " doubles");
-}
-
-static void face_labels_boxes_any(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev, const double* pool,
-                                  int pool_len, int bw, void* workspace, long long ws_len, int OH, int OW, void* cls, void* box, bool u8, void* stream) {
-    const char* who = "face_labels_boxes";
-    if ((!cls && !box) || (cls && !curves) || (box && !keypoints) || !desc_host || !desc_dev || !workspace) throw ArgError("face_labels_boxes: null tensor");
-    if (F < 1 || 2 * (long long)F > 65535) throw ArgError("face_labels_boxes: F must be 1 .. 32767 (two images per frame along the grid's y)");
-    if (bw < 1) throw ArgError("face_labels_boxes: bw must be at least 1");
-    if (OH < 1 || OW < 1 || (double)OH * OW >= 2147483647.0 / 4) throw ArgError("face_labels_boxes: bad output shape");
-    if (pool_len < 0 || ws_len < 0) throw ArgError("face_labels_boxes: negative pool or workspace length");
-    if (((uintptr_t)workspace & 3) != 0) throw ArgError("face_labels_boxes: the workspace must be 4-byte aligned");
-    if (16ll * F > ws_len) throw ArgError("face_labels_boxes: the workspace of " + std::to_string(ws_len) + " bytes cannot hold the " + std::to_string(2 * F) + " min / max pairs");
-    std::vector<std::pair<long long, int>> starts((size_t)F);         // (offset, frame)
-    int max_hw = 0;
-    bool pass[2] = {false, false};
-    for (int f = 0; f < F; ++f) {
-        const int* d = desc_host + (size_t)f * kTlDesc;
-        const int h = d[0], w = d[1];
-        if (h < 1 || w < 1 || h > kTlMaxSide || w > kTlMaxSide) throw ArgError(box_frame(who, f) + "crop of " + std::to_string(h) + " x " + std::to_string(w) + " (h x w): sides must be 1 .. 32767");
-        check_label_axis(who, f, "rows", h, OH, d[3], d[4], pool, pool_len);
-        check_label_axis(who, f, "columns", w, OW, d[5], d[6], pool, pool_len);
-        const long long off = d[2], end = off + 4ll * h * w;
-        if (off < 16ll * F) throw ArgError(box_frame(who, f) + "its workspace region at offset " + std::to_string(off) + " overlaps the " + std::to_string(2 * F) + " min / max pairs");
-        if (end > ws_len) throw ArgError(box_frame(who, f) + "its workspace region ends at " + std::to_string(end) + ", beyond the workspace of " + std::to_string(ws_len) + " bytes");
-        starts[(size_t)f] = {off, f};
-        max_hw = std::max(max_hw, h * w);
-        pass[0] = pass[0] || d[3] > 0; pass[1] = pass[1] || d[5] > 0;
-    }
-    std::sort(starts.begin(), starts.end());
-    for (int i = 1; i < F; ++i) {
-        const int p = starts[(size_t)i - 1].second, f = starts[(size_t)i].second;
-        const int* dp = desc_host + (size_t)p * kTlDesc;
-        if (starts[(size_t)i - 1].first + 4ll * dp[0] * dp[1] > starts[(size_t)i].first)
-            throw ArgError(box_frame(who, std::max(p, f)) + "its workspace region overlaps that of frame " + std::to_string(std::min(p, f)));
-    }
-    hipStream_t s = (hipStream_t)stream;
-    TrackLabelArgs a{keypoints, curves, desc_dev, pool, static_cast<unsigned char*>(workspace), ws_len, pool_len, F, bw, OH, OW,
-                     cls ? 0 : 1, (cls ? 1 : 0) + (box ? 1 : 0), {cls, box}};
-    const unsigned px = (unsigned)((max_hw + 255) / 256), images = (unsigned)(a.nmaps * F);
-    hipLaunchKernelGGL(track_fill_kernel, dim3((max_hw + 1023) / 1024, F), dim3(256), 0, s, a);
-    check_launch("track_fill");
-    if (cls) {
-        hipLaunchKernelGGL(track_edges_kernel, dim3(kFaceSubEdges, F), dim3(64), 0, s, a);
-        check_launch("track_edges");
-    }
-    for (int axis = 0; axis < 2; ++axis) {
-        if (!pass[axis]) continue;                                   // no frame of the call takes this pass
-        hipLaunchKernelGGL(track_gauss_kernel, dim3(px, images), dim3(256), 0, s, a, axis);
-        check_launch("track_gauss");
-    }
-    hipLaunchKernelGGL(track_minmax_kernel, dim3(std::min(64u, px), images), dim3(256), 0, s, a);
-    check_launch("track_minmax");
-    const dim3 grid((OH * OW + 255) / 256, images);
-    if (u8) hipLaunchKernelGGL(track_resize_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(track_resize_kernel<false>, grid, dim3(256), 0, s, a);
-    check_launch("track_resize");
-}
-
-int tsnet_face_labels_boxes(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev, const double* pool, int pool_len,
-                            int bw, void* workspace, long long workspace_len, int OH, int OW, float* labels, float* masks, void* stream) {
-    OP_BEGIN
-    face_labels_boxes_any(keypoints, curves, F, desc_host, desc_dev, pool, pool_len, bw, workspace, workspace_len, OH, OW, labels, masks, false, stream);
-    OP_END
-}
-
-int tsnet_face_labels_boxes_u8(const double* keypoints, const double* curves, int F, const int* desc_host, const int* desc_dev, const double* pool, int pool_len,
-                               int bw, void* workspace, long long workspace_len, int OH, int OW, unsigned char* labels, unsigned char* masks, void* stream) {
-    OP_BEGIN
-    face_labels_boxes_any(keypoints, curves, F, desc_host, desc_dev, pool, pool_len, bw, workspace, workspace_len, OH, OW, labels, masks, true, stream);
-    OP_END
-}
-
 }  // extern "C"
+
+#define TSNET_ENGINE_CPP      // clip_entries.hpp refuses every other includer
+#include "clip_entries.hpp"

@@ -10,6 +10,7 @@
 // in Pillow's operation order; engine.cpp is compiled without fp contraction) and the kernel does the integer work, so the result EQUALS
 // frame.crop(box).resize(size) byte for byte (tests/test_frames.py: live Pillow, and the stored loader outputs of the g10 goldens).
 // Image.crop semantics: the box may leave the frame, the part outside reads as 0; the resampling window clamps to the CROP, never to the frame.
+// paste.hpp, the way back, shares the vertical pass (fr_vpass) and the window of rows a tile keeps (fr_row_window) with the loader: one spelling.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -84,6 +85,41 @@ struct FrameArgs {
 __device__ __forceinline__ int fr_k24(int k) { return (k << 8) >> 8; }
 __device__ __forceinline__ int fr_clip8(int acc) { const int v = acc >> kBicubicBits; return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
+// The rows of the horizontal pass a tile keeps in LDS for its resized rows [oyA, oyB), oyA < oyB: source rows [ybase, ybase + rows) of a crop
+// ch rows tall, from the vertical tables (not read when skipy), never more than kFrRows.  cap: rows also end at the crop's last row (paste.hpp,
+// whose source rows are read without a check against the image).  Shared by prepare_frames_body and paste.hpp's paste_frames_body.
+__device__ __forceinline__ void fr_row_window(const int* yfirst, const int* ycount, int ch, int oyA, int oyB, bool skipy, bool cap, int& ybase, int& rows) {
+    if (skipy) { ybase = oyA; rows = oyB - oyA; }
+    else {
+        ybase = yfirst[oyA];
+        ybase = ybase < 0 ? 0 : (ybase > ch ? ch : ybase);
+        int yend = yfirst[oyB - 1] + ycount[oyB - 1];
+        yend = yend > ch ? ch : yend;
+        rows = yend - ybase;
+    }
+    if (cap && ybase + rows > ch) rows = ch - ybase;
+    rows = rows < 0 ? 0 : (rows > kFrRows ? kFrRows : rows);
+}
+
+// One output byte of the vertical pass: resized row oy (0 <= oy < oh) of an LDS column whose rows lie `stride` bytes apart; the column holds
+// `rows` rows of the horizontal pass, the first of them source row ybase (fr_row_window).  Shared by prepare_frames_body and paste.hpp's
+// paste_frames_body.  The range test of the skipy branch is the paste's; the loader read col[(oy - ybase) * stride] without one, and for it the
+// test is always true (rows = oyB - oyA <= th there and oy lies in [oyA, oyB)): the same bytes, five more instructions per loader kernel.
+__device__ __forceinline__ int fr_vpass(const int* yfirst, const int* ycount, const int* ycoef, int ytaps, const unsigned char* col, int stride, int oy,
+                                        int ybase, int rows, bool skipy) {
+    if (skipy) { const int rr = oy - ybase; return rr >= 0 && rr < rows ? col[rr * stride] : 0; }
+    const int first = yfirst[oy] - ybase;
+    int cnt = ycount[oy];
+    cnt = cnt > ytaps ? ytaps : cnt;
+    const int* k = ycoef + (size_t)oy * ytaps;
+    int acc = 1 << (kBicubicBits - 1);
+    for (int j = 0; j < cnt; ++j) {
+        const int rr = first + j;
+        if (rr >= 0 && rr < rows) acc += (int)col[rr * stride] * fr_k24(k[j]);
+    }
+    return fr_clip8(acc);
+}
+
 // grid = (ceil(OW / 64), ceil(OH / th), F), 256 threads.  A workgroup owns th x 64 pixels of one frame's PADDED output.  It runs the horizontal
 // pass for the crop rows its output rows read, straight from the frame (the taps of neighbouring lanes overlap: the vector L1 serves them) into
 // LDS as bytes, plane by plane; then the vertical pass from LDS, and stores fp32 rows of 64 consecutive floats per plane.  The byte image
@@ -106,15 +142,7 @@ __device__ __forceinline__ void prepare_frames_body(const FrameArgs& a, const fl
     const bool skipx = a.ow == a.cw, skipy = a.oh == a.ch;
     int ybase = 0, rows = 0;
     if (content) {
-        if (skipy) { ybase = oyA; rows = oyB - oyA; }
-        else {
-            ybase = a.yfirst[oyA];
-            ybase = ybase < 0 ? 0 : (ybase > a.ch ? a.ch : ybase);
-            int yend = a.yfirst[oyB - 1] + a.ycount[oyB - 1];
-            yend = yend > a.ch ? a.ch : yend;
-            rows = yend - ybase;
-        }
-        rows = rows < 0 ? 0 : (rows > kFrRows ? kFrRows : rows);
+        fr_row_window(a.yfirst, a.ycount, a.ch, oyA, oyB, skipy, false, ybase, rows);
         const unsigned char* img = a.frames + (size_t)f * a.h * a.w * 3;
         for (int i = tid; i < rows * kFrRowBytes; i += blockDim.x) {
             const int r = i / kFrRowBytes, e = i - r * kFrRowBytes, c = e / kFrTileW, lx = e - c * kFrTileW;
@@ -148,23 +176,8 @@ __device__ __forceinline__ void prepare_frames_body(const FrameArgs& a, const fl
         const int X = X0 + lx, Y = Y0 + ly, oy = Y - a.pad_top;
         if (X >= a.OW) continue;
         int v = 0;                                                // the bars of resize_square: byte 0
-        if (content && oy >= oyA && oy < oyB && lx >= lxA && lx < lxB) {
-            const unsigned char* col = hbuf + c * kFrTileW + lx;
-            if (skipy) {
-                v = col[(oy - ybase) * kFrRowBytes];
-            } else {
-                const int first = a.yfirst[oy] - ybase;
-                int cnt = a.ycount[oy];
-                cnt = cnt > a.ytaps ? a.ytaps : cnt;
-                const int* k = a.ycoef + (size_t)oy * a.ytaps;
-                int acc = 1 << (kBicubicBits - 1);
-                for (int j = 0; j < cnt; ++j) {
-                    const int rr = first + j;
-                    if (rr >= 0 && rr < rows) acc += (int)col[rr * kFrRowBytes] * fr_k24(k[j]);
-                }
-                v = fr_clip8(acc);
-            }
-        }
+        if (content && oy >= oyA && oy < oyB && lx >= lxA && lx < lxB)
+            v = fr_vpass(a.yfirst, a.ycount, a.ycoef, a.ytaps, hbuf + c * kFrTileW + lx, kFrRowBytes, oy, ybase, rows, skipy);
         const int p = 2 - c;                                      // RGB -> BGR
         const size_t o = (((size_t)f * 3 + p) * a.OH + Y) * a.OW + X;
         if (U8) reinterpret_cast<unsigned char*>(a.out)[o] = (unsigned char)v;

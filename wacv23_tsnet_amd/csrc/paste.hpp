@@ -9,7 +9,10 @@
 //   * masked paste (paste_mask_L), per byte with a = frame, b = resized gen, m = resized mask: t = b * m + a * (255 - m) + 128,
 //     out = (t + (t >> 8)) >> 8.  The mask is one channel through the same tables and rounding as a colour channel.
 // The resampler is frames.hpp's: integer passes on tsnet_bicubic_table's tables, the horizontal one first and ROUNDED TO BYTES, a pass along an
-// axis that keeps its size skipped.
+// axis that keeps its size skipped.  The vertical pass and the window of source rows a tile keeps are frames.hpp's own code, fr_vpass and
+// fr_row_window, called from both bodies.  The horizontal pass is this file's (paste_hpass): it reads a rectangle the launcher proved inside gen
+// at a run-time pixel stride, where the loader checks every read against the frame and returns zeros outside it -- one function for both would
+// carry the other's checks into each kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,22 +46,6 @@ __device__ __forceinline__ int paste_hpass(const PasteArgs& a, const unsigned ch
     return fr_clip8(acc);
 }
 
-// One output byte of the vertical pass: resized row oy (0 <= oy < oh) of an LDS column whose rows lie `stride` bytes apart; the column holds
-// `rows` rows of the horizontal pass, the first of them source row ybase.
-__device__ __forceinline__ int paste_vpass(const PasteArgs& a, const unsigned char* col, int stride, int oy, int ybase, int rows, bool skipy) {
-    if (skipy) { const int rr = oy - ybase; return rr >= 0 && rr < rows ? col[rr * stride] : 0; }
-    const int first = a.yfirst[oy] - ybase;
-    int cnt = a.ycount[oy];
-    cnt = cnt > a.ytaps ? a.ytaps : cnt;
-    const int* k = a.ycoef + (size_t)oy * a.ytaps;
-    int acc = 1 << (kBicubicBits - 1);
-    for (int j = 0; j < cnt; ++j) {
-        const int rr = first + j;
-        if (rr >= 0 && rr < rows) acc += (int)col[rr * stride] * fr_k24(k[j]);
-    }
-    return fr_clip8(acc);
-}
-
 // grid = (ceil(region width / 64), ceil(region height / th), F), 256 threads, region = box ∩ frame.  A workgroup owns th x 64 pixels of one
 // frame's region.  It runs the horizontal pass for the source rows its output rows read, from gen (and mask) into LDS as bytes, INTERLEAVED
 // as the frame is (byte e of a row: pixel e / 3, channel e % 3), the mask's 64 bytes per row behind the colour rows; then the vertical pass
@@ -79,16 +66,7 @@ __device__ __forceinline__ void paste_frames_body(const PasteArgs& a) {
     if (nx <= 0 || oyA >= oyB || oxA < 0 || oxA + nx > a.ow) return;         // uniform over the workgroup; the launcher rules it out
     const bool skipx = a.ow == a.cw, skipy = a.oh == a.ch;
     int ybase, rows;
-    if (skipy) { ybase = oyA; rows = oyB - oyA; }
-    else {
-        ybase = a.yfirst[oyA];
-        ybase = ybase < 0 ? 0 : (ybase > a.ch ? a.ch : ybase);
-        int yend = a.yfirst[oyB - 1] + a.ycount[oyB - 1];
-        yend = yend > a.ch ? a.ch : yend;
-        rows = yend - ybase;
-    }
-    if (ybase + rows > a.ch) rows = a.ch - ybase;
-    rows = rows < 0 ? 0 : (rows > kFrRows ? kFrRows : rows);
+    fr_row_window(a.yfirst, a.ycount, a.ch, oyA, oyB, skipy, true, ybase, rows);
     // source row ybase + r of the rectangle, 0 <= ybase + r < ch: inside gen, the launcher checked the rectangle
     const size_t src0 = ((size_t)f * a.GH + a.sy0 + ybase) * a.GW + a.sx0;
     for (int i = tid; i < rows * kFrRowBytes; i += blockDim.x) {
@@ -112,9 +90,9 @@ __device__ __forceinline__ void paste_frames_body(const PasteArgs& a) {
         const int X = X0 + lx, Y = Y0 + ly, oy = Y - a.y0;
         if (lx >= nx || X < 0 || X >= a.w || Y < 0 || Y >= a.h || oy < oyA || oy >= oyB) continue;
         unsigned char* dst = img + ((size_t)Y * a.w + X0) * 3 + e;            // byte e of the tile row: consecutive lanes, consecutive bytes
-        int v = paste_vpass(a, hbuf + e, kFrRowBytes, oy, ybase, rows, skipy);
+        int v = fr_vpass(a.yfirst, a.ycount, a.ycoef, a.ytaps, hbuf + e, kFrRowBytes, oy, ybase, rows, skipy);
         if (MASK) {
-            const int m = paste_vpass(a, mbuf + lx, kFrTileW, oy, ybase, rows, skipy);
+            const int m = fr_vpass(a.yfirst, a.ycount, a.ycoef, a.ytaps, mbuf + lx, kFrTileW, oy, ybase, rows, skipy);
             const int t = v * m + (int)*dst * (255 - m) + 128;              // paste_mask_L
             v = (t + (t >> 8)) >> 8;
         }

@@ -36,10 +36,10 @@ constexpr int kCurveRec = 8;             // doubles per fitted piece: {kind, a, 
     {60, 61, 62}, {62, 63, 64}, {64, 65, 66}, {66, 67, 60}                                                         /* inner mouth */
 static const signed char hFaceSubEdgeTable[kFaceSubEdges][3] = {TSNET_FACE_SUB_EDGES};
 
-// grid = (kFaceSubEdges, F); rec: (F, 34, 8) fitted pieces (tsnet_fit_face_curves); out: (F, h, w) bytes, zeroed by the caller
-__global__ __launch_bounds__(64) void face_edges_kernel(const double* __restrict__ rec, unsigned char* __restrict__ out, int h, int w, int bw) {
-    const int e = blockIdx.x, f = blockIdx.y;
-    const double* r = rec + ((size_t)f * kFaceSubEdges + e) * kCurveRec;
+// ONE fitted piece drawn into ONE image (h, w): the record is sampled at np.linspace(u_first, u_last, ceil(u_last - u_first)), truncated to pixels,
+// and every sample stamps the square [-bw, bw) clamped to the image's border.  The block's threads share the samples.  The one spelling of
+// interp_points + draw_edge on the device: face_edges_kernel and track_labels.hpp's track_edges_kernel call it.
+__device__ __forceinline__ void draw_face_piece(const double* r, unsigned char* img, int h, int w, int bw) {
     const int kind = (int)r[0];
     if (!(kind & 1)) return;                                      // |a| > 1 (:333-334) or no fit
     const bool swap = (kind & 2) != 0, quad = (kind & 4) != 0;
@@ -56,23 +56,35 @@ __global__ __launch_bounds__(64) void face_edges_kernel(const double* __restrict
                 int yy = y + di, xx = x + dj;
                 yy = yy < 0 ? 0 : (yy > h - 1 ? h - 1 : yy);
                 xx = xx < 0 ? 0 : (xx > w - 1 ? w - 1 : xx);
-                out[((size_t)f * h + yy) * w + xx] = 255;         // every writer stores the same value
+                img[(size_t)yy * w + xx] = 255;                   // every writer stores the same value
             }
     }
 }
 
-// grid = F; out: (F, h, w) bytes, fully written
-__global__ __launch_bounds__(256) void face_bbox_kernel(const double* __restrict__ kp, unsigned char* __restrict__ out, int h, int w) {
-    const int f = blockIdx.x;
-    const double* k = kp + (size_t)f * kFaceKeypoints * 2;
+// grid = (kFaceSubEdges, F); rec: (F, 34, 8) fitted pieces (tsnet_fit_face_curves); out: (F, h, w) bytes, zeroed by the caller
+__global__ __launch_bounds__(64) void face_edges_kernel(const double* __restrict__ rec, unsigned char* __restrict__ out, int h, int w, int bw) {
+    const int e = blockIdx.x, f = blockIdx.y;
+    draw_face_piece(rec + ((size_t)f * kFaceSubEdges + e) * kCurveRec, out + (size_t)f * h * w, h, w, bw);
+}
+
+// The box of one frame's 68 key points k, grown by w / 16, h / 16 and cut to the image: columns [bx0, bx1), rows [by0, by1).  Shared by
+// face_bbox_kernel and track_labels.hpp's track_fill_kernel, which keep their own pixel loops.
+__device__ __forceinline__ void face_keypoint_box(const double* k, int h, int w, int& bx0, int& bx1, int& by0, int& by1) {
     double x0 = k[0], x1 = k[0], y0 = k[1], y1 = k[1];
     for (int i = 1; i < kFaceKeypoints; ++i) {
         x0 = fmin(x0, k[2 * i]); x1 = fmax(x1, k[2 * i]);
         y0 = fmin(y0, k[2 * i + 1]); y1 = fmax(y1, k[2 * i + 1]);
     }
     const int xm = w / 16, ym = h / 16;
-    const int bx0 = (int)fmax(0.0, x0 - xm), bx1 = (int)fmin((double)w, x1 + xm);
-    const int by0 = (int)fmax(0.0, y0 - ym), by1 = (int)fmin((double)h, y1 + ym);
+    bx0 = (int)fmax(0.0, x0 - xm); bx1 = (int)fmin((double)w, x1 + xm);
+    by0 = (int)fmax(0.0, y0 - ym); by1 = (int)fmin((double)h, y1 + ym);
+}
+
+// grid = F; out: (F, h, w) bytes, fully written
+__global__ __launch_bounds__(256) void face_bbox_kernel(const double* __restrict__ kp, unsigned char* __restrict__ out, int h, int w) {
+    const int f = blockIdx.x;
+    int bx0, bx1, by0, by1;
+    face_keypoint_box(kp + (size_t)f * kFaceKeypoints * 2, h, w, bx0, bx1, by0, by1);
     for (int i = threadIdx.x; i < h * w; i += blockDim.x) {
         const int y = i / w, x = i - y * w;
         out[(size_t)f * h * w + i] = (y >= by0 && y < by1 && x >= bx0 && x < bx1) ? 255 : 0;
@@ -294,22 +306,29 @@ __device__ __forceinline__ int mirror_index(int i, int n) {          // coord_ma
     return (q & 1) ? c - r : r;
 }
 
-// one 1-D Gaussian pass along `axis` (0 = rows, 1 = columns) of F images (h, w); wts: lw + 1 doubles (centre first)
+// One output byte of a 1-D Gaussian pass along `axis` (0 = rows, 1 = columns) at (y, x) of ONE image (h, w); wts: lw + 1 doubles (centre
+// first).  The accumulation order is the contract: the centre, then the mirrored pairs outwards, truncated back to a byte.  Shared by
+// gauss1d_u8_kernel and track_labels.hpp's track_gauss_kernel.
+__device__ __forceinline__ unsigned char gauss1d_u8_at(const unsigned char* img, int h, int w, int y, int x, int axis,
+                                                       const double* wts, int lw) {
+    const int n = axis ? w : h, pos = axis ? x : y;
+    double acc = (double)img[(size_t)y * w + x] * wts[0];
+    for (int j = 1; j <= lw; ++j) {
+        const int a = mirror_index(pos + j, n), b = mirror_index(pos - j, n);
+        const double va = axis ? (double)img[(size_t)y * w + a] : (double)img[(size_t)a * w + x];
+        const double vb = axis ? (double)img[(size_t)y * w + b] : (double)img[(size_t)b * w + x];
+        acc = acc + (va + vb) * wts[j];
+    }
+    return (unsigned char)acc;                                        // truncation: acc is in [0, 255]
+}
+
+// one 1-D Gaussian pass along `axis` of F images (h, w)
 __global__ __launch_bounds__(256) void gauss1d_u8_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out, int F, int h, int w,
                                                          int axis, const double* __restrict__ wts, int lw) {
     const size_t total = (size_t)F * h * w;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int x = (int)(i % w), y = (int)((i / w) % h);
-        const unsigned char* img = in + (i / ((size_t)w * h)) * (size_t)w * h;
-        const int n = axis ? w : h, pos = axis ? x : y;
-        double acc = (double)in[i] * wts[0];
-        for (int j = 1; j <= lw; ++j) {
-            const int a = mirror_index(pos + j, n), b = mirror_index(pos - j, n);
-            const double va = axis ? (double)img[(size_t)y * w + a] : (double)img[(size_t)a * w + x];
-            const double vb = axis ? (double)img[(size_t)y * w + b] : (double)img[(size_t)b * w + x];
-            acc = acc + (va + vb) * wts[j];
-        }
-        out[i] = (unsigned char)acc;                                  // truncation: acc is in [0, 255]
+        out[i] = gauss1d_u8_at(in + (i / ((size_t)w * h)) * (size_t)w * h, h, w, y, x, axis, wts, lw);
     }
 }
 
@@ -325,24 +344,30 @@ __global__ __launch_bounds__(256) void u8_minmax_kernel(const unsigned char* __r
     __hip_atomic_fetch_max(mm + 2 * f + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// One output value of the label resize at (Y, X) from ONE image (h, w), the scale factors fr = h / OH, fc = w / OW (fp64 quotients, the caller's:
+// one per image) and the image's {min, max} pair mm: the bilinear sample at f (o + 0.5) - 0.5 on the image / 255, clamped to the image's own
+// range, > 0.5 -> 1.f or 0.f.  Shared by resize_label_kernel and track_labels.hpp's track_resize_kernel.
+__device__ __forceinline__ float resize_label_at(const unsigned char* img, int h, int w, double fr, double fc, int Y, int X, const int* mm) {
+    const double r = fr * ((double)Y + 0.5) - 0.5, c = fc * ((double)X + 0.5) - 0.5;
+    const double r0 = floor(r), c0 = floor(c), r1 = ceil(r), c1 = ceil(c);
+    const double dr = r - r0, dc = c - c0;
+    const int ir0 = mirror_index((int)r0, h), ir1 = mirror_index((int)r1, h), ic0 = mirror_index((int)c0, w), ic1 = mirror_index((int)c1, w);
+    const double tl = (double)img[(size_t)ir0 * w + ic0] / 255.0, tr = (double)img[(size_t)ir0 * w + ic1] / 255.0;
+    const double bl = (double)img[(size_t)ir1 * w + ic0] / 255.0, br = (double)img[(size_t)ir1 * w + ic1] / 255.0;
+    const double top = (1.0 - dc) * tl + dc * tr, bot = (1.0 - dc) * bl + dc * br;
+    double v = (1.0 - dr) * top + dr * bot;
+    const double lo = (double)mm[0] / 255.0, hi = (double)mm[1] / 255.0;
+    v = v < lo ? lo : (v > hi ? hi : v);
+    return v > 0.5 ? 1.f : 0.f;
+}
+
 __global__ __launch_bounds__(256) void resize_label_kernel(const unsigned char* __restrict__ in, int F, int h, int w, int OH, int OW,
                                                            const int* __restrict__ mm, float* __restrict__ out) {
     const size_t total = (size_t)F * OH * OW;
     const double fr = (double)h / (double)OH, fc = (double)w / (double)OW;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int X = (int)(i % OW), Y = (int)((i / OW) % OH), f = (int)(i / ((size_t)OW * OH));
-        const unsigned char* img = in + (size_t)f * h * w;
-        const double r = fr * ((double)Y + 0.5) - 0.5, c = fc * ((double)X + 0.5) - 0.5;
-        const double r0 = floor(r), c0 = floor(c), r1 = ceil(r), c1 = ceil(c);
-        const double dr = r - r0, dc = c - c0;
-        const int ir0 = mirror_index((int)r0, h), ir1 = mirror_index((int)r1, h), ic0 = mirror_index((int)c0, w), ic1 = mirror_index((int)c1, w);
-        const double tl = (double)img[(size_t)ir0 * w + ic0] / 255.0, tr = (double)img[(size_t)ir0 * w + ic1] / 255.0;
-        const double bl = (double)img[(size_t)ir1 * w + ic0] / 255.0, br = (double)img[(size_t)ir1 * w + ic1] / 255.0;
-        const double top = (1.0 - dc) * tl + dc * tr, bot = (1.0 - dc) * bl + dc * br;
-        double v = (1.0 - dr) * top + dr * bot;
-        const double lo = (double)mm[2 * f] / 255.0, hi = (double)mm[2 * f + 1] / 255.0;
-        v = v < lo ? lo : (v > hi ? hi : v);
-        out[i] = v > 0.5 ? 1.f : 0.f;
+        out[i] = resize_label_at(in + (size_t)f * h * w, h, w, fr, fc, Y, X, mm + 2 * f);
     }
 }
 

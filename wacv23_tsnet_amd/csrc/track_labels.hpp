@@ -3,9 +3,11 @@
 //
 // The kernels are the ragged forms of raster.hpp's face_edges_kernel, face_bbox_kernel, gauss1d_u8_kernel, u8_minmax_kernel and
 // resize_label_kernel: one launch of each serves every frame of the call, a frame's size and place come from its DEVICE descriptor, the grid
-// covers the largest image of the call and a block beyond its own image's extent returns.  Per pixel the operations and their order are those
-// of raster.hpp (the float64 Gaussian accumulate with its truncating cast, mirrored borders, the bilinear sample at f (o + 0.5) - 0.5, the clamp
-// to the image's own min / max, the threshold at 0.5), so frame f of a call has the bits of the single-size entries called on frame f alone.
+// covers the largest image of the call and a block beyond its own image's extent returns.  Every per-pixel step is SHARED with those kernels,
+// not restated: both forms call raster.hpp's draw_face_piece, face_keypoint_box, gauss1d_u8_at and resize_label_at on one image and its own
+// h, w.  The kernels here keep what differs -- the descriptor checks, a frame's place in the workspace, the grid -- so frame f of a call has the
+// bits of the single-size entries called on frame f alone.  (The min / max of an image has no order to keep -- min and max commute -- and each
+// kernel folds it its own way: track_minmax_kernel in the block first, u8_minmax_kernel per thread.)
 // The 2F maps of a call are the IMAGES of the ragged batch: image m < F is the edge map of frame m, image F + f the bounding-box mask of frame f.
 //
 // Descriptor, kTlDesc ints per frame: {h, w, off, lw_rows, woff_rows, lw_cols, woff_cols, 0}
@@ -77,8 +79,8 @@ __device__ __forceinline__ unsigned char* tl_buf(const TlFrame& t, int map, int 
 }
 __device__ __forceinline__ int tl_final(const TlFrame& t) { return (t.lw[0] > 0) != (t.lw[1] > 0) ? 1 : 0; }
 
-// grid = (ceil(max h w / 1024), F), 256 threads, four pixels each: the mask (face_bbox_kernel) into mask A, zeros into edge map A, and the
-// frame's two {min, max} pairs set to {255, 0}
+// grid = (ceil(max h w / 1024), F), 256 threads, four pixels each: the mask (the box of face_keypoint_box, as face_bbox_kernel fills it) into
+// mask A, zeros into edge map A, and the frame's two {min, max} pairs set to {255, 0}
 __global__ __launch_bounds__(256) void track_fill_kernel(TrackLabelArgs a) {
     const int f = blockIdx.y;
     TlFrame t;
@@ -93,17 +95,7 @@ __global__ __launch_bounds__(256) void track_fill_kernel(TrackLabelArgs a) {
     if (blockIdx.x * 1024 >= (unsigned)hw) return;
     const bool edges = a.map0 == 0, mask = a.map0 + a.nmaps == 2;
     int bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
-    if (mask) {
-        const double* k = a.kp + (size_t)f * kFaceKeypoints * 2;
-        double x0 = k[0], x1 = k[0], y0 = k[1], y1 = k[1];
-        for (int i = 1; i < kFaceKeypoints; ++i) {
-            x0 = fmin(x0, k[2 * i]); x1 = fmax(x1, k[2 * i]);
-            y0 = fmin(y0, k[2 * i + 1]); y1 = fmax(y1, k[2 * i + 1]);
-        }
-        const int xm = w / 16, ym = h / 16;
-        bx0 = (int)fmax(0.0, x0 - xm); bx1 = (int)fmin((double)w, x1 + xm);
-        by0 = (int)fmax(0.0, y0 - ym); by1 = (int)fmin((double)h, y1 + ym);
-    }
+    if (mask) face_keypoint_box(a.kp + (size_t)f * kFaceKeypoints * 2, h, w, bx0, bx1, by0, by1);
     unsigned char* e = tl_buf(t, 0, 0);
     unsigned char* m = tl_buf(t, 1, 0);
     for (int j = 0; j < 4; ++j) {
@@ -117,36 +109,15 @@ __global__ __launch_bounds__(256) void track_fill_kernel(TrackLabelArgs a) {
     }
 }
 
-// grid = (kFaceSubEdges, F), 64 threads: face_edges_kernel into edge map A, clamped to the frame's own h, w
+// grid = (kFaceSubEdges, F), 64 threads: draw_face_piece into edge map A, clamped to the frame's own h, w
 __global__ __launch_bounds__(64) void track_edges_kernel(TrackLabelArgs a) {
     const int e = blockIdx.x, f = blockIdx.y;
     TlFrame t;
     if (!tl_frame(a, f, t)) return;
-    const double* r = a.curves + ((size_t)f * kFaceSubEdges + e) * kCurveRec;
-    const int kind = (int)r[0];
-    if (!(kind & 1)) return;                                      // |a| > 1 (:333-334) or no fit
-    const bool swap = (kind & 2) != 0, quad = (kind & 4) != 0;
-    const double qa = r[1], b = r[2], c = r[3], u0 = r[4], u1 = r[5];
-    const int num = (int)ceil(u1 - u0);
-    const double step = num > 1 ? (u1 - u0) / (double)(num - 1) : 0.0;
-    const int h = t.h, w = t.w, bw = a.bw;
-    unsigned char* out = tl_buf(t, 0, 0);
-    for (int i = threadIdx.x; i < num; i += blockDim.x) {
-        const double cu = (i == num - 1 && num > 1) ? u1 : u0 + (double)i * step;     // np.linspace: arange * step + start, last = stop
-        const double cv = quad ? (qa * (cu * cu) + b * cu) + c : b * cu + c;
-        const int iu = (int)cu, iv = (int)cv;                     // astype(int): truncation
-        const int x = swap ? iv : iu, y = swap ? iu : iv;
-        for (int di = -bw; di < bw; ++di)
-            for (int dj = -bw; dj < bw; ++dj) {
-                int yy = y + di, xx = x + dj;
-                yy = yy < 0 ? 0 : (yy > h - 1 ? h - 1 : yy);
-                xx = xx < 0 ? 0 : (xx > w - 1 ? w - 1 : xx);
-                out[(size_t)yy * w + xx] = 255;                   // every writer stores the same value
-            }
-    }
+    draw_face_piece(a.curves + ((size_t)f * kFaceSubEdges + e) * kCurveRec, tl_buf(t, 0, 0), t.h, t.w, a.bw);
 }
 
-// grid = (ceil(max h w / 256), nmaps F), one pixel per thread: gauss1d_u8_kernel along `axis` (0 = rows, 1 = columns) for the frames that take
+// grid = (ceil(max h w / 256), nmaps F), one pixel per thread: gauss1d_u8_at along `axis` (0 = rows, 1 = columns) for the frames that take
 // that pass (lw > 0); the others return
 __global__ __launch_bounds__(256) void track_gauss_kernel(TrackLabelArgs a, int axis) {
     const int map = a.map0 + blockIdx.y / a.F, f = blockIdx.y % a.F;
@@ -162,15 +133,7 @@ __global__ __launch_bounds__(256) void track_gauss_kernel(TrackLabelArgs a, int 
     unsigned char* out = tl_buf(t, map, src ^ 1);
     const double* wts = axis ? t.wts[1] : t.wts[0];
     const int y = i / w, x = i - y * w;
-    const int n = axis ? w : h, pos = axis ? x : y;
-    double acc = (double)img[i] * wts[0];
-    for (int j = 1; j <= lw; ++j) {
-        const int p = mirror_index(pos + j, n), q = mirror_index(pos - j, n);
-        const double va = axis ? (double)img[(size_t)y * w + p] : (double)img[(size_t)p * w + x];
-        const double vb = axis ? (double)img[(size_t)y * w + q] : (double)img[(size_t)q * w + x];
-        acc = acc + (va + vb) * wts[j];
-    }
-    out[i] = (unsigned char)acc;                                     // truncation: acc is in [0, 255]
+    out[i] = gauss1d_u8_at(img, h, w, y, x, axis, wts, lw);
 }
 
 // grid = (min(64, ceil(max h w / 256)), nmaps F), 256 threads: u8_minmax_kernel of every image's final buffer into its pair.  The block folds
@@ -201,7 +164,7 @@ __global__ __launch_bounds__(256) void track_minmax_kernel(TrackLabelArgs a) {
     }
 }
 
-// grid = (ceil(OH OW / 256), nmaps F), one output pixel per thread: resize_label_kernel from the image's final buffer into out[map][f]
+// grid = (ceil(OH OW / 256), nmaps F), one output pixel per thread: resize_label_at from the image's final buffer into out[map][f]
 template <bool U8>
 __global__ __launch_bounds__(256) void track_resize_kernel(TrackLabelArgs a) {
     const int map = a.map0 + blockIdx.y / a.F, f = blockIdx.y % a.F;
@@ -212,21 +175,9 @@ __global__ __launch_bounds__(256) void track_resize_kernel(TrackLabelArgs a) {
     float res = 0.f;
     if (tl_frame(a, f, t)) {
         const int h = t.h, w = t.w, OW = a.OW;
-        const unsigned char* img = tl_buf(t, map, tl_final(t));
-        const int* mm = reinterpret_cast<const int*>(a.ws) + 2 * (map * a.F + f);
         const double fr = (double)h / (double)a.OH, fc = (double)w / (double)OW;
         const int Y = i / OW, X = i - Y * OW;
-        const double r = fr * ((double)Y + 0.5) - 0.5, c = fc * ((double)X + 0.5) - 0.5;
-        const double r0 = floor(r), c0 = floor(c), r1 = ceil(r), c1 = ceil(c);
-        const double dr = r - r0, dc = c - c0;
-        const int ir0 = mirror_index((int)r0, h), ir1 = mirror_index((int)r1, h), ic0 = mirror_index((int)c0, w), ic1 = mirror_index((int)c1, w);
-        const double tl = (double)img[(size_t)ir0 * w + ic0] / 255.0, tr = (double)img[(size_t)ir0 * w + ic1] / 255.0;
-        const double bl = (double)img[(size_t)ir1 * w + ic0] / 255.0, br = (double)img[(size_t)ir1 * w + ic1] / 255.0;
-        const double top = (1.0 - dc) * tl + dc * tr, bot = (1.0 - dc) * bl + dc * br;
-        double v = (1.0 - dr) * top + dr * bot;
-        const double lo = (double)mm[0] / 255.0, hi = (double)mm[1] / 255.0;
-        v = v < lo ? lo : (v > hi ? hi : v);
-        res = v > 0.5 ? 1.f : 0.f;
+        res = resize_label_at(tl_buf(t, map, tl_final(t)), h, w, fr, fc, Y, X, reinterpret_cast<const int*>(a.ws) + 2 * (map * a.F + f));
     }
     if (U8) static_cast<unsigned char*>(a.out[map])[o] = (unsigned char)res;
     else static_cast<float*>(a.out[map])[o] = res;
