@@ -21,7 +21,8 @@
  * back into the video frames; tsnet_prepare_frames_boxes, tsnet_prepare_frames_boxes_u8, tsnet_paste_frames_boxes -- the same with a box per frame;
  * tsnet_face_labels_boxes, tsnet_face_labels_boxes_u8 -- the face labels of a clip with a crop per frame, frames of different sizes in one pass;
  * tsnet_op_upconv2d -- the decoder's up-convolution as one operator; tsnet_op_conv2d_epi -- a convolution with its epilogue's statistics, addend,
- * published maximum, device-derived operand scale and bf16 storage, as the forward calls it.
+ * published maximum, device-derived operand scale and bf16 storage, as the forward calls it; tsnet_op_patch_warp, tsnet_op_train_tail -- the
+ * launches of tsnet_train_extras on the caller's tensors.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -33,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8), tsnet_op_upconv2d, tsnet_op_conv2d_epi; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
+#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8), tsnet_op_upconv2d, tsnet_op_conv2d_epi, tsnet_op_patch_warp, tsnet_op_train_tail; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
 #define TSNET_MAX_SOURCES 8
 
 enum {
@@ -293,6 +294,16 @@ int tsnet_timing_read(tsnet_handle h, double ms_out[TSNET_TIMING_CLASSES], int64
  *   add_stats) holds n_src images, and slots -- HOST ints, one per (source k, frame b) pair, entry k*B + b (add_stats: one per image n) -- names
  *   the image each pair reads, in place of the siblings' SB / x_sb expression.  Everything else as the sibling; a slot outside 0 .. n_src - 1
  *   returns TSNET_ERR_ARG.
+ * tsnet_op_patch_warp <- the patch warp of tsnet_train_extras alone (F.unfold + F.grid_sample + F.fold, TSNet.py:373-379): src_img K HOST-listed
+ *   device pointers to (B,3,H,W) raw images, div K HOST floats (255, or 1 for a frame already in [0,1]), flow (K*B, h*w, 2) with image s*B + b,
+ *   out (K,B,3,H,W).  1 <= K <= 8; h divides H, w divides W, H/h = W/w.
+ * tsnet_op_train_tail <- everything tsnet_train_extras does after the patch warp (TSNet.py:329-330, 381-390, 403-405), by the same launches: x
+ *   (K*B,3,H*W) is re-normalised IN PLACE to the per-channel mean / unbiased std of tar_img / 255 (tar_img (B,3,H,W) raw; frame n takes target
+ *   n % B), columns outside [fore_x0, fore_x1) then replaced by bg (3 HOST floats) when fore_x1 > fore_x0 (TSNet_pose.py:399-400);
+ *   losses[0] = sum over sources of 10 * mean |x - tar_img / 255|, losses[1] = 1 - mean cosine similarity of the rows of pg and sg ((B*P, C), C a
+ *   multiple of 4, 16-byte aligned), or 0 with pg = sg = NULL (the pose form: no cosine launch).  gen_mean, gen_std (K*B*3) and ref_mean, ref_std
+ *   (B*3): NULL, or device floats that receive the statistics the image was re-normalised with.  The reductions' partials live in a scratch
+ *   buffer of the call, filled with NaN first.
  * The entry points from tsnet_op_warp_k_shared on check their arguments on the host and return TSNET_ERR_ARG, with a message and nothing
  * launched, for a null tensor, a channel count that is not a multiple of 4, K outside 1..8, an extent that does not divide, a bad Cp, S < 1
  * or HW < 1; they return after the stream has drained.
@@ -383,6 +394,11 @@ int tsnet_op_pack_input_u8(const uint8_t* const* img, const uint8_t* const* lbl,
                            unsigned int* amax, void* stream);
 int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta, int relu,
                            int N, int H, int W, int C, int x_bf16, int y_bf16, float* y, void* stream);
+int tsnet_op_patch_warp(const float* const* src_img, const float* div, const float* flow, int K, int B, int H, int W, int h, int w, float* out,
+                        void* stream);
+int tsnet_op_train_tail(float* x, const float* tar_img, const float* pg, const float* sg, int K, int B, int H, int W, int P, int C,
+                        int fore_x0, int fore_x1, const float* bg, float* gen_mean, float* gen_std, float* ref_mean, float* ref_std,
+                        float* losses, void* stream);
 const char* tsnet_op_last_error(void);
 
 /* ---- demo post-processing (demo/demo_face.py:96-105,180-198 = demo/demo_pose.py:98-107,

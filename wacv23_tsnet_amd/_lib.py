@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "tsnet_prepare_frames_boxes", "tsnet_prepare_frames_boxes_u8", "tsnet_paste_frames_boxes",
     "tsnet_face_labels_boxes", "tsnet_face_labels_boxes_u8",
     "tsnet_op_upconv2d", "tsnet_op_conv2d_epi",
+    "tsnet_op_patch_warp", "tsnet_op_train_tail",
 )
 
 
@@ -168,6 +169,9 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.tsnet_op_upconv2d.argtypes = lib.tsnet_op_conv2d.argtypes
     if hasattr(lib, "tsnet_op_conv2d_epi"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
         lib.tsnet_op_conv2d_epi.argtypes = lib.tsnet_op_conv2d.argtypes[:-1] + [C.POINTER(TsnetConvEpi), _vp]
+    if hasattr(lib, "tsnet_op_train_tail"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_op_patch_warp.argtypes = [pp, _fp, _vp] + [C.c_int] * 6 + [_vp, _vp]
+        lib.tsnet_op_train_tail.argtypes = [_vp] * 4 + [C.c_int] * 8 + [_fp] + [_vp] * 6
     return lib
 
 

@@ -1468,6 +1468,48 @@ int tsnet_forward_u8(tsnet_handle h, const uint8_t* const* src_img, const uint8_
     return forward_any(h, src_in(src_img, src_lbl, src_bbox, mean_bgr), tar_in(tar_lbl, tar_bbox), out_rgb, out_flow, B, stream);
 }
 
+// ---- the training extras' launches (train_extras.hpp), stated once: tsnet_train_extras runs them on the engine's flows, features and workspace,
+// tsnet_op_patch_warp / tsnet_op_train_tail on the caller's tensors
+constexpr int kTrainChunks = 16;    // blocks of renorm_l1_kernel per (frame, channel): l1 partials are (K*B*3*kTrainChunks) doubles
+constexpr int kTrainNcos = 256;     // blocks of cosine_partial_kernel = its partials
+
+struct TrainWs {
+    float *gen_mean, *gen_std;      // (K*B*3) each
+    float *ref_mean, *ref_std;      // (B*3) each
+    double *l1_part, *cos_part;     // (K*B*3*kTrainChunks), (kTrainNcos)
+};
+
+// model/TSNet.py:373-379: src_img K x (B,3,H,W) raw, div K host floats, flow (K*B, h*w, 2) -> out (K,B,3,H,W)
+static void launch_patch_warp(const float* const* src_img, const float* div, const float* flow, float* out, int K, int B, int H, int W, int hh, int ww,
+                              hipStream_t st) {
+    PatchWarpArgs pa{};
+    for (int s = 0; s < K; ++s) { pa.src[s] = src_img[s]; pa.div[s] = div[s]; }
+    pa.flow = flow; pa.out = out; pa.K = K; pa.B = B; pa.H = H; pa.W = W; pa.h = hh; pa.w = ww; pa.down = H / hh;
+    hipLaunchKernelGGL(patch_warp_kernel, dim3(ew_grid((size_t)K * B * H * W)), dim3(256), 0, st, pa);
+    check_launch("patch_warp");
+}
+
+// everything after the patch warp: x (K*B,3,H*W) re-normalised in place to the statistics of tar_img (B,3,H,W) raw, the composite when
+// fore_x1 > fore_x0, losses[0] = loss_warp; pg / sg (B*P, C) or both null (the pose form: no cosine launch, losses[1] = 0)
+static void launch_train_tail(float* x, const float* tar_img, const float* pg, const float* sg, int K, int B, int H, int W, int P, int C,
+                              int fore_x0, int fore_x1, const float* bg, const TrainWs& ws, float* losses, hipStream_t st) {
+    const int N = K * B, HW = H * W, chunks = kTrainChunks, ncos = kTrainNcos;
+    const bool pose = !pg && !sg;
+    hipLaunchKernelGGL(frame_stats_kernel, dim3(3, B), dim3(256), 0, st, tar_img, 3, HW, 255.0f, ws.ref_mean, ws.ref_std);      // TSNet.py:329-330
+    check_launch("frame_stats(tar)");
+    hipLaunchKernelGGL(frame_stats_kernel, dim3(3, N), dim3(256), 0, st, x, 3, HW, 1.0f, ws.gen_mean, ws.gen_std);              // :381-382
+    check_launch("frame_stats(warp)");
+    hipLaunchKernelGGL(renorm_l1_kernel, dim3(chunks, 3, N), dim3(256), 0, st, x, tar_img, B, HW, ws.gen_mean, ws.gen_std, ws.ref_mean, ws.ref_std, ws.l1_part,
+                       W, fore_x0, fore_x1, bg[0], bg[1], bg[2]);
+    check_launch("renorm_l1");
+    if (!pose) {
+        hipLaunchKernelGGL(cosine_partial_kernel, dim3(ncos), dim3(256), 0, st, pg, sg, B * P, C, ws.cos_part);
+        check_launch("cosine_partial");
+    }
+    hipLaunchKernelGGL(train_losses_kernel, dim3(1), dim3(64), 0, st, ws.l1_part, K, B * 3 * chunks, (double)B * 3 * HW, ws.cos_part, pose ? 0 : ncos, (double)B * P, losses);
+    check_launch("train_losses");
+}
+
 int tsnet_train_extras(tsnet_handle h, const float* const* src_img, const float* tar_img, int B,
                        float* warp_src_img, float* losses, void* stream) {
     API_BEGIN(h)
@@ -1480,36 +1522,21 @@ int tsnet_train_extras(tsnet_handle h, const float* const* src_img, const float*
     for (int s = 0; s < K; ++s) if (!src_img[s]) throw ArgError("train_extras: null source image (need n_source entries)");
     if (H % hh || W % ww || H / hh != W / ww) throw ArgError("train_extras: image size must be a multiple of the feature size");
     hipStream_t st = (hipStream_t)stream;
-    const int N = K * B, HW = H * W, chunks = 16, ncos = 256;
+    const int N = K * B;
     // workspace: gen mean/std (2*N*3) + ref mean/std (2*B*3) floats, then doubles: l1 partials (N*3*chunks) + cos partials
     const size_t nf = (size_t)2 * h->K * h->Bmax * 3 + 2 * h->Bmax * 3, nfp = (nf + 3) / 4 * 4;
-    const size_t nd = (size_t)h->K * h->Bmax * 3 * chunks + ncos;
+    const size_t nd = (size_t)h->K * h->Bmax * 3 * kTrainChunks + kTrainNcos;
     if (!h->train_ws) HIP_TRY(hipMalloc((void**)&h->train_ws, nfp * sizeof(float) + nd * sizeof(double)));
-    float* gen_mean = h->train_ws; float* gen_std = gen_mean + N * 3;
-    float* ref_mean = h->train_ws + 2 * h->K * h->Bmax * 3; float* ref_std = ref_mean + B * 3;
-    double* l1_part = reinterpret_cast<double*>(h->train_ws + nfp); double* cos_part = l1_part + (size_t)h->K * h->Bmax * 3 * chunks;
+    TrainWs ws;
+    ws.gen_mean = h->train_ws; ws.gen_std = ws.gen_mean + N * 3;
+    ws.ref_mean = h->train_ws + 2 * h->K * h->Bmax * 3; ws.ref_std = ws.ref_mean + B * 3;
+    ws.l1_part = reinterpret_cast<double*>(h->train_ws + nfp); ws.cos_part = ws.l1_part + (size_t)h->K * h->Bmax * 3 * kTrainChunks;
 
-    PatchWarpArgs pa{};
-    for (int s = 0; s < K; ++s) { pa.src[s] = src_img[s]; pa.div[s] = h->src_div[s]; }
-    pa.flow = h->flow; pa.out = warp_src_img; pa.K = K; pa.B = B; pa.H = H; pa.W = W; pa.h = hh; pa.w = ww; pa.down = H / hh;
-    hipLaunchKernelGGL(patch_warp_kernel, dim3(ew_grid((size_t)N * HW)), dim3(256), 0, st, pa);
-    check_launch("patch_warp");
-    hipLaunchKernelGGL(frame_stats_kernel, dim3(3, B), dim3(256), 0, st, tar_img, 3, HW, 255.0f, ref_mean, ref_std);      // TSNet.py:329-330
-    check_launch("frame_stats(tar)");
-    hipLaunchKernelGGL(frame_stats_kernel, dim3(3, N), dim3(256), 0, st, warp_src_img, 3, HW, 1.0f, gen_mean, gen_std);   // :381-382
-    check_launch("frame_stats(warp)");
+    launch_patch_warp(src_img, h->src_div, h->flow, warp_src_img, K, B, H, W, hh, ww, st);
     const bool pose = h->cfg.pose_composite != 0;       // TSNet_pose.py:399-400 composite before the L1; no alignment loss
     float bg[3];
     for (int c = 0; c < 3; ++c) bg[c] = (-h->cfg.pose_mean[c]) / 255.0f;            // TSNet_pose.py:276
-    hipLaunchKernelGGL(renorm_l1_kernel, dim3(chunks, 3, N), dim3(256), 0, st, warp_src_img, tar_img, B, HW, gen_mean, gen_std, ref_mean, ref_std, l1_part,
-                       W, pose ? 64 : 0, pose ? 192 : 0, bg[0], bg[1], bg[2]);
-    check_launch("renorm_l1");
-    if (!pose) {
-        hipLaunchKernelGGL(cosine_partial_kernel, dim3(ncos), dim3(256), 0, st, h->pg, h->sg, B * P, C, cos_part);
-        check_launch("cosine_partial");
-    }
-    hipLaunchKernelGGL(train_losses_kernel, dim3(1), dim3(64), 0, st, l1_part, K, B * 3 * chunks, (double)B * 3 * HW, cos_part, pose ? 0 : ncos, (double)B * P, losses);
-    check_launch("train_losses");
+    launch_train_tail(warp_src_img, tar_img, pose ? nullptr : h->pg, pose ? nullptr : h->sg, K, B, H, W, P, C, pose ? 64 : 0, pose ? 192 : 0, bg, ws, losses, st);
     API_END(h)
 }
 
@@ -2031,6 +2058,53 @@ int tsnet_op_fuse_tail_slots(const float* src_fea, const float* tar_fea, const f
                              int B, int K, int P, int C1, float* zbar, const int* slots, int n_src, void* stream) {
     OP_BEGIN
     op_fuse_tail_any(src_fea, tar_fea, y2, alpha, beta, B, K, -1, slots, n_src, P, C1, zbar, stream);
+    OP_END
+}
+
+int tsnet_op_patch_warp(const float* const* src_img, const float* div, const float* flow, int K, int B, int H, int W, int h, int w, float* out,
+                        void* stream) {
+    OP_BEGIN
+    if (K < 1 || K > TSNET_MAX_SOURCES) throw ArgError("patch_warp op: 1 <= K <= 8 sources");
+    if (!src_img || !div || !flow || !out) throw ArgError("patch_warp op: null tensor");
+    for (int s = 0; s < K; ++s) {
+        if (!src_img[s]) throw ArgError("patch_warp op: null source image (need K entries)");
+        if (!(div[s] > 0.f)) throw ArgError("patch_warp op: the image divisors must be positive");
+    }
+    if (B < 1 || H < 1 || W < 1 || h < 1 || w < 1 || (double)H * W >= 2147483647.0 || (double)K * B * h * w >= 2147483647.0 / 2)
+        throw ArgError("patch_warp op: bad shape (B, H, W, h, w >= 1)");
+    if (H % h || W % w || H / h != W / w) throw ArgError("patch_warp op: image size must be a multiple of the feature size, the same along both axes");
+    launch_patch_warp(src_img, div, flow, out, K, B, H, W, h, w, (hipStream_t)stream);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    OP_END
+}
+
+int tsnet_op_train_tail(float* x, const float* tar_img, const float* pg, const float* sg, int K, int B, int H, int W, int P, int C,
+                        int fore_x0, int fore_x1, const float* bg, float* gen_mean, float* gen_std, float* ref_mean, float* ref_std,
+                        float* losses, void* stream) {
+    OP_BEGIN
+    if (!x || !tar_img || !losses) throw ArgError("train_tail op: null tensor");
+    if (K < 1 || K > TSNET_MAX_SOURCES) throw ArgError("train_tail op: 1 <= K <= 8 sources");
+    if (B < 1 || (size_t)K * B > 65535 || H < 1 || W < 1 || (double)H * W >= 2147483647.0) throw ArgError("train_tail op: bad shape (B, H, W >= 1, K * B <= 65535)");
+    if ((pg == nullptr) != (sg == nullptr)) throw ArgError("train_tail op: pg and sg come together (both null: the pose form)");
+    if (pg) {
+        if (C < 4 || (C & 3)) throw ArgError("train_tail op: C must be a multiple of 4");
+        if (P < 1 || (double)B * P >= 2147483647.0) throw ArgError("train_tail op: bad shape (P >= 1)");
+        if (((uintptr_t)pg & 15) || ((uintptr_t)sg & 15)) throw ArgError("train_tail op: pg and sg must be 16-byte aligned");
+    }
+    const float zero[3] = {0.f, 0.f, 0.f};
+    if (fore_x1 > fore_x0 && !bg) throw ArgError("train_tail op: the composite needs its background");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)K * B, nl1 = N * 3 * kTrainChunks;
+    DevBufs mem;
+    float* fs = mem.alloc<float>((2 * N * 3 + 2 * (size_t)B * 3) * sizeof(float));
+    double* ds = mem.alloc<double>((nl1 + kTrainNcos) * sizeof(double));
+    HIP_TRY(hipMemsetAsync(ds, 0xFF, (nl1 + kTrainNcos) * sizeof(double), st));       // every partial a NaN: a slot read before it is written shows in the losses
+    TrainWs ws;
+    ws.gen_mean = gen_mean ? gen_mean : fs; ws.gen_std = gen_std ? gen_std : fs + N * 3;
+    ws.ref_mean = ref_mean ? ref_mean : fs + 2 * N * 3; ws.ref_std = ref_std ? ref_std : fs + 2 * N * 3 + (size_t)B * 3;
+    ws.l1_part = ds; ws.cos_part = ds + nl1;
+    launch_train_tail(x, tar_img, pg, sg, K, B, H, W, P, C, fore_x0, fore_x1, bg ? bg : zero, ws, losses, st);
+    HIP_TRY(hipStreamSynchronize(st));
     OP_END
 }
 
