@@ -612,6 +612,36 @@ int tsnet_face_labels_boxes_u8(const double* keypoints, const double* curves, in
                                const double* pool, int pool_len, int bw, void* workspace, long long workspace_len, int OH, int OW,
                                unsigned char* labels, unsigned char* masks, void* stream);
 
+/* Feathered paste masks: Image.filter(ImageFilter.GaussianBlur(r)) of Pillow on "L" images, byte for byte (csrc/mask_blur.hpp).  Pillow's
+ * Gaussian blur is three passes of an extended box blur per axis in 32-bit integers, each pass rounded to bytes, rows first, then columns.
+ *
+ * tsnet_gaussian_box_params: HOST only.  The constants of one axis for a blur radius: with s2 = radius^2 / passes, L = sqrt(12 s2 + 1),
+ * l = floor((L - 1) / 2), a = (2l + 1)(l(l + 1) - 3 s2) / (6 (s2 - (l + 1)^2)) and R = l + a, all in FLOAT arithmetic (doubles only inside
+ * sqrt and floor, as C promotes them; double arithmetic throughout gives other bytes, e.g. at radius 1 and 0.3):
+ *     *box_radius = (int)R;  *ww = (unsigned)((float)(1 << 24) / (R * 2 + 1));  *fw = ((1 << 24) - (2 * box_radius + 1) * ww) / 2
+ * One pass along a line in[0 .. n), clamp replicating the end pixels:
+ *     out[x] = (acc * ww + far * fw + (1 << 23)) >> 24,  acc = sum of in[clamp(x + d)] over |d| <= box_radius,
+ *     far = in[clamp(x - box_radius - 1)] + in[clamp(x + box_radius + 1)].
+ * Pillow's GaussianBlur has passes = 3.  A pixel farther than 3 (box_radius + 1) from every non-zero pixel is exactly 0 after the three passes.
+ * TSNET_ERR_ARG: a negative or non-finite radius (or one whose box radius is beyond 1e9), passes < 1, a NULL output.
+ *
+ * tsnet_blur_mask: out = GaussianBlur((radius_x, radius_y)) of every frame of `in`, (F,H,W) DEVICE bytes.  An axis whose radius is 0 is
+ * skipped; both 0 is a copy.
+ *   in == NULL: the source is the indicator of rect = HOST ints {x0, y0, x1, y1}, inside the image and not empty -- 255 inside, 0 outside, the
+ *          same for all F frames; no input is read.  With an input, rect is not looked at (may be NULL).
+ *   flags: bit 0 -- every non-zero input byte counts as 255 (0 / 1 masks go in as they are); bits 8-15 -- route selector, 0 = the library's
+ *          choice, 1 = the rows kernel then the columns kernel (the only route there is); every other bit must be 0.
+ *   tmp:   F * H * W DEVICE bytes of the caller's, the rows' result on its way to the columns; contents are not kept.
+ *   out:   (F,H,W) DEVICE bytes; it must be neither in nor tmp (overlaps beyond the first byte are not checked).
+ * At most two kernels on `stream` (one when an axis is skipped): no allocation, no memset, no synchronisation.
+ * TSNET_ERR_ARG (message in tsnet_op_last_error; every refusal comes before the first launch, nothing is written): out or tmp NULL; in and rect
+ * both NULL; F, H or W < 1 (or F > 65535); H or W over 512, the longest line the kernels' tile holds (kMbMaxSide, named in the message); a
+ * radius that is negative, not a number or over 4096; an empty rectangle or one not inside the image; unknown flag bits or route; out == in or
+ * out == tmp. */
+int tsnet_gaussian_box_params(float radius, int passes, int* box_radius, unsigned* ww, unsigned* fw);
+int tsnet_blur_mask(const unsigned char* in, int F, int H, int W, const int* rect, float radius_x, float radius_y, int flags,
+                    unsigned char* out, unsigned char* tmp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,7 +123,15 @@ def main():
                     "device and write <i>_<name>_full.png; the frames pasted into are synthetic (no driving frames are stored with the goldens)")
     ap.add_argument("--track-crop", action="store_true", help="a crop per frame from that frame's own landmarks (the reference's fix_crop_pos=False) "
                     "for source and driving labels; with --paste-back, a paste box per frame")
+    ap.add_argument("--feather", type=float, default=None, metavar="R", help="with --paste-back: a soft seam, the paste mask through Pillow's "
+                    "GaussianBlur(R) on the device (FrameLoader.feather_mask)")
+    ap.add_argument("--feather-from", choices=("box", "bbox"), default=None, help="with --feather: box (default) = the feathered crop box, one mask "
+                    "for the clip; bbox = every driving frame's own bounding-box mask, feathered")
     args = ap.parse_args()
+    if (args.feather is not None or args.feather_from is not None) and not args.paste_back:
+        ap.error("--feather and --feather-from need --paste-back")
+    if args.feather_from is not None and args.feather is None:
+        ap.error("--feather-from needs --feather R")
     if args.drive and not args.clip:
         ap.error("--drive needs --clip (the subject)")
     dev = torch.device("cuda", 0)
@@ -224,6 +232,9 @@ def main():
             paste = dict(paste_into=paste["paste_into"], paste_boxes=pcrops[:, [2, 0, 3, 1]])
         print(f"[demo_clip] --paste-back: pasting into SYNTHETIC {fw} x {fh} frames (a gradient; only key points are at hand) at "
               + (f"{F} boxes, one per frame, from {tuple(int(v) for v in paste['paste_boxes'][0])}" if args.track_crop else f"box {paste['paste_box']}"))
+    if args.feather is not None:
+        paste.update(paste_feather=args.feather, paste_feather_from=args.feather_from or "box")
+        print(f"[demo_clip] --feather {args.feather} from {paste['paste_feather_from']}")
     frames = runner.run(tar_lbl, tar_box, out_dir=args.out, name=name, **paste)
     print(f"[demo_clip] {demo.RESIZE_NOTE}")
     print(f"[demo_clip] {frames.shape[0]} {'full ' if args.paste_back else ''}frames written to {args.out} (crop {crop}, brush {bw}); rasterisation of {F + K} frames: {t_raster * 1e3:.2f} ms on the first call; "

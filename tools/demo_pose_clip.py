@@ -90,7 +90,15 @@ def main():
                     "byte masks, widened by the engine on load (tsnet_*_u8); the files written equal those of a run without the flag")
     ap.add_argument("--paste-back", action="store_true", help="paste every generated frame into a full video frame at the clip's crop box on the "
                     "device and write <i>_<name>_full.png; the frames pasted into are synthetic (only key points are at hand)")
+    ap.add_argument("--feather", type=float, default=None, metavar="R", help="with --paste-back: a soft seam, the paste mask through Pillow's "
+                    "GaussianBlur(R) on the device (FrameLoader.feather_mask)")
+    ap.add_argument("--feather-from", choices=("box", "bbox"), default=None, help="with --feather: box (default) = the feathered crop box, one mask "
+                    "for the clip; bbox = every driving frame's own bounding-box mask, feathered")
     args = ap.parse_args()
+    if (args.feather is not None or args.feather_from is not None) and not args.paste_back:
+        ap.error("--feather and --feather-from need --paste-back")
+    if args.feather_from is not None and args.feather is None:
+        ap.error("--feather-from needs --feather R")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     os.makedirs(args.out, exist_ok=True)
@@ -138,6 +146,9 @@ def main():
                      paste_src_box=(64, 0, 192, 256))
         print(f"[demo_pose_clip] --paste-back: pasting into SYNTHETIC {size[0]} x {size[1]} frames (a gradient; only key points are at hand) "
               f"at box {paste['paste_box']}, source rectangle {paste['paste_src_box']}")
+    if args.feather is not None:
+        paste.update(paste_feather=args.feather, paste_feather_from=args.feather_from or "box")
+        print(f"[demo_pose_clip] --feather {args.feather} from {paste['paste_feather_from']}")
     frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_pose", **paste)
     print(f"[demo_pose_clip] {frames.shape[0]} {'full ' if args.paste_back else ''}frames written to {args.out} (crop {tuple(crop)}, classes present {present}); "
           f"labels of {F + K} frames from the key points: {t_raster * 1e3:.2f} ms")

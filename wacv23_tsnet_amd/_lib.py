@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "tsnet_face_labels_boxes", "tsnet_face_labels_boxes_u8",
     "tsnet_op_upconv2d", "tsnet_op_conv2d_epi",
     "tsnet_op_patch_warp", "tsnet_op_train_tail",
+    "tsnet_gaussian_box_params", "tsnet_blur_mask",
 )
 
 
@@ -172,6 +173,9 @@ def bind(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "tsnet_op_train_tail"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
         lib.tsnet_op_patch_warp.argtypes = [pp, _fp, _vp] + [C.c_int] * 6 + [_vp, _vp]
         lib.tsnet_op_train_tail.argtypes = [_vp] * 4 + [C.c_int] * 8 + [_fp] + [_vp] * 6
+    if hasattr(lib, "tsnet_blur_mask"):          # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_gaussian_box_params.argtypes = [C.c_float, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+        lib.tsnet_blur_mask.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]
     return lib
 
 

@@ -1,6 +1,6 @@
 // clip_entries.hpp -- the C entry points of the clip side (include/tsnet_abi.h): what a video clip needs around the forward, none of it touching
 // tsnet_engine, Ctx or a convolution -- frame statistics and post-processing (postproc.hpp), the host curve fits and key-point preparation
-// (lmfit.hpp, face_adapt.hpp), rasterisation and label resizing (raster.hpp), the frame loader (frames.hpp), the paste (paste.hpp) and the labels
+// (lmfit.hpp, face_adapt.hpp), rasterisation and label resizing (raster.hpp), the frame loader (frames.hpp), the paste (paste.hpp), its feathered masks (mask_blur.hpp) and the labels
 // of a clip with a crop per frame (track_labels.hpp).  engine.cpp includes this file once, after its own entries: it is part of that translation
 // unit and of no other.  HOST code.
 #pragma once
@@ -19,6 +19,7 @@
 #include "face_adapt.hpp"
 #include "frames.hpp"
 #include "lmfit.hpp"
+#include "mask_blur.hpp"
 #include "paste.hpp"
 #include "postproc.hpp"
 #include "raster.hpp"
@@ -431,6 +432,56 @@ int tsnet_paste_frames_boxes(const unsigned char* gen, const unsigned char* mask
     if (mask) hipLaunchKernelGGL(paste_frames_boxes_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
     else hipLaunchKernelGGL(paste_frames_boxes_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
     check_launch("paste_frames_boxes");
+    OP_END
+}
+
+// ---- feathered paste masks (mask_blur.hpp): Pillow's GaussianBlur on "L" images
+int tsnet_gaussian_box_params(float radius, int passes, int* box_radius, unsigned* ww, unsigned* fw) {
+    OP_BEGIN
+    if (!box_radius || !ww || !fw) throw ArgError("gaussian_box_params: null output");
+    if (!(radius >= 0.f) || std::isinf(radius)) throw ArgError("gaussian_box_params: the radius must be finite and not negative");
+    if (passes < 1) throw ArgError("gaussian_box_params: passes must be at least 1");
+    const float R = mb_box_radius(radius, passes);
+    if (!(R >= 0.f && R <= 1e9f)) throw ArgError("gaussian_box_params: the box radius of this blur radius does not fit an int");
+    mb_line_constants(R, *box_radius, *ww, *fw);
+    OP_END
+}
+
+int tsnet_blur_mask(const unsigned char* in, int F, int H, int W, const int* rect, float radius_x, float radius_y, int flags,
+                    unsigned char* out, unsigned char* tmp, void* stream) {
+    OP_BEGIN
+    if (!out || !tmp) throw ArgError("blur_mask: null output or intermediate");
+    if (!in && !rect) throw ArgError("blur_mask: neither an input image nor a rectangle");
+    if (F < 1 || F > 65535 || H < 1 || W < 1) throw ArgError("blur_mask: bad shape");
+    if (H > kMbMaxSide || W > kMbMaxSide)
+        throw ArgError("blur_mask: image of " + std::to_string(H) + " x " + std::to_string(W) + " (H x W): a side is over kMbMaxSide = " + std::to_string(kMbMaxSide));
+    for (float r : {radius_x, radius_y})
+        if (!(r >= 0.f) || !(r <= kMbMaxRadius)) throw ArgError("blur_mask: a radius must be a number in 0 .. " + std::to_string((int)kMbMaxRadius));
+    if ((flags & ~0xFF01) != 0) throw ArgError("blur_mask: unknown flag bits");
+    if (((flags >> 8) & 0xFF) > 1) throw ArgError("blur_mask: unknown route " + std::to_string((flags >> 8) & 0xFF) + " (0 = the library's choice, 1 = rows then columns)");
+    if (!in && (rect[0] < 0 || rect[1] < 0 || rect[2] > W || rect[3] > H || rect[2] <= rect[0] || rect[3] <= rect[1]))
+        throw ArgError("blur_mask: the rectangle is empty or not inside the image");
+    if (out == in || out == tmp) throw ArgError("blur_mask: out must not be in or tmp");
+    hipStream_t s = (hipStream_t)stream;
+    const bool rows = radius_x != 0.f, cols = radius_y != 0.f;
+    MaskBlurArgs a{in, out, H, W, 0, 0, 0, 0, flags & 1, 0, 0, 0u, 0u};
+    if (!in) { a.x0 = rect[0]; a.y0 = rect[1]; a.x1 = rect[2]; a.y1 = rect[3]; }
+    const dim3 grid_rows((H + kMbLines - 1) / kMbLines, F), grid_cols((W + kMbLines - 1) / kMbLines, F);
+    if (rows) {                                                      // the rows first; through tmp when the columns follow
+        a.out = cols ? tmp : out;
+        a.passes = kMbPasses;
+        mb_line_constants(mb_box_radius(radius_x, kMbPasses), a.radius, a.ww, a.fw);
+        hipLaunchKernelGGL(mask_blur_rows_kernel, grid_rows, dim3(256), 0, s, a);
+        check_launch("mask_blur_rows");
+        a.in = tmp; a.binary = 0;                                    // what follows reads bytes that are final
+    }
+    if (cols || !rows) {                                             // neither axis: the column form with no pass is the copy
+        a.out = out;
+        a.passes = cols ? kMbPasses : 0;
+        if (cols) mb_line_constants(mb_box_radius(radius_y, kMbPasses), a.radius, a.ww, a.fw);
+        hipLaunchKernelGGL(mask_blur_cols_kernel, grid_cols, dim3(256), 0, s, a);
+        check_launch("mask_blur_cols");
+    }
     OP_END
 }
 

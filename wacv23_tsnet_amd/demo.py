@@ -249,7 +249,7 @@ class ClipRunner:
         return self.frames(tar_lbl, tar_bbox)[0]
 
     def run(self, tar_lbls: torch.Tensor, tar_bboxs: torch.Tensor, out_dir: str = None, tar_imgs: torch.Tensor = None, name: str = "clip",
-            paste_into=None, paste_box=None, paste_src_box=None, paste_mask=None, paste_boxes=None):
+            paste_into=None, paste_box=None, paste_src_box=None, paste_mask=None, paste_boxes=None, paste_feather=None, paste_feather_from="box"):
         """tar_lbls (F,L,H,W), tar_bboxs (F,H,W); returns the generated frames (F,H,W,3) uint8 (host).  With out_dir: strips + GIF.
         paste_into: (F,h,w,3) uint8 video frames, tensor or array -- every group's bytes are resized to paste_box = (x0, y0, x1, y1) (the crop box
         the clip was loaded with; it may leave the frame) and pasted into its frames on the device (`FrameLoader.paste`: Pillow's resize + paste,
@@ -257,10 +257,20 @@ class ClipRunner:
         (F,H,W) uint8, None = plain paste.  `run` then returns the full frames (F,h,w,3) uint8 (host), a copy -- paste_into is left as it is --
         and out_dir also gets them as "{i:06d}_{name}_full.png"; strips and GIF are written from the generated bytes as without it.
         paste_boxes: (F,4) instead of paste_box, a box per frame (tracking crops, raster.crop_coords_clip in x0, y0, x1, y1 order): every group
-        pastes with its slice of boxes, still one launch per group (`tsnet_paste_frames_boxes`)."""
+        pastes with its slice of boxes, still one launch per group (`tsnet_paste_frames_boxes`).
+        paste_feather: a radius (or (rx, ry)) for a soft seam (`FrameLoader.feather_mask`: Pillow's GaussianBlur of the mask, byte for byte), None =
+        the hard seam.  paste_feather_from="box": the feathered indicator of paste_src_box shrunk by `feather_inset`, made once per run and reused
+        for every group; "bbox": every group's tar_bboxs rows (float32 or compact) become that group's mask -- the feathered face region, another
+        for every frame.  With paste_mask the given mask is blurred instead (once, before the first group)."""
         import os
         n = tar_lbls.shape[0]
         full = None
+        if paste_feather_from not in ("box", "bbox"):
+            raise ValueError(f"paste_feather_from must be 'box' or 'bbox', not {paste_feather_from!r}")
+        if paste_feather is not None and paste_into is None:
+            raise ValueError("paste_feather needs paste_into")
+        if paste_feather is not None and paste_mask is not None and paste_feather_from == "bbox":
+            raise ValueError("paste_mask and paste_feather_from='bbox': one source for the mask, not both")
         if paste_box is not None and paste_boxes is not None:
             raise ValueError("paste_box and paste_boxes: one box for the clip or one per frame, not both")
         if paste_into is not None:
@@ -278,12 +288,23 @@ class ClipRunner:
             full = host.to(dev).contiguous()
             if full.data_ptr() == host.data_ptr():                  # already on the device: paste into a copy
                 full = full.clone()
-        groups = []
+            if paste_feather is not None and paste_mask is not None:
+                paste_mask = ld._paste_mask(paste_mask, paste_feather, None, None)
+        groups, box_mask = [], None
         for i in range(0, n, self.batch):
             g = self.frames(tar_lbls[i:i + self.batch], tar_bboxs[i:i + self.batch])
             if full is not None:
+                mask = None if paste_mask is None else paste_mask[i:i + self.batch]
+                if paste_feather is not None and paste_mask is None:
+                    if paste_feather_from == "bbox":                # 0 / 1 rows in either form: every non-zero byte counts as 255
+                        tb = tar_bboxs[i:i + self.batch].to(dev)
+                        mask = ld.feather_mask(tb if tb.dtype == torch.uint8 else (tb != 0).to(torch.uint8), paste_feather, binary=True)
+                    else:
+                        if box_mask is None:                        # one mask for the run: the first group is the largest
+                            box_mask = ld._paste_mask(None, paste_feather, tuple(g.shape[:3]), paste_src_box)
+                        mask = box_mask[:g.shape[0]]
                 ld.paste(g, full[i:i + self.batch], paste_box if paste_boxes is None else paste_boxes[i:i + self.batch], src_box=paste_src_box,
-                         mask=None if paste_mask is None else paste_mask[i:i + self.batch], inplace=True)
+                         mask=mask, inplace=True)
             groups.append(g)
         out = torch.cat(groups).cpu().numpy()
         if out_dir:

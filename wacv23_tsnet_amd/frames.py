@@ -9,7 +9,8 @@ doubles per axis), so the tensors EQUAL the reference's, byte for byte before th
 
 The way back is here too: `FrameLoader.paste` resizes generated frames (the bytes `DemoPostprocessor` returns) to the crop box they came from and
 pastes them into the full frames (csrc/paste.hpp, `tsnet_paste_frames`) -- Pillow's `crop().resize()` + `Image.paste()`, mask included, byte
-for byte (tests/test_paste_frames.py).
+for byte (tests/test_paste_frames.py).  `FrameLoader.feather_mask` makes the mask of a soft seam (csrc/mask_blur.hpp, `tsnet_blur_mask`): Pillow's
+`Image.filter(ImageFilter.GaussianBlur(r))` on "L" images, byte for byte (tests/test_feather_mask.py); `paste(..., feather=r)` uses it.
 
 Decoding PNG / JPEG files stays with PIL on the host; the training loaders' random crop / scale / flip are out of scope."""
 from __future__ import annotations
@@ -262,7 +263,77 @@ class FrameLoader:
             raise ValueError(f"expected uint8 {what} of shape {want}, got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
         return t
 
-    def paste(self, gen, frames, box: Sequence[int], src_box: Optional[Sequence[int]] = None, mask=None, inplace: bool = False) -> torch.Tensor:
+    # ------------------------------------------------------------------------------------------------------------------ feathered masks
+    def _box_params(self, radius: float) -> Tuple[int, int, int]:
+        """(box_radius, ww, fw) of one axis from `tsnet_gaussian_box_params` (three passes, as Pillow's GaussianBlur)"""
+        br, ww, fw = C.c_int(), C.c_uint(), C.c_uint()
+        if self.lib.tsnet_gaussian_box_params(float(radius), 3, C.byref(br), C.byref(ww), C.byref(fw)) != 0:
+            raise ValueError(f"feather radius {radius!r}: {self.lib.tsnet_op_last_error().decode()}")
+        return br.value, ww.value, fw.value
+
+    @staticmethod
+    def _radii(radius) -> Tuple[float, float]:
+        rx, ry = (radius, radius) if np.ndim(radius) == 0 else radius
+        return float(rx), float(ry)
+
+    def feather_inset(self, radius):
+        """3 (box_radius + 1) + 1: by how many pixels a rectangle must be shrunk per side so that the outermost ring of its box is exactly 0
+        after `feather_mask` (a pixel farther than 3 (box_radius + 1) from every non-zero pixel stays 0).  A number for a number, (ix, iy) for
+        a radius pair (rx, ry)."""
+        if np.ndim(radius) == 0:
+            return 3 * (self._box_params(radius)[0] + 1) + 1
+        rx, ry = self._radii(radius)
+        return 3 * (self._box_params(rx)[0] + 1) + 1, 3 * (self._box_params(ry)[0] + 1) + 1
+
+    def feather_mask(self, src, radius, size: Optional[Sequence[int]] = None, rect: Optional[Sequence[int]] = None, binary: bool = False) -> torch.Tensor:
+        """A paste mask with a soft edge (`tsnet_blur_mask`, csrc/mask_blur.hpp): per frame f, byte for byte,
+            Image.fromarray(src[f], "L").filter(ImageFilter.GaussianBlur(radius))
+        src: (F,H,W) uint8, tensor or array (uploaded when on the host); binary=True: every non-zero byte counts as 255 (0 / 1 masks as they are).
+        src=None: the source is the indicator of rect = (x0, y0, x1, y1) -- 255 inside, 0 outside -- in size = (F,H,W), the same for every frame;
+        nothing is read or uploaded.  radius: a number or (rx, ry), as GaussianBlur takes it; an axis with radius 0 is skipped.  H, W <= 512.
+        Returns the (F,H,W) uint8 mask on the device.  The intermediate between the two kernels is the loader's and kept between calls; on
+        device tensors the call only enqueues (at most) two kernels on the current stream."""
+        rx, ry = self._radii(radius)
+        rect_c = None
+        if src is None:
+            if size is None or rect is None:
+                raise ValueError("feather_mask(None, ...) needs size=(F,H,W) and rect=(x0, y0, x1, y1)")
+            F, H, W = (int(v) for v in size)
+            rect_c = (C.c_int * 4)(*(int(v) for v in rect))
+            m = None
+        else:
+            m = self._u8(src, "mask", 3).to(self.device).contiguous()
+            F, H, W = m.shape
+        n = max(F * H * W, 1)
+        tmp = getattr(self, "_feather_tmp", None)
+        if tmp is None or tmp.numel() < n:
+            tmp = self._feather_tmp = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out = torch.empty((max(F, 0), max(H, 0), max(W, 0)), dtype=torch.uint8, device=self.device)
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        with ctx:
+            rc = self.lib.tsnet_blur_mask(None if m is None else m.data_ptr(), F, H, W, rect_c, rx, ry, 1 if binary else 0,
+                                          out.data_ptr(), tmp.data_ptr(), self._stream())
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"tsnet_blur_mask failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep_feather = [m]                                     # alive until the stream has consumed it
+        return out
+
+    def _paste_mask(self, mask, feather, size, src_box):
+        """the mask of a paste with feather=radius: the given mask blurred (0 / 1 masks as binary), or, in size = (F,GH,GW), the feathered
+        indicator of the source rectangle shrunk by `feather_inset` per side"""
+        if mask is not None:
+            m = self._u8(mask, "mask", 3)
+            return self.feather_mask(m, feather, binary=bool(m.numel()) and int(m.max()) <= 1)
+        F, GH, GW = size
+        sx0, sy0, sx1, sy1 = (0, 0, GW, GH) if src_box is None else (int(v) for v in src_box)
+        ix, iy = self.feather_inset(self._radii(feather))
+        rect = (sx0 + ix, sy0 + iy, sx1 - ix, sy1 - iy)
+        if rect[2] <= rect[0] or rect[3] <= rect[1]:
+            raise ValueError(f"feather {feather!r} needs an inset of {ix} x {iy} pixels per side (feather_inset), which leaves nothing of the "
+                             f"{sx1 - sx0} x {sy1 - sy0} source rectangle")
+        return self.feather_mask(None, feather, size=(F, GH, GW), rect=rect)
+
+    def paste(self, gen, frames, box: Sequence[int], src_box: Optional[Sequence[int]] = None, mask=None, inplace: bool = False, feather=None) -> torch.Tensor:
         """Generated frames back into the video (`tsnet_paste_frames`, csrc/paste.hpp): per frame f, byte for byte,
             g = Image.fromarray(gen[f]).crop(src_box).resize((x1 - x0, y1 - y0)); frame_f.paste(g, (x0, y0), m)
         with m the mask through the same crop and resize, or None.  gen: (F,GH,GW,3) uint8 RGB as `DemoPostprocessor` returns it; frames:
@@ -270,7 +341,13 @@ class FrameLoader:
         written); src_box: the part of gen that holds picture, None = all of it; mask: (F,GH,GW) uint8, 255 = gen, 0 = frame (Pillow's
         paste_mask_L blend in between).  Tensors or arrays; what is on the host is uploaded.  Returns the frames on the device: a clone, or with
         inplace=True `frames` itself when it already is a contiguous tensor on the device.  gen / mask must not share memory with frames.
-        box may be an (F,4) array-like, one box per frame (`tsnet_paste_frames_boxes`, still one kernel); src_box stays one per call."""
+        box may be an (F,4) array-like, one box per frame (`tsnet_paste_frames_boxes`, still one kernel); src_box stays one per call.
+        feather: a radius (or (rx, ry)) for a soft seam, None = the call as it always was.  With mask=None the mask is `feather_mask` of the
+        indicator of src_box shrunk by `feather_inset` per side -- in Pillow's terms the rectangle image through
+        filter(ImageFilter.GaussianBlur(feather)) -- so that the blend reaches exactly 0 on the source rectangle's outermost ring; a
+        rectangle too small for the inset is a ValueError.  With a mask, the mask is blurred first (one holding only 0 / 1 as 0 / 255)."""
+        if feather is not None:
+            mask = self._paste_mask(mask, feather, tuple(self._u8(gen, "generated frames", 4).shape[:3]), src_box)
         if np.ndim(box) == 2:
             return self._paste_boxes(gen, frames, box, src_box, mask, inplace)
         g = self._u8(gen, "generated frames", 4)
@@ -307,21 +384,22 @@ class FrameLoader:
         self._keep = [g, m]                                          # alive until the stream has consumed them
         return out
 
-    def paste_face(self, gen, frames, crop: Sequence[int], mask=None, inplace: bool = False) -> torch.Tensor:
+    def paste_face(self, gen, frames, crop: Sequence[int], mask=None, inplace: bool = False, feather=None) -> torch.Tensor:
         """The inverse of `face`: crop = [min_y, max_y, min_x, max_x]; the whole generated image goes back into that box."""
         if np.ndim(crop) == 2:
-            return self.paste(gen, frames, self._boxes(crop, len(frames), (2, 0, 3, 1)), mask=mask, inplace=inplace)
+            return self.paste(gen, frames, self._boxes(crop, len(frames), (2, 0, 3, 1)), mask=mask, inplace=inplace, feather=feather)
         min_y, max_y, min_x, max_x = crop
-        return self.paste(gen, frames, (min_x, min_y, max_x, max_y), mask=mask, inplace=inplace)
+        return self.paste(gen, frames, (min_x, min_y, max_x, max_y), mask=mask, inplace=inplace, feather=feather)
 
-    def paste_pose(self, gen, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mask=None, inplace: bool = False) -> torch.Tensor:
+    def paste_pose(self, gen, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mask=None, inplace: bool = False,
+                   feather=None) -> torch.Tensor:
         """The inverse of `pose`: crop = (xs, ys, xe, ye); the img_size picture between resize_square's bars goes back into that box."""
         gh, gw = (gen.shape[1], gen.shape[2]) if hasattr(gen, "shape") and len(gen.shape) == 4 else (0, 0)
         S = max(int(img_size[0]), int(img_size[1]))
         if (gh, gw) != (S, S):
             raise ValueError(f"expected generated frames of {S} x {S} (img_size {tuple(img_size)} padded square), got {gw} x {gh}")
         px, py = (S - int(img_size[0])) // 2, (S - int(img_size[1])) // 2
-        return self.paste(gen, frames, crop, src_box=(px, py, px + int(img_size[0]), py + int(img_size[1])), mask=mask, inplace=inplace)
+        return self.paste(gen, frames, crop, src_box=(px, py, px + int(img_size[0]), py + int(img_size[1])), mask=mask, inplace=inplace, feather=feather)
 
 
 class _Null:
