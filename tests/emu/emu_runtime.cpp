@@ -41,7 +41,8 @@ unsigned char* g_dyn_smem = g_smem_buf;
 namespace {
 constexpr size_t kStack = 96 * 1024;
 struct Fiber { void* sp = nullptr; bool done = false; unsigned char* stack = nullptr; };
-std::vector<Fiber> g_fibers;
+struct FiberPool : std::vector<Fiber> { ~FiberPool() { for (Fiber& f : *this) free(f.stack); } };     // the stacks live as long as the process and go with it
+FiberPool g_fibers;
 void* g_sched_sp = nullptr;
 int g_cur = -1, g_nt = 0, g_alive = 0;
 const std::function<void()>* g_body = nullptr;

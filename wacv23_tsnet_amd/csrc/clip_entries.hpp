@@ -1,7 +1,7 @@
 // clip_entries.hpp -- the C entry points of the clip side (include/tsnet_abi.h): what a video clip needs around the forward, none of it touching
 // tsnet_engine, Ctx or a convolution -- frame statistics and post-processing (postproc.hpp), the host curve fits and key-point preparation
 // (lmfit.hpp, face_adapt.hpp), rasterisation and label resizing (raster.hpp), the frame loader (frames.hpp), the paste (paste.hpp), its feathered masks (mask_blur.hpp) and the labels
-// of a clip with a crop per frame (track_labels.hpp).  engine.cpp includes this file once, after its own entries: it is part of that translation
+// of a clip with a crop per frame (track_labels.hpp).  engine.cpp includes this file once, last, after its own entries and op_entries.hpp: it is part of that translation
 // unit and of no other.  HOST code.
 #pragma once
 #ifndef TSNET_ENGINE_CPP

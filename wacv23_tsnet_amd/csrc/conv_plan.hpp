@@ -1,7 +1,7 @@
 // conv_plan.hpp -- which kernel, tile and schedule a convolution launch runs on.  Plain C++17: no HIP, no device code, so that every launch
 // choice can be checked on the CPU (tests/test_conv_plan.py).  The planner VALIDATES AND CHOOSES: plan_conv refuses (std::invalid_argument)
 // every layer geometry the kernels cannot index (validate_conv) and every request whose kernel the product build does not instantiate, so
-// a ConvPlan always names a kernel that exists.  engine.cpp's run_conv checks what depends on pointers, asks plan_conv, fills ConvArgs from
+// a ConvPlan always names a kernel that exists.  run_conv (launch.hpp, part of engine.cpp's unit) checks what depends on pointers, asks plan_conv, fills ConvArgs from
 // the plan and hands both to the family's launcher (kernels.hpp), which only dispatches: no launcher repeats a rule written here.
 //
 // The promise these rules keep: the kernel family and the tile rows (and with them the statistics tiling) depend on the layer and the frame

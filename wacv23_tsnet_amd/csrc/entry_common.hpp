@@ -1,6 +1,6 @@
 // entry_common.hpp -- what every C entry point of the library needs and nothing of the engine: how a HIP failure or a refused argument becomes
 // an exception (HIP_TRY, ArgError / WeightError, check_launch), how the handle-free entries turn one into a status code and the text behind
-// tsnet_op_last_error (OP_BEGIN / OP_END), and the grid of an elementwise launch.  Included by engine.cpp and by clip_entries.hpp, which is part
+// tsnet_op_last_error (OP_BEGIN / OP_END), and the grid of an elementwise launch.  Included by launch.hpp, op_entries.hpp and clip_entries.hpp, which are parts
 // of engine.cpp's unit: everything here has internal linkage, as it had inside engine.cpp.  HOST code.
 #pragma once
 #include <hip/hip_runtime.h>
