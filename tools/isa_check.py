@@ -76,28 +76,31 @@ def analyse(asm_path, pattern=""):
 _ASM = {}
 
 
-def compile_all(units, tools=False):
+def compile_all(units, tools=False, csrc=None):
     """compile several translation units at once (hipcc is single-threaded per unit: four units in the time of the slowest); compile_asm then returns from the cache"""
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(len(units)) as ex:
-        list(ex.map(lambda u: compile_asm(tools, u), units))
+        list(ex.map(lambda u: compile_asm(tools, u, csrc), units))
 
 
-def compile_asm(tools=False, unit="conv_h2_launch.cpp"):
-    if (tools, unit) not in _ASM:
-        _ASM[(tools, unit)] = _compile_asm(tools, unit)
-    return _ASM[(tools, unit)]
+def compile_asm(tools=False, unit="conv_h2_launch.cpp", csrc=None):
+    """csrc: the csrc directory of ANOTHER checkout of this project (tools/isa_diff.py); its include/ is taken from that checkout too"""
+    csrc = os.path.abspath(csrc) if csrc else None
+    if (tools, unit, csrc) not in _ASM:
+        _ASM[(tools, unit, csrc)] = _compile_asm(tools, unit, csrc)
+    return _ASM[(tools, unit, csrc)]
 
 
-def _compile_asm(tools, unit):
+def _compile_asm(tools, unit, csrc=None):
     tmp = tempfile.mkdtemp(prefix="tsnet_isa_")
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     from wacv23_tsnet_amd import build as B          # the library's own flags: the ISA looked at is the ISA that ships
-    cmd = ["/opt/rocm/bin/hipcc"] + B.FLAGS + B.UNIT_FLAGS.get(unit, []) + ["-save-temps", "-I" + os.path.join(ROOT, "include")]
+    cmd = ["/opt/rocm/bin/hipcc"] + B.FLAGS + B.UNIT_FLAGS.get(unit, []) + ["-save-temps"]
     if tools:
         cmd.append("-DTSNET_TOOLS")
-    cmd += ["-c", os.path.join(ROOT, "wacv23_tsnet_amd", "csrc", unit), "-o", os.path.join(tmp, "x.o")]
+    src = os.path.abspath(csrc) if csrc else os.path.join(ROOT, "wacv23_tsnet_amd", "csrc")
+    cmd += ["-I" + os.path.join(os.path.dirname(os.path.dirname(src)), "include"), "-c", os.path.join(src, unit), "-o", os.path.join(tmp, "x.o")]
     subprocess.run(cmd, cwd=tmp, check=True, capture_output=True)
     return os.path.join(tmp, unit.replace(".cpp", "") + "-hip-amdgcn-amd-amdhsa-gfx950.s")
 

@@ -1,5 +1,20 @@
 // conv_common.hpp -- what every convolution kernel of the forward shares: the operand format, the hardware hooks, the argument block,
-// the epilogue (bias, fp64 InstanceNorm partials, in-kernel finalize, fp32 store) and the weight packers.
+// the steps every tile function repeats around its own schedule, and the epilogue (bias, fp64 InstanceNorm partials, in-kernel finalize,
+// fp32 store).  The shared steps, each spelled once here and called from the tile functions of conv_h2 / h2r / g64 / h2s32 / w1 / w1_one:
+//   reflect_index, TSNET_RESOLVE_PAD      reflection, or the bounds test of zero padding, of a tap's input pixel
+//   conv_operand_scale, conv_unscale      host or device operand scale of an image; the epilogue's 2^-(sa + sw)
+//   conv_mfma                             one MFMA of a chain (zeroed c when the chain is fresh; bf16 or fp16 instruction)
+//   transform_octet                       IN + ReLU (branch-free), the operand scale, zero padding kept after the affine transform
+//   store_operand_octet / _quad           one plane, or the hi / lo split (two pairs per statement), then the planes' stores
+//   bf16x8_widen / bf16x4_widen           bf16 storage -> fp32, exactly
+//   patch_tile, patch_out_index           the PR x 32 rectangle of a patch tile; its epilogue row map
+//   row_tile, row_out_index               the row tile of the implicit GEMMs; its epilogue row map
+// conv_w1 resolves an item's row once and its columns per pixel, so it uses reflect_index alone, not the pair.
+// A kernel's code must not move when a step is shared (tools/isa_diff.py against the parent commit): where a helper changed the code of a tile
+// function, that function keeps its own copy under a "not shared" comment.  Deliberately NOT shared, for the same reason: the weight-plane
+// descriptors, the transform-table fill, the accumulator init and the un-scale loop (they take the descriptor or accumulator arrays by
+// reference, or hold the table loop, and change register allocation in 18 - 75 kernels of a unit: the figures of the trial that preceded
+// this clean-up, on helpers by reference and by template argument; no further spelling was tried since).
 //
 // Operand format (tools/probes/split_probe.hip).  An fp32 value x scaled by a power of two s is held as two fp16
 // numbers  hi = rne(x*s),  lo = rne(x*s - hi):  the residual of a round-to-nearest hi has at most 12 significant bits left and lo rounds
@@ -236,6 +251,13 @@ __device__ __forceinline__ void bf16x8_widen(const F4& p, F4 (&o)[2]) {
     }
 }
 
+// four consecutive bf16 channels (one 8-byte vector) -> one float4, exactly
+__device__ __forceinline__ void bf16x4_widen(const F2& p, F4& o) {
+    const unsigned w0 = __builtin_bit_cast(unsigned, p.v[0]), w1 = __builtin_bit_cast(unsigned, p.v[1]);
+    o.v[0] = __builtin_bit_cast(float, w0 << 16); o.v[1] = __builtin_bit_cast(float, w0 & 0xFFFF0000u);
+    o.v[2] = __builtin_bit_cast(float, w1 << 16); o.v[3] = __builtin_bit_cast(float, w1 & 0xFFFF0000u);
+}
+
 // The eight channels at fp32 byte offset (voff + soff) of an activation tensor -- or, xb16, of the same tensor stored as bf16 (half the
 // offsets, one load).  A lane whose voff is kOOB reads zeros either way (kOOB / 2 still lies past any descriptor: tensors are < 2 GiB).
 __device__ __forceinline__ void load_x_octet(const tsnet_brsrc_t& rs, bool xb16, unsigned voff, unsigned soff, F4 (&o)[2]) {
@@ -319,6 +341,113 @@ __device__ __forceinline__ void transform_octet(const F4 (&sx)[2], const float* 
             for (int e = 0; e < 4; ++e) t[q].v[e] = __builtin_fmaxf(sx[q].v[e] * in_scale, relu_floor);
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// THE STEPS EVERY TILE FUNCTION REPEATS around its own schedule, each spelled once (conv_h2 / h2r / g64 / h2s32 / w1 / w1_one call them).
+// They take scalars, F4s or a small fixed array of them -- the two scales come back through float references, the staging stores write
+// through the pointer they are given -- and never the descriptor or accumulator arrays of a tile function: inlined, they leave every
+// kernel's code as the hand-written copies had it (checked per tile function with tools/isa_diff.py).
+
+// Reflection padding (nn.ReflectionPad2d: the border pixel is not repeated) of index i on an axis of n, |overhang| < n.
+__device__ __forceinline__ int reflect_index(int i, int n) {
+    i = i < 0 ? -i : i;
+    return i >= n ? 2 * (n - 1) - i : i;
+}
+// The input pixel (iy, ix) of a tap under the layer's padding: reflected into the map, or -- zero padding -- tested against it into ok (a
+// lane without a pixel gets the offset kOOB: its load returns zeros and costs no branch).  A macro: as a function, with ok by reference or
+// by value, the bounds test is selected in another order in every kernel that has it.
+#define TSNET_RESOLVE_PAD(a, iy, ix, ok)                                             \
+    do {                                                                             \
+        if ((a).reflect) {                                                           \
+            iy = reflect_index(iy, (a).H);                                           \
+            ix = reflect_index(ix, (a).W);                                           \
+        } else {                                                                     \
+            ok = ok && iy >= 0 && iy < (a).H && ix >= 0 && ix < (a).W;               \
+        }                                                                            \
+    } while (0)
+
+// Operand scale of image img: the host's a-priori pair, or -- the producer published max |x| -- derived on the device.  The bf16 plane
+// (NPROD = 1) holds the operand itself and has no scale.
+template <int NPROD>
+__device__ __forceinline__ void conv_operand_scale(const ConvArgs& a, int img, float& in_scale, float& in_unscale) {
+    in_scale = a.in_scale; in_unscale = a.in_unscale;
+    if (NPROD != 1 && a.in_amax) h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
+}
+// ... and what the epilogue multiplies by: 2^-(sa + sw), exact
+__device__ __forceinline__ float conv_unscale(const float* w_unscale, float in_unscale) { return w_unscale ? in_unscale * w_unscale[0] : in_unscale; }
+
+// One MFMA of a chain: c + a * b, or -- fresh: the chain starts here -- a * b alone (c zeroed in registers: the accumulator is not cleared
+// between chains).  The bf16 instruction for NPROD = 1, the fp16 one for every other operand kind.
+template <int NPROD>
+__device__ __forceinline__ f32x16 conv_mfma(const F4& a, const F4& b, f32x16 c, bool fresh) {
+    if (fresh) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c[r] = 0.f;
+    }
+    if (NPROD == 1) return TSNET_MFMA_BF16(a, b, c);
+    else return TSNET_MFMA_F16(a, b, c);
+}
+
+// The tail of a staging store.  Octet form: eight transformed channels -> the one plane (bf16, or F16P fp16) at dst, or the hi plane at
+// dst and the lo plane at dst + lo_off, 16 bytes each.
+template <bool ONEP, bool F16P>
+__device__ __forceinline__ void store_operand_octet(const F4 (&t)[2], unsigned char* dst, int lo_off) {
+    F4 Hh, Ll;
+    if (ONEP) {
+        one_plane_octet<F16P>(t[0], t[1], Hh);
+        *reinterpret_cast<F4*>(dst) = Hh;
+    } else {
+        split_h2_octet(t[0], t[1], Hh, Ll);
+        *reinterpret_cast<F4*>(dst) = Hh;
+        *reinterpret_cast<F4*>(dst + lo_off) = Ll;
+    }
+}
+// Quad form (lane = channel quad: conv_g64, conv_h2s32): four channels -> 8 bytes per plane, the half of a fragment octet.
+template <bool ONEP, bool F16P>
+__device__ __forceinline__ void store_operand_quad(const float (&t)[4], unsigned char* dst, int plane_off) {
+    if (ONEP) {
+        uint2 w;
+        w.x = cvt_pk_one<F16P>(t[0], t[1]); w.y = cvt_pk_one<F16P>(t[2], t[3]);
+        *reinterpret_cast<uint2*>(dst) = w;
+    } else {
+        unsigned h0, l0, h1, l1;
+        TSNET_SPLIT_2PAIRS(t[0], t[1], t[2], t[3], h0, l0, h1, l1);
+        uint2 hw2, lw2;
+        hw2.x = h0; hw2.y = h1; lw2.x = l0; lw2.y = l1;
+        *reinterpret_cast<uint2*>(dst) = hw2;
+        *reinterpret_cast<uint2*>(dst + plane_off) = lw2;
+    }
+}
+
+// A PATCH tile: tile_m -> the PR x 32 output rectangle (oy0, ox0) of image img; tin = its index inside the image, tper = tiles per image.
+struct PatchTile { int tper, img, tin, oy0, ox0; };
+template <int PR>
+__device__ __forceinline__ PatchTile patch_tile(const ConvArgs& a, int tile_m) {
+    PatchTile t;
+    const int tcols = a.Wo / kPatchCols;
+    t.tper = (a.Ho / PR) * tcols;
+    t.img = tile_m / t.tper; t.tin = tile_m - t.img * t.tper;
+    t.oy0 = (t.tin / tcols) * PR; t.ox0 = (t.tin % tcols) * kPatchCols;
+    return t;
+}
+// ... and the output position of its local row l (32 per output row) for the epilogue; m_img = the image's first position
+__device__ __forceinline__ int patch_out_index(const ConvArgs& a, int m_img, int oy0, int ox0, int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); }
+
+// A ROW tile of the implicit GEMMs: block -> BM consecutive output positions from r0 of ONE image (a ragged last tile) x BN channels from n0.
+struct RowTile { int tile_m, n0, hw, img, r0; };
+template <int BM, int BN>
+__device__ __forceinline__ RowTile row_tile(const ConvArgs& a, int block) {
+    RowTile t;
+    const int bid = xcd_item(block, a.tiles_m * a.tiles_n);
+    t.tile_m = bid / a.tiles_n;
+    t.n0 = (bid - t.tile_m * a.tiles_n) * BN;
+    t.hw = a.Ho * a.Wo;
+    t.img = t.tile_m / a.tpi;
+    t.r0 = (t.tile_m - t.img * a.tpi) * BM;
+    return t;
+}
+// ... and the output position of its local row l for the epilogue: -1 for a row past the end of the image
+__device__ __forceinline__ int row_out_index(const RowTile& t, int m_img, int l) { return t.r0 + l < t.hw ? m_img + t.r0 + l : -1; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Bilinear x2 upsample (nn.Upsample, align_corners = False) in ONE spelling: upsample2x_kernel (norm_elementwise.hpp) and the fused patch

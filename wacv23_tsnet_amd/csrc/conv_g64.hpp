@@ -13,6 +13,8 @@
 //     whole step ahead (four sets: the group index is the set index, static).
 // Tiles: BM = 64 rows (four waves side by side over 128 channels: the 1 x 1 layers' 4096 rows make 256 workgroups) or 128 rows (eight waves,
 // 2 x 4); BN = 128.  An M tile lies inside one image (ragged last tile), as in conv_h2r.
+// Padding, operand scale, the MFMA of a chain, the staging store's tail (quad form), the bf16 quad widening and the row-tile decode are
+// spelled once in conv_common.hpp.
 #pragma once
 #include "conv_common.hpp"
 
@@ -42,14 +44,10 @@ void conv_g64_kernel(ConvArgs a) {
     const int wm0 = (wave / WARPS_N) * 64, wn0 = (wave % WARPS_N) * 32;
     const int li = lane & 31, lh = lane >> 5;
 
-    const int bid = xcd_item(blockIdx.x, a.tiles_m * a.tiles_n);
-    const int tile_m = bid / a.tiles_n, tile_n = bid - tile_m * a.tiles_n;
-    const int n0 = tile_n * BN;
-    const int hw = a.Ho * a.Wo;
-    const int img = tile_m / a.tpi;
-    const int r0 = (tile_m - img * a.tpi) * BM;                      // first position of the tile inside its image
-    float in_scale = a.in_scale, in_unscale = a.in_unscale;
-    if (NPROD != 1 && a.in_amax) h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
+    const RowTile rt = row_tile<BM, BN>(a, blockIdx.x);
+    const int n0 = rt.n0, hw = rt.hw, img = rt.img, r0 = rt.r0;      // r0: first position of the tile inside its image
+    float in_scale, in_unscale;
+    conv_operand_scale<NPROD>(a, img, in_scale, in_unscale);
 
     const int C2 = a.Cin - a.Csplit;
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
@@ -102,14 +100,7 @@ void conv_g64_kernel(ConvArgs a) {
         for (int s = 0; s < RS; ++s) {
             int iy = s_oy[s] + ky, ix = s_ox[s] + kx;
             bool ok = s_valid[s] && tap < a.taps;
-            if (a.reflect) {
-                iy = iy < 0 ? -iy : iy;
-                iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-                ix = ix < 0 ? -ix : ix;
-                ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
-            } else {
-                ok = ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            }
+            TSNET_RESOLVE_PAD(a, iy, ix, ok);
             am[s] = ok ? 1.f : 0.f;
             if (second) {
                 const unsigned v = ok ? (unsigned)(((pix2 + iy * a.W + ix) * C2 + (cb - a.Csplit) + q8 * 4) * 4) : kOOB;
@@ -117,12 +108,7 @@ void conv_g64_kernel(ConvArgs a) {
             } else if (xb16) {                                       // bf16 storage: the quad is 8 bytes, the two 32-channel halves 64 bytes apart; widened exactly
                 const unsigned v = ok ? (unsigned)(((pix0 + iy * a.W + ix) * a.Csplit + cb + q8 * 4) * 2) : kOOB;
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const F2 p = TSNET_BUF_LOAD8(rsx, v, (unsigned)(h * 64));
-                    const unsigned w0 = __builtin_bit_cast(unsigned, p.v[0]), w1 = __builtin_bit_cast(unsigned, p.v[1]);
-                    ar[s][h].v[0] = __builtin_bit_cast(float, w0 << 16); ar[s][h].v[1] = __builtin_bit_cast(float, w0 & 0xFFFF0000u);
-                    ar[s][h].v[2] = __builtin_bit_cast(float, w1 << 16); ar[s][h].v[3] = __builtin_bit_cast(float, w1 & 0xFFFF0000u);
-                }
+                for (int h = 0; h < 2; ++h) bf16x4_widen(TSNET_BUF_LOAD8(rsx, v, (unsigned)(h * 64)), ar[s][h]);
             } else {
                 const unsigned v = ok ? (unsigned)(((pix0 + iy * a.W + ix) * a.Csplit + cb + q8 * 4) * 4) : kOOB;
                 ar[s][0] = TSNET_BUF_LOAD16(rsx, v, 0u); ar[s][1] = TSNET_BUF_LOAD16(rsx, v, 128u);
@@ -145,19 +131,7 @@ void conv_g64_kernel(ConvArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaxf(ar[s][h].v[e] * in_scale, relu_floor);
                 }
-                unsigned char* dst = base + lds_w[s] + h * 2 * GP;
-                if (ONEP) {
-                    uint2 w;
-                    w.x = cvt_pk_one<F16P>(t[0], t[1]); w.y = cvt_pk_one<F16P>(t[2], t[3]);
-                    *reinterpret_cast<uint2*>(dst) = w;
-                } else {
-                    unsigned h0, l0, h1, l1;
-                    TSNET_SPLIT_2PAIRS(t[0], t[1], t[2], t[3], h0, l0, h1, l1);
-                    uint2 hw2, lw2;
-                    hw2.x = h0; hw2.y = h1; lw2.x = l0; lw2.y = l1;
-                    *reinterpret_cast<uint2*>(dst) = hw2;
-                    *reinterpret_cast<uint2*>(dst + PLANE) = lw2;
-                }
+                store_operand_quad<ONEP, F16P>(t, base + lds_w[s] + h * 2 * GP, PLANE);
             }
         }
     };
@@ -184,15 +158,7 @@ void conv_g64_kernel(ConvArgs a) {
         for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; tot[i][r] = 0.f; }
     auto product = [&](int g, int pa, int pb, bool fresh) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            f32x16 c = acc[i];
-            if (fresh) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) c[r] = 0.f;
-            }
-            if (NPROD == 1) acc[i] = TSNET_MFMA_BF16(af[pa][i], bf[g][pb], c);
-            else acc[i] = TSNET_MFMA_F16(af[pa][i], bf[g][pb], c);
-        }
+        for (int i = 0; i < MT; ++i) acc[i] = conv_mfma<NPROD>(af[pa][i], bf[g][pb], acc[i], fresh);
     };
 
     // ---- prologue: A(0) into stage 0, A(1) in registers, B(0) in the four sets
@@ -227,7 +193,7 @@ void conv_g64_kernel(ConvArgs a) {
         for (int i = 0; i < MT; ++i) tot[i] += acc[i];              // (a vector add: v_pk_add_f32, as in conv_h2r -- the element-wise form is 15 - 60 instructions longer per step here and spills in the bf16 form)
     }
 
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;
+    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;      // (not conv_unscale: sharing changes the code of 24 kernels)
     f32x16 out[MT][NTL];
 #pragma unroll
     for (int i = 0; i < MT; ++i)
@@ -235,8 +201,7 @@ void conv_g64_kernel(ConvArgs a) {
         for (int r = 0; r < 16; ++r) out[i][0][r] = tot[i][r] * unscale;
     const int m_img = img * hw;
     __syncthreads();                                                 // the stages are free: the epilogue reduces through them
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, out, smem_raw, tid, wave, n0, (size_t)tile_m,
-                                                 [&](int l) { return r0 + l < hw ? m_img + r0 + l : -1; });
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, out, smem_raw, tid, wave, n0, (size_t)rt.tile_m, [&](int l) { return row_out_index(rt, m_img, l); });
 }
 
 }  // namespace tsnet

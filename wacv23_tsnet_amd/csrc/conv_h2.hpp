@@ -2,6 +2,8 @@
 //   h2_tile   3x3 / stride 1 / pad 1 (ResnetBlocks, FuseNet, decoder up-convolutions: 83 % of the FLOPs; TSNet.py:27,42,147)
 //   h2s_tile  7x7 stems at 8 input channels (TSNet.py:66 with label_nc = 2)
 //   h2d_tile  3x3 / stride 2 / zero pad 1 downsampling (TSNet.py:70)
+// The steps they share with each other and with the other convolution kernels -- padding, operand scale, the MFMA of a chain, the staging
+// store's tail, the tile decode -- are conv_common.hpp's ("the steps every tile function repeats").
 // fp32 input, the producer's InstanceNorm + ReLU applied while the patch is staged, fp16 x 2 operands / three MFMA products (or one bf16
 // plane / one product), fp32 accumulate in two levels, fp64 statistics in the epilogue (conv_common.hpp).
 //
@@ -95,17 +97,16 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
     const int wn0 = (wave % WARPS_N) * WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    const int tcols = a.Wo / kPatchCols, tper = (a.Ho / PR) * tcols;
-    const int img = tile_m / tper, tin = tile_m - img * tper;
-    const int oy0 = (tin / tcols) * PR, ox0 = (tin % tcols) * kPatchCols;
+    const PatchTile pt = patch_tile<PR>(a, tile_m);
+    const int img = pt.img, oy0 = pt.oy0, ox0 = pt.ox0;
     const int ncc = a.Cin >> 4;
-    float in_scale = a.in_scale, in_unscale = a.in_unscale;
-    if (NPROD != 1 && a.in_amax) h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
+    float in_scale, in_unscale;
+    conv_operand_scale<NPROD>(a, img, in_scale, in_unscale);
 
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
     const bool xb16 = NPROD == 1 && a.x_bf16;                        // bf16 storage: the input tensor holds bf16 (conv_common.hpp load_x_octet)
     const tsnet_brsrc_t rsx = tsnet_make_brsrc(a.x, (unsigned)((size_t)a.N * (UP2 ? (a.H >> 1) * (a.W >> 1) : a.H * a.W) * a.Cin * (xb16 ? 2 : 4)));
-    tsnet_brsrc_t rsw[NPL];
+    tsnet_brsrc_t rsw[NPL];                                          // (not shared: in the earlier trial, sharing the weight-plane descriptors changed the code of 37 - 42 kernels of this unit)
 #pragma unroll
     for (int p = 0; p < NPL; ++p) rsw[p] = tsnet_make_brsrc(a.w + p * planew, (unsigned)(planew * 2));
 
@@ -120,14 +121,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         const int pr = pp / PC, pc = pp - pr * PC;
         int iy = oy0 - 1 + pr, ix = ox0 - 1 + pc;
         bool ok = pp < PP;
-        if (a.reflect) {
-            iy = iy < 0 ? -iy : iy;
-            iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-            ix = ix < 0 ? -ix : ix;
-            ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
-        } else {
-            ok = ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        }
+        TSNET_RESOLVE_PAD(a, iy, ix, ok);
         const int pix = iy * a.W + ix;
         vP[r] = ok ? (unsigned)(((img * a.H * a.W + pix) * a.Cin + oct * 8) * 4) : kOOB;
         vM[r] = ok ? 1.f : 0.f;
@@ -155,8 +149,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         int idx = tid & 127;
         idx = idx < 3 * PC ? idx : idx - 64;
         const int j = idx / PC, pc = idx - j * PC;
-        auto refl = [](int i, int n) { i = i < 0 ? -i : i; return i >= n ? 2 * (n - 1) - i : i; };
-        const int ix = refl(ox0 - 1 + pc, a.W), iyA = refl(oy0 - 1 + 2 * j, a.H), iyB = refl(oy0 + 2 * j, a.H);
+        const int ix = reflect_index(ox0 - 1 + pc, a.W), iyA = reflect_index(oy0 - 1 + 2 * j, a.H), iyB = reflect_index(oy0 + 2 * j, a.H);
         int x0, x1, r0, r1, a0, a1;
         float w0;
         up2_source(ix, a.W >> 1, x0, x1, w0, uWx);
@@ -168,7 +161,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         uDst = octU * REGION + (2 * j * PC + pc) * 16;
     }
     float* tab = reinterpret_cast<float*>(smem_raw + OFF_TAB);       // [Cin] alpha*s, then [Cin] beta*s
-    if (AFFINE) {
+    if (AFFINE) {                                                    // (not shared: in the earlier trial, sharing the table fill changed the code of 56 kernels of this unit)
         const float ts = UP2 ? 1.f : in_scale;
         for (int c = tid; c < a.Cin; c += 256 * KG) {
             tab[c] = a.in_alpha[(size_t)img * a.Cin + c] * ts;
@@ -195,15 +188,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         transform_octet<AFFINE, ZPAD_KEEP>(sx[r], ta, a.Cin, in_scale, relu_floor, vM[r], t);
         // a block past the patch does not exist: its wave writes into the sink (wave-uniform select, no branch)
         unsigned char* dst = gbase + (b < PBLK ? par * PATCH_BYTES + oct * REGION + b * 512 : OFF_SINK + oct * 512) + (lane & 31) * 16;
-        F4 Hh, Ll;
-        if (ONEP) {
-            one_plane_octet<F16P>(t[0], t[1], Hh);
-            *reinterpret_cast<F4*>(dst) = Hh;
-        } else {
-            split_h2_octet(t[0], t[1], Hh, Ll);
-            *reinterpret_cast<F4*>(dst) = Hh;
-            *reinterpret_cast<F4*>(dst + (b < PBLK ? PLANE_P : 1024)) = Ll;
-        }
+        store_operand_octet<ONEP, F16P>(t, dst, b < PBLK ? PLANE_P : 1024);
     };
 
     // UP2 stage 1: the lane's low-res octet of slab cn -> registers; IN + ReLU, fp32 -> low-res buffer lb
@@ -283,7 +268,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         for (int p = 0; p < NPL; ++p) ar[DB ? (kx & 1) : 0][r][p] = *reinterpret_cast<const F4*>(pbase + p * PLANE_P + (r * PC + kx) * 16);
     };
 
-    f32x16 acc[MT][NTL], tot[MT][NTL];
+    f32x16 acc[MT][NTL], tot[MT][NTL];                               // (not shared: in the earlier trial, sharing the init changed the code of 75 kernels of this unit, the un-scale loop below 21)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -295,15 +280,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < NTL; ++j) {
-                f32x16 c = acc[i][j];
-                if (fresh) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) c[r] = 0.f;
-                }
-                if (NPROD == 1) acc[i][j] = TSNET_MFMA_BF16(ar[DB ? (kx & 1) : 0][i + ky][pa], bf[sb][pb][j], c);
-                else acc[i][j] = TSNET_MFMA_F16(ar[DB ? (kx & 1) : 0][i + ky][pa], bf[sb][pb][j], c);
-            }
+            for (int j = 0; j < NTL; ++j) acc[i][j] = conv_mfma<NPROD>(ar[DB ? (kx & 1) : 0][i + ky][pa], bf[sb][pb][j], acc[i][j], fresh);
     };
     // step s of local slab cc (stage par): B(cc, s) sits in set s % BD, the rows of its tap column in ar; issues first B of BD - 1 steps ahead
     // and the patch row(s) the NEXT step needs: row ky + MT of this column (ky < 2); rows 0 .. MT-2 of the next column at ky = 1 (their last
@@ -441,7 +418,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
         }
     }
 
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;
+    const float unscale = conv_unscale(a.w_unscale, in_unscale);
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -449,7 +426,7 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
 #pragma unroll
             for (int r = 0; r < 16; ++r) tot[i][j][r] *= unscale;    // exact: power of two
     const int m_img = img * a.Ho * a.Wo;
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * tper + tin,
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,      // (not patch_out_index, here and in h2s / h2d: sharing changes the code of 71 kernels)
                                                  [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); }, kg == 0);
 }
 
@@ -508,11 +485,10 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
     const int wn0 = (wave % WARPS_N) * 32;
     const int li = lane & 31, lh = lane >> 5;
 
-    const int tcols = a.Wo / kPatchCols, tper = (a.Ho / kPatchRows) * tcols;
-    const int img = tile_m / tper, tin = tile_m - img * tper;
-    const int oy0 = (tin / tcols) * kPatchRows, ox0 = (tin % tcols) * kPatchCols;
-    float in_scale = a.in_scale, in_unscale = a.in_unscale;
-    if (NPROD != 1 && a.in_amax) h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
+    const PatchTile pt = patch_tile<kPatchRows>(a, tile_m);
+    const int img = pt.img, oy0 = pt.oy0, ox0 = pt.ox0;
+    float in_scale, in_unscale;
+    conv_operand_scale<NPROD>(a, img, in_scale, in_unscale);
 
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
     const tsnet_brsrc_t rsx = tsnet_make_brsrc(a.x, (unsigned)((size_t)a.N * a.H * a.W * 8 * 4));
@@ -535,17 +511,13 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
     for (int r = 0; r < 2; ++r) {
         const int pp = tid + r * 256;
         const int pr = pp / PC, pc = pp - pr * PC;
-        int iy = oy0 - 3 + pr, ix = ox0 - 3 + pc;
-        iy = iy < 0 ? -iy : iy;
-        iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-        ix = ix < 0 ? -ix : ix;
-        ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
+        const int iy = reflect_index(oy0 - 3 + pr, a.H), ix = reflect_index(ox0 - 3 + pc, a.W);
         const unsigned v = pp < PP ? (unsigned)((((img * a.H + iy) * a.W) + ix) * 32) : kOOB;
         F4 x0 = TSNET_BUF_LOAD16(rsx, v, 0u), x1 = TSNET_BUF_LOAD16(rsx, v, 16u);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { x0.v[e] *= in_scale; x1.v[e] *= in_scale; }
         if (pp < 384) {                                               // slots 380..383 hold zeros (never read, kept finite)
-            F4 Hh, Ll;
+            F4 Hh, Ll;                                                // (not store_operand_octet: sharing changes the code of 2 kernels)
             if (ONEP) {
                 one_plane_octet<F16P>(x0, x1, Hh);
                 *reinterpret_cast<F4*>(smem_raw + pp * 16) = Hh;
@@ -589,15 +561,7 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
         for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; tot[i][0][r] = 0.f; }
     auto product = [&](int sa, int sb, int pa, int pb, bool fresh) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            f32x16 c = acc[i];
-            if (fresh) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) c[r] = 0.f;
-            }
-            if (NPROD == 1) acc[i] = TSNET_MFMA_BF16(af[sa][pa][i], bf[sb][pb], c);
-            else acc[i] = TSNET_MFMA_F16(af[sa][pa][i], bf[sb][pb], c);
-        }
+        for (int i = 0; i < MT; ++i) acc[i] = conv_mfma<NPROD>(af[sa][pa][i], bf[sb][pb], acc[i], fresh);
     };
     // step st = 6 c + j: A(st) in set j & 1, B(st) in set j % 3 (six steps per chain keep both rotations static); issues A(st + 1), B(st + 2) first
     auto step = [&](int st, int j) __attribute__((always_inline)) {
@@ -626,14 +590,14 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
     step(24, 0);
     fold();
 
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;
+    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;      // (not conv_unscale: sharing changes the code of 3 kernels)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) tot[i][0][r] *= unscale;                     // exact: power of two
     const int m_img = img * a.Ho * a.Wo;
     __syncthreads();                                                  // the epilogue reuses the patch region for its reduction
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * tper + tin,
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,
                                                  [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); });
 }
 
@@ -701,12 +665,11 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
     const int wn0 = (wave % WARPS_N) * WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    const int tcols = a.Wo / kPatchCols, tper = (a.Ho / PR) * tcols;
-    const int img = tile_m / tper, tin = tile_m - img * tper;
-    const int oy0 = (tin / tcols) * PR, ox0 = (tin % tcols) * kPatchCols;
+    const PatchTile pt = patch_tile<PR>(a, tile_m);
+    const int img = pt.img, oy0 = pt.oy0, ox0 = pt.ox0;
     const int ncc = a.Cin >> 4;
-    float in_scale = a.in_scale, in_unscale = a.in_unscale;
-    if (NPROD != 1 && a.in_amax) h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
+    float in_scale, in_unscale;
+    conv_operand_scale<NPROD>(a, img, in_scale, in_unscale);
 
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
     const bool xb16 = NPROD == 1 && a.x_bf16;                        // bf16 storage: the input tensor holds bf16
@@ -759,15 +722,7 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
         const int so = slot_of(r);
         const bool real = so >= 0;
         unsigned char* dst = smem_raw + (real ? (cn & 1) * PATCH_BYTES + oct * REGION + so : OFF_SINK + (lane & 63) * 16);
-        F4 Hh, Ll;
-        if (ONEP) {
-            one_plane_octet<F16P>(t[0], t[1], Hh);
-            *reinterpret_cast<F4*>(dst) = Hh;
-        } else {
-            split_h2_octet(t[0], t[1], Hh, Ll);
-            *reinterpret_cast<F4*>(dst) = Hh;
-            *reinterpret_cast<F4*>(dst + (real ? PLANE_P : 1024)) = Ll;
-        }
+        store_operand_octet<ONEP, F16P>(t, dst, real ? PLANE_P : 1024);
     };
 
     // ---- fragments
@@ -804,15 +759,7 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < NTL; ++j) {
-                f32x16 c = acc[i][j];
-                if (fresh) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) c[r] = 0.f;
-                }
-                if (NPROD == 1) acc[i][j] = TSNET_MFMA_BF16(af[sa][pa][i], bf[sb][pb][j], c);
-                else acc[i][j] = TSNET_MFMA_F16(af[sa][pa][i], bf[sb][pb][j], c);
-            }
+            for (int j = 0; j < NTL; ++j) acc[i][j] = conv_mfma<NPROD>(af[sa][pa][i], bf[sb][pb][j], acc[i][j], fresh);
     };
     // staging of slab cc + 1 over the nine taps of slab cc, one round in flight at a time:
     //   five rounds: load at taps 0 1 3 4 6, store at taps 1 3 4 6 8;   three rounds: load at taps 0 3 6, store at taps 2 5 8
@@ -881,7 +828,7 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
     for (; cc + 2 <= ncc; cc += 2) { slab(cc, 0); slab(cc + 1, 1); }
     if (cc < ncc) slab(cc, 0);
 
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;
+    const float unscale = conv_unscale(a.w_unscale, in_unscale);
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -890,7 +837,7 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
             for (int r = 0; r < 16; ++r) tot[i][j][r] *= unscale;
     const int m_img = img * a.Ho * a.Wo;
     __syncthreads();                                                 // the epilogue reuses the patch region
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * tper + tin,
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,
                                                  [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); });
 }
 

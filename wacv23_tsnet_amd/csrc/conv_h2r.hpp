@@ -11,6 +11,7 @@
 // sets: the loop is unrolled by four, so parities are static), one barrier per step, chains of four k-groups folded into the running
 // total.  K order is tap-major (k = tap * Cin + c).  An M tile is 128 output positions of ONE image (images whose size is not a multiple
 // of 128 get a ragged last tile): the transform table and the data-derived operand scale are per image.
+// Padding, operand scale, the MFMA of a chain, the staging store's tail and the row-tile decode are spelled once in conv_common.hpp.
 #pragma once
 #include "conv_common.hpp"
 
@@ -38,14 +39,10 @@ void conv_h2r_kernel(ConvArgs a) {
     const int wm0 = (wave / WARPS_N) * WM, wn0 = (wave % WARPS_N) * WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    const int bid = xcd_item(blockIdx.x, a.tiles_m * a.tiles_n);
-    const int tile_m = bid / a.tiles_n, tile_n = bid - tile_m * a.tiles_n;
-    const int n0 = tile_n * BN;
-    const int hw = a.Ho * a.Wo;
-    const int img = tile_m / a.tpi;
-    const int r0 = (tile_m - img * a.tpi) * BM;                      // first position of the tile inside its image
-    float in_scale = a.in_scale, in_unscale = a.in_unscale;
-    if (NPROD != 1 && a.in_amax) h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
+    const RowTile rt = row_tile<BM, BN>(a, blockIdx.x);
+    const int n0 = rt.n0, hw = rt.hw, img = rt.img, r0 = rt.r0;      // r0: first position of the tile inside its image
+    float in_scale, in_unscale;
+    conv_operand_scale<NPROD>(a, img, in_scale, in_unscale);
 
     const int C2 = a.Cin - a.Csplit;
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
@@ -94,14 +91,7 @@ void conv_h2r_kernel(ConvArgs a) {
         const int ky = tap / KS, kx = tap - ky * KS;
         int iy = s_oy + ky, ix = s_ox + kx;
         bool ok = s_valid && tap < a.taps;
-        if (a.reflect) {
-            iy = iy < 0 ? -iy : iy;
-            iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-            ix = ix < 0 ? -ix : ix;
-            ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
-        } else {
-            ok = ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        }
+        TSNET_RESOLVE_PAD(a, iy, ix, ok);
         const bool second = !SMALL_CIN && c0 >= a.Csplit;             // torch.cat on the channel axis, formed on load
         const unsigned v1 = ok ? (unsigned)(((s_pix + iy * a.W + ix) * a.Csplit + c0) * 4) : kOOB;
         const unsigned v2 = ok ? (unsigned)(((s_pix2 + iy * a.W + ix) * C2 + (c0 - a.Csplit)) * 4) : kOOB;
@@ -116,15 +106,7 @@ void conv_h2r_kernel(ConvArgs a) {
         F4 t[2];
         transform_octet<AFFINE>(ar[set], tab + ac0[set], a.Cin, in_scale, relu_floor, am[set], t);
         unsigned char* dst = smem_raw + stage * STAGE + tid * 16;
-        F4 Hh, Ll;
-        if (ONEP) {
-            one_plane_octet<F16P>(t[0], t[1], Hh);
-            *reinterpret_cast<F4*>(dst) = Hh;
-        } else {
-            split_h2_octet(t[0], t[1], Hh, Ll);
-            *reinterpret_cast<F4*>(dst) = Hh;
-            *reinterpret_cast<F4*>(dst + PLANE_A) = Ll;
-        }
+        store_operand_octet<ONEP, F16P>(t, dst, PLANE_A);
     };
 
     // ---- fragments
@@ -155,15 +137,7 @@ void conv_h2r_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < NTL; ++j) {
-                f32x16 c = acc[i][j];
-                if (fresh) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) c[r] = 0.f;
-                }
-                if (NPROD == 1) acc[i][j] = TSNET_MFMA_BF16(af[pa][i], bf[sb][pb][j], c);
-                else acc[i][j] = TSNET_MFMA_F16(af[pa][i], bf[sb][pb][j], c);
-            }
+            for (int j = 0; j < NTL; ++j) acc[i][j] = conv_mfma<NPROD>(af[pa][i], bf[sb][pb][j], acc[i][j], fresh);
     };
 
     // step kc (u = kc mod 4, static): A(kc) in LDS stage u&1, A(kc+1) in register set (u+1)&1, B(kc) in bf[u&1]
@@ -205,7 +179,7 @@ void conv_h2r_kernel(ConvArgs a) {
             for (int j = 0; j < NTL; ++j) tot[i][j] += acc[i][j];
     }
 
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;
+    const float unscale = conv_unscale(a.w_unscale, in_unscale);
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -213,8 +187,7 @@ void conv_h2r_kernel(ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) tot[i][j][r] *= unscale;
     const int m_img = img * hw;
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)tile_m,
-                                                 [&](int l) { return r0 + l < hw ? m_img + r0 + l : -1; });
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)rt.tile_m, [&](int l) { return row_out_index(rt, m_img, l); });
 }
 
 constexpr int h2r_lds_bytes(int Cin) { return 2 * 2 * 128 * 32 + 64 + 2 * Cin * 4; }

@@ -12,6 +12,7 @@
 //   * K order and chains are conv_h2r's (k = tap * 32 + c; chains of four k-groups from k = 0, a last partial chain of two): THE SAME BITS as
 //     the general kernel on the same layer (tests: torch.equal), so the layer's kernel could change without touching a tolerance.
 // A tile = 4 x 32 output pixels x 64 channels, four waves 2 x 2, wave tile 64 x 32; 49 KiB of LDS: three workgroups per CU.
+// Reflection, operand scale, the MFMA of a chain, the staging store's tail (quad form) and the patch-tile decode are conv_common.hpp's.
 #pragma once
 #include "conv_common.hpp"
 
@@ -43,11 +44,10 @@ void conv_h2s32_kernel(ConvArgs a) {
     const int bid = xcd_item(blockIdx.x, a.tiles_m * a.tiles_n);
     const int tile_m = bid / a.tiles_n;
     const int n0 = (bid - tile_m * a.tiles_n) * BN;
-    const int tcols = a.Wo / kPatchCols, tper = (a.Ho / kPatchRows) * tcols;
-    const int img = tile_m / tper, tin = tile_m - img * tper;
-    const int oy0 = (tin / tcols) * kPatchRows, ox0 = (tin % tcols) * kPatchCols;
-    float in_scale = a.in_scale, in_unscale = a.in_unscale;
-    if (NPROD != 1 && a.in_amax) h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
+    const PatchTile pt = patch_tile<kPatchRows>(a, tile_m);
+    const int img = pt.img, oy0 = pt.oy0, ox0 = pt.ox0;
+    float in_scale, in_unscale;
+    conv_operand_scale<NPROD>(a, img, in_scale, in_unscale);
 
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
     const tsnet_brsrc_t rsx = tsnet_make_brsrc(a.x, (unsigned)((size_t)a.N * a.H * a.W * 32 * 4));
@@ -73,11 +73,7 @@ void conv_h2s32_kernel(ConvArgs a) {
         for (int r = 0; r < ROUNDS; ++r) {
             const int idx = tid + r * 256, pp = idx >> 3, q8 = idx & 7;
             const int pr = pp / PC, pc = pp - pr * PC;
-            int iy = oy0 - 3 + pr, ix = ox0 - 3 + pc;
-            iy = iy < 0 ? -iy : iy;
-            iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-            ix = ix < 0 ? -ix : ix;
-            ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
+            const int iy = reflect_index(oy0 - 3 + pr, a.H), ix = reflect_index(ox0 - 3 + pc, a.W);
             const unsigned v = pp < PP ? (unsigned)((((img * a.H + iy) * a.W) + ix) * 128 + q8 * 16) : kOOB;
             x[r] = TSNET_BUF_LOAD16(rsx, v, 0u);
         }
@@ -89,18 +85,7 @@ void conv_h2s32_kernel(ConvArgs a) {
             float t[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) t[e] = x[r].v[e] * in_scale;
-            if (ONEP) {
-                uint2 w;
-                w.x = cvt_pk_one<F16P>(t[0], t[1]); w.y = cvt_pk_one<F16P>(t[2], t[3]);
-                *reinterpret_cast<uint2*>(dst) = w;
-            } else {
-                unsigned h0, l0, h1, l1;
-                TSNET_SPLIT_2PAIRS(t[0], t[1], t[2], t[3], h0, l0, h1, l1);
-                uint2 hw2, lw2;
-                hw2.x = h0; hw2.y = h1; lw2.x = l0; lw2.y = l1;
-                *reinterpret_cast<uint2*>(dst) = hw2;
-                *reinterpret_cast<uint2*>(dst + PLANE) = lw2;
-            }
+            store_operand_quad<ONEP, F16P>(t, dst, PLANE);
         }
     }
     __syncthreads();
@@ -128,15 +113,7 @@ void conv_h2s32_kernel(ConvArgs a) {
         for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; tot[i][0][r] = 0.f; }
     auto product = [&](int sa, int sb, int pa, int pb, bool fresh) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            f32x16 c = acc[i];
-            if (fresh) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) c[r] = 0.f;
-            }
-            if (NPROD == 1) acc[i] = TSNET_MFMA_BF16(af[sa][pa][i], bf[sb][pb], c);
-            else acc[i] = TSNET_MFMA_F16(af[sa][pa][i], bf[sb][pb], c);
-        }
+        for (int i = 0; i < MT; ++i) acc[i] = conv_mfma<NPROD>(af[sa][pa][i], bf[sb][pb], acc[i], fresh);
     };
     // step s = 4 c + j (tap 2 c + (j >> 1), group j & 1): A(s) in set j & 1, B(s) in set j; issues A(s + 1) and B(s + 3) first
     auto step = [&](int c, int j) __attribute__((always_inline)) {
@@ -166,14 +143,14 @@ void conv_h2s32_kernel(ConvArgs a) {
     step(24, 0); step(24, 1);                                                     // tap 48 (their look-ahead reads tap 48 again and zeros past K)
     fold();
 
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;
+    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;      // (not conv_unscale, nor patch_out_index below: either changes the code of 3 kernels)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) tot[i][0][r] *= unscale;                     // exact: power of two
     const int m_img = img * a.Ho * a.Wo;
     __syncthreads();                                                              // the epilogue reuses the patch region for its reduction
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * tper + tin,
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,
                                                  [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); });
 }
 

@@ -35,6 +35,7 @@
 //   * <= 128 VGPRs (two SIMDs carry four of the fourteen waves; tests/test_isa.py), 154 - 158 KiB of LDS.
 // Bits: the item shape moves no arithmetic -- tests/test_emu_w1_pair_lanes.py holds the kernel to the record of the half-row items, value for value.
 // How it got here, form by form with measurements: DESIGN.md section 4.4.
+// Reflection, operand scale, the MFMA of a chain, the patch-tile decode and the epilogue's row map are spelled once in conv_common.hpp.
 #pragma once
 #include <type_traits>
 
@@ -108,25 +109,24 @@ constexpr int kW1Pix = 6;                                                       
 // goes into the load's scalar offset) apart.  Three offsets per item instead of six: the producers hold two tiles' worth across the epilogue.
 struct W1ItemOffs { unsigned first, mid, last; };                                 // pixel 0 | pixel 1 (pixels 2..4: + the pixel pitch each) | pixel 5; kOOB = zeros
 
+// the operand scale of a tile's image: |V| <= 2 max|x|, so a device-derived scale leaves one bit of head-room more than the direct form's
+template <int NPROD>
+__device__ __forceinline__ void w1_operand_scale(const ConvArgs& a, const int img, float& in_scale, float& in_unscale) {
+    conv_operand_scale<NPROD>(a, img, in_scale, in_unscale);
+    if (NPROD != 1 && a.in_amax) { in_scale *= 0.5f; in_unscale *= 2.0f; }
+}
+
 __device__ __forceinline__ void w1_item_offsets(const ConvArgs& a, const int img, const int oy0, const int ox0, const int prow, const int g, const int quad,
                                                 const bool real, W1ItemOffs& o) {
-    int iy = oy0 - 1 + prow;
+    int iy = oy0 - 1 + prow;                                         // (the row once per item, the column per pixel: the halves of TSNET_RESOLVE_PAD apart)
     bool rok = real;
-    if (a.reflect) {
-        iy = iy < 0 ? -iy : iy;
-        iy = iy >= a.H ? 2 * (a.H - 1) - iy : iy;
-    } else {
-        rok = rok && iy >= 0 && iy < a.H;
-    }
+    if (a.reflect) iy = reflect_index(iy, a.H);
+    else rok = rok && iy >= 0 && iy < a.H;
     auto at = [&](int q) __attribute__((always_inline)) {
         int ix = ox0 - 1 + 4 * g + q;
         bool ok = rok;
-        if (a.reflect) {
-            ix = ix < 0 ? -ix : ix;
-            ix = ix >= a.W ? 2 * (a.W - 1) - ix : ix;
-        } else {
-            ok = ok && ix >= 0 && ix < a.W;
-        }
+        if (a.reflect) ix = reflect_index(ix, a.W);
+        else ok = ok && ix >= 0 && ix < a.W;
         return ok ? (unsigned)(((img * a.H * a.W + iy * a.W + ix) * a.Cin + quad * 4) * 4) : kOOB;
     };
     o.first = at(0); o.mid = at(1); o.last = at(kW1Pix - 1);
@@ -220,16 +220,7 @@ template <int NPROD, int NPL>
 __device__ __forceinline__ void w1_step_products(f32x16 (&acc)[2], const F4 (&a0)[NPL], const F4 (&a1)[NPL], const F4 (&bw)[NPL], const bool fresh) {
     auto product = [&](int pa, int pb, bool fr) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            f32x16 c = acc[i];
-            if (fr) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) c[r] = 0.f;
-            }
-            const F4& A = i ? a1[pa] : a0[pa];
-            if (NPROD == 1) acc[i] = TSNET_MFMA_BF16(A, bw[pb], c);
-            else acc[i] = TSNET_MFMA_F16(A, bw[pb], c);
-        }
+        for (int i = 0; i < 2; ++i) acc[i] = conv_mfma<NPROD>(i ? a1[pa] : a0[pa], bw[pb], acc[i], fr);
     };
     if (NPROD == 1) {
         product(0, 0, fresh);
@@ -320,14 +311,10 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
             tile_m = (a.xcd_gn > 0 ? xcd / gn : xcd) * tm + (loc / tn) * nrun + j;
             tile_n = (a.xcd_gn > 0 ? xcd % gn : 0) * tn + loc % tn;
         }
-        t.img = tile_m / tper; t.tin = tile_m - t.img * tper;
-        t.oy0 = (t.tin / tcols) * kPatchRows; t.ox0 = (t.tin % tcols) * kPatchCols;
+        const PatchTile pt = patch_tile<kPatchRows>(a, tile_m);
+        t.img = pt.img; t.tin = pt.tin; t.oy0 = pt.oy0; t.ox0 = pt.ox0;
         t.n0 = tile_n * 64;
-        t.in_scale = a.in_scale; t.in_unscale = a.in_unscale;
-        if (NPROD != 1 && a.in_amax) {                               // |V| <= 2 max|x|: one bit of head-room more than the direct form
-            h2_device_scale(a.in_amax + t.img, a.in_bound_add, t.in_scale, t.in_unscale);
-            t.in_scale *= 0.5f; t.in_unscale *= 2.0f;
-        }
+        w1_operand_scale<NPROD>(a, t.img, t.in_scale, t.in_unscale);
         return t;
     };
     W1Tile T = tile_at(0);
@@ -376,7 +363,7 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
     // ---- the epilogue of one tile (every wave runs it: the producers keep the barriers company).  `two_pass`: the tile has a successor in
     // the chunk, whose V(0) and V(1) sit in the other two stages -- only the stage at st_free may be used
     auto epilogue = [&](const W1Tile& t, const int st_free, const bool two_pass) __attribute__((always_inline)) {
-        const float unscale = a.w_unscale ? t.in_unscale * a.w_unscale[0] : t.in_unscale;
+        const float unscale = conv_unscale(a.w_unscale, t.in_unscale);
         __syncthreads();                                             // every read of the tile's last stage has been issued
         // the epilogue sits inside the tile loop: its lane-derived addresses are computed here, per tile, not hoisted across the K loop
         int tid_e = tid;
@@ -416,7 +403,7 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
         }
         const int m_img = t.img * a.Ho * a.Wo;
         conv_epilogue<64, 4, 2, 1, 1, 8>(a, out, ebase, tid_e, consumer ? wave : nt, t.n0, (size_t)t.img * tper + t.tin,
-                                      [&](int l) { return m_img + (t.oy0 + (l >> 5)) * a.Wo + t.ox0 + (l & 31); }, consumer);
+                                         [&](int l) { return patch_out_index(a, m_img, t.oy0, t.ox0, l); }, consumer);
     };
 
     if (wave >= 8) {

@@ -33,16 +33,12 @@ __device__ __forceinline__ void w1_tile_one(const ConvArgs& a, unsigned char* sm
     const int wn0 = nt * 32;
     const int li = lane & 31, lh = lane >> 5;
 
-    const int tcols = a.Wo / kPatchCols, tper = (a.Ho / kPatchRows) * tcols;
-    const int img = tile_m / tper, tin = tile_m - img * tper;
-    const int oy0 = (tin / tcols) * kPatchRows, ox0 = (tin % tcols) * kPatchCols;
+    const PatchTile pt = patch_tile<kPatchRows>(a, tile_m);
+    const int img = pt.img, oy0 = pt.oy0, ox0 = pt.ox0;
     const int ncc = a.Cin >> 4;
     const int npp = (ncc + 1) >> 1;                                  // periods of two 16-channel slabs (an odd count: the last slab is all zeros)
-    float in_scale = a.in_scale, in_unscale = a.in_unscale;
-    if (NPROD != 1 && a.in_amax) {                                   // |V| <= 2 max|x|: one bit of head-room more than the direct form
-        h2_device_scale(a.in_amax + img, a.in_bound_add, in_scale, in_unscale);
-        in_scale *= 0.5f; in_unscale *= 2.0f;
-    }
+    float in_scale, in_unscale;
+    w1_operand_scale<NPROD>(a, img, in_scale, in_unscale);
 
     const size_t planew = (size_t)((a.nchunks + 1) / 2 * 2) * a.Npad * 16;
     const tsnet_brsrc_t rsx = tsnet_make_brsrc(a.x, (unsigned)((size_t)a.N * a.H * a.W * a.Cin * 4));
@@ -181,7 +177,7 @@ __device__ __forceinline__ void w1_tile_one(const ConvArgs& a, unsigned char* sm
     }
 
     // ---- output transform: the four positions of a pair meet through LDS
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;
+    const float unscale = conv_unscale(a.w_unscale, in_unscale);
     __syncthreads();                                                 // every stage has been read
     float* ex = reinterpret_cast<float*>(smem_raw);                  // [position][pair 64][channel 64]
     const bool consumer = wave < 8;
@@ -200,8 +196,7 @@ __device__ __forceinline__ void w1_tile_one(const ConvArgs& a, unsigned char* sm
     w1_output_transform(ex + (size_t)(mq * 16) * 64 + wn0 + li, 64 * 64, lh, out[0][0]);
     __syncthreads();                                                 // the shared epilogue reuses the region for its reductions
     const int m_img = img * a.Ho * a.Wo;
-    conv_epilogue<64, 4, 2, 1, 1>(a, out, smem_raw, tid, consumer ? wave : nt, n0, (size_t)img * tper + tin,
-                                  [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); }, consumer);
+    conv_epilogue<64, 4, 2, 1, 1>(a, out, smem_raw, tid, consumer ? wave : nt, n0, (size_t)img * pt.tper + pt.tin, [&](int l) { return patch_out_index(a, m_img, oy0, ox0, l); }, consumer);
 }
 
 template <int NPROD, bool AFFINE, int OPT = 0>
