@@ -22,7 +22,8 @@
  * tsnet_face_labels_boxes, tsnet_face_labels_boxes_u8 -- the face labels of a clip with a crop per frame, frames of different sizes in one pass;
  * tsnet_op_upconv2d -- the decoder's up-convolution as one operator; tsnet_op_conv2d_epi -- a convolution with its epilogue's statistics, addend,
  * published maximum, device-derived operand scale and bf16 storage, as the forward calls it; tsnet_op_patch_warp, tsnet_op_train_tail -- the
- * launches of tsnet_train_extras on the caller's tensors.
+ * launches of tsnet_train_extras on the caller's tensors; tsnet_gaussian_box_params, tsnet_blur_mask -- feathered paste masks; tsnet_yuv_coeffs,
+ * tsnet_rgb_to_yuv420, tsnet_yuv420_to_rgb -- frames in and out as YUV 4:2:0.
  */
 #ifndef TSNET_ABI_H
 #define TSNET_ABI_H
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8), tsnet_op_upconv2d, tsnet_op_conv2d_epi, tsnet_op_patch_warp, tsnet_op_train_tail; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
+#define TSNET_ABI_VERSION 5      /* 5: tsnet_op_warp_k (round 6); added since, version unchanged: tsnet_face_adapt_stats, tsnet_face_adapt_apply, tsnet_smooth_keypoints, the source bank (tsnet_bank_*, tsnet_forward_bank, tsnet_op_*_slots), compact inputs (tsnet_*_u8), tsnet_op_upconv2d, tsnet_op_conv2d_epi, tsnet_op_patch_warp, tsnet_op_train_tail, tsnet_gaussian_box_params, tsnet_blur_mask, tsnet_yuv_coeffs, tsnet_rgb_to_yuv420, tsnet_yuv420_to_rgb; 4: tsnet_cfg.operand_mode = 2 (bf16 storage); tsnet_op_conv2d kernel = 3 (Winograd-along-x form); tsnet_op_flow_k, tsnet_flow_plan */
 #define TSNET_MAX_SOURCES 8
 
 enum {
@@ -641,6 +642,42 @@ int tsnet_face_labels_boxes_u8(const double* keypoints, const double* curves, in
 int tsnet_gaussian_box_params(float radius, int passes, int* box_radius, unsigned* ww, unsigned* fw);
 int tsnet_blur_mask(const unsigned char* in, int F, int H, int W, const int* rect, float radius_x, float radius_y, int flags,
                     unsigned char* out, unsigned char* tmp, void* stream);
+
+/* Video in and out as YUV 4:2:0 (csrc/yuv_frames.hpp): packed RGB bytes <-> planar 8-bit Y'CbCr with the chroma planes at half size in both
+ * directions, 1.5 bytes per pixel.  The contract is INTEGER arithmetic; tests/yuv_cases.py restates it in numpy and the tests hold equality.
+ * A conversion is fixed by a standard -- 601: BT.601, Kr = 0.299, Kb = 0.114; 709: BT.709, Kr = 0.2126, Kb = 0.0722; Kg = 1 - Kr - Kb -- and
+ * a range: full (JFIF, ITU-T T.871): sy = sc = 1, Y offset 0; limited: sy = 219/255, sc = 224/255, Y offset 16.  The chroma offset is 128.
+ *
+ * tsnet_yuv_coeffs: HOST only, computed in double.  The rows of the real matrix are Y = sy (Kr, Kg, Kb), Cb = sc (-Kr, -Kg, 1 - Kb) /
+ * (2 (1 - Kb)), Cr = sc (1 - Kr, -Kg, -Kb) / (2 (1 - Kr)); every entry times 65536, rounded to nearest; then the GREEN entry of each row is
+ * corrected so that the Y row sums to round(65536 sy) and the chroma rows to 0: a grey pixel has chroma exactly 128.
+ *   fwd[12]: the rows Y, Cb, Cr as {cR, cG, cB, offset}.
+ *   inv[6]:  {iy, rv, gu, gv, bu, oy}: iy = round(65536 / sy), rv = round(65536 * 2 (1 - Kr) / sc), bu = round(65536 * 2 (1 - Kb) / sc),
+ *            gu = -round(65536 Kb 2 (1 - Kb) / (Kg sc)), gv = -round(65536 Kr 2 (1 - Kr) / (Kg sc)), oy = the Y offset.
+ * (601 full: Y row 19595, 38470, 7471 -- libjpeg's.)  TSNET_ERR_ARG: a standard other than 601 or 709, a NULL table.
+ *
+ * Layouts.  A frame of h x w pixels is h w + 2 ch cw bytes with ch = (h + 1) / 2, cw = (w + 1) / 2; frames are contiguous (no stride, no pitch).
+ *   0 = I420: the Y plane, then the Cb plane, then the Cr plane (a Y4M frame's payload);
+ *   1 = NV12: the Y plane, then ch rows of cw interleaved (Cb, Cr) pairs (hardware encoders and decoders).
+ *
+ * tsnet_rgb_to_yuv420: rgb (F,h,w,3) DEVICE bytes -> yuv, F frames, DEVICE; fwd: 12 HOST ints.
+ *   Y[y][x] = clamp((cR R + cG G + cB B + (off << 16) + 32768) >> 16, 0, 255) with the Y row;
+ *   the chroma sample (j, i) covers the n = 4, 2 or 1 pixels of the 2 x 2 block at (2j, 2i) that lie inside the frame; with S the sum over them of
+ *   cR R + cG G + cB B (that plane's row): C = clamp((S (4 / n) + (off << 18) + (1 << 17)) >> 18, 0, 255) -- one rounding of the block's mean
+ *   chroma, centred (JPEG) siting.  >> is arithmetic.
+ * tsnet_yuv420_to_rgb: the inverse; inv: 6 HOST ints.  The chroma of pixel (y, x) is the sample at (y >> 1, x >> 1), replicated; with
+ *   t = (Y - oy) iy, u = Cb - 128, v = Cr - 128:  R = clamp((t + rv v + 32768) >> 16), G = clamp((t + gu u + gv v + 32768) >> 16),
+ *   B = clamp((t + bu u + 32768) >> 16).
+ * Each is ONE kernel on `stream` for all F frames: no allocation, no memset, no synchronisation.  A lane moves a block of 8 x 2 pixels with 8- or
+ * 4-byte accesses where the block is whole and its rows are aligned, byte by byte on ragged edges and unaligned rows; the bytes are the same.
+ * TSNET_ERR_ARG (message in tsnet_op_last_error starting with the entry's name less "tsnet_"; every refusal comes before the launch, nothing is
+ * written): a NULL tensor or table; F, h or w < 1; F over 65535 (kYuvMaxFrames, the grid); a frame over 2^31 - 1 RGB bytes (h w 3, the 32-bit
+ * index inside a frame); a layout other than 0 or 1; yuv == rgb (overlaps beyond the first byte are not checked); a forward table with a row
+ * whose sum of |c| is over 1 << 17 (kYuvRowSumMax) or an inverse table with an entry over 1 << 21 in size (kYuvInvCoefMax) -- beyond them the
+ * sums may overflow 32 bits; a table offset outside 0 .. 255. */
+int tsnet_yuv_coeffs(int standard, int full_range, int* fwd, int* inv);
+int tsnet_rgb_to_yuv420(const unsigned char* rgb, int F, int h, int w, const int* fwd, int layout, unsigned char* yuv, void* stream);
+int tsnet_yuv420_to_rgb(const unsigned char* yuv, int F, int h, int w, const int* inv, int layout, unsigned char* rgb, void* stream);
 
 #ifdef __cplusplus
 }

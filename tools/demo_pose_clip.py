@@ -94,6 +94,9 @@ def main():
                     "GaussianBlur(R) on the device (FrameLoader.feather_mask)")
     ap.add_argument("--feather-from", choices=("box", "bbox"), default=None, help="with --feather: box (default) = the feathered crop box, one mask "
                     "for the clip; bbox = every driving frame's own bounding-box mask, feathered")
+    ap.add_argument("--y4m", default=None, metavar="OUT.y4m", help="also write the clip as a Y4M video file (uncompressed YUV 4:2:0, BT.601 full "
+                    "range; ffmpeg -i OUT.y4m out.mp4 takes it): the full frames with --paste-back, the generated frames without; converted on the "
+                    "device (FrameLoader.to_yuv420) and downloaded at half the bytes of RGB")
     args = ap.parse_args()
     if (args.feather is not None or args.feather_from is not None) and not args.paste_back:
         ap.error("--feather and --feather-from need --paste-back")
@@ -149,7 +152,9 @@ def main():
     if args.feather is not None:
         paste.update(paste_feather=args.feather, paste_feather_from=args.feather_from or "box")
         print(f"[demo_pose_clip] --feather {args.feather} from {paste['paste_feather_from']}")
-    frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_pose", **paste)
+    frames = runner.run(lbl[K:], box[K:], out_dir=args.out, name=args.clip or "synthetic_pose", y4m=args.y4m, **paste)
+    if args.y4m:
+        print(f"[demo_pose_clip] --y4m: {frames.shape[0]} frames of {frames.shape[2]} x {frames.shape[1]} written to {args.y4m}")
     print(f"[demo_pose_clip] {frames.shape[0]} {'full ' if args.paste_back else ''}frames written to {args.out} (crop {tuple(crop)}, classes present {present}); "
           f"labels of {F + K} frames from the key points: {t_raster * 1e3:.2f} ms")
 

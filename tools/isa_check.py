@@ -148,10 +148,13 @@ def main():
             flag = "   <-- spills in the loop of a hot kernel"; bad += 1
         print(f"{r['name']:62s} vgpr={r['vgpr']:3d} loop: mfma={r['mfma']:3d} instr={r['total']:4d} scratch={r['scratch']:2d} "
               f"longest mfma run={r['mfma_run_max']:2d} longest other run={r['other_run_max']:3d}{flag}")
-    # the feathered-mask kernels (csrc/mask_blur.hpp, in engine.cpp's unit): no MFMA loop to look into; whole-kernel registers and scratch
+    # the feathered-mask kernels (csrc/mask_blur.hpp) and the YUV 4:2:0 conversions (csrc/yuv_frames.hpp), in engine.cpp's unit: no MFMA loop to
+    # look into; whole-kernel registers and scratch
     pat = args[0] if args else ""
-    if not pat or pat in "mask_blur_rows_kernel mask_blur_cols_kernel":
-        for name, (vgpr, scratch) in sorted(kernel_resources(compile_asm("--tools" in sys.argv, "engine.cpp"), "mask_blur").items()):
+    for names, part in (("mask_blur_rows_kernel mask_blur_cols_kernel", "mask_blur"), ("rgb_to_yuv420_kernel yuv420_to_rgb_kernel", "yuv420")):
+        if pat and pat not in names:
+            continue
+        for name, (vgpr, scratch) in sorted(kernel_resources(compile_asm("--tools" in sys.argv, "engine.cpp"), part).items()):
             flag = ""
             if scratch:
                 flag = "   <-- uses scratch"; bad += 1

@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "tsnet_op_upconv2d", "tsnet_op_conv2d_epi",
     "tsnet_op_patch_warp", "tsnet_op_train_tail",
     "tsnet_gaussian_box_params", "tsnet_blur_mask",
+    "tsnet_yuv_coeffs", "tsnet_rgb_to_yuv420", "tsnet_yuv420_to_rgb",
 )
 
 
@@ -176,6 +177,9 @@ def bind(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "tsnet_blur_mask"):          # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
         lib.tsnet_gaussian_box_params.argtypes = [C.c_float, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
         lib.tsnet_blur_mask.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]
+    if hasattr(lib, "tsnet_rgb_to_yuv420"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
+        lib.tsnet_yuv_coeffs.argtypes = [C.c_int, C.c_int, _vp, _vp]
+        lib.tsnet_rgb_to_yuv420.argtypes = lib.tsnet_yuv420_to_rgb.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]
     return lib
 
 

@@ -1,7 +1,7 @@
 // clip_entries.hpp -- the C entry points of the clip side (include/tsnet_abi.h): what a video clip needs around the forward, none of it touching
 // tsnet_engine, Ctx or a convolution -- frame statistics and post-processing (postproc.hpp), the host curve fits and key-point preparation
-// (lmfit.hpp, face_adapt.hpp), rasterisation and label resizing (raster.hpp), the frame loader (frames.hpp), the paste (paste.hpp), its feathered masks (mask_blur.hpp) and the labels
-// of a clip with a crop per frame (track_labels.hpp).  engine.cpp includes this file once, last, after its own entries and op_entries.hpp: it is part of that translation
+// (lmfit.hpp, face_adapt.hpp), rasterisation and label resizing (raster.hpp), the frame loader (frames.hpp), the paste (paste.hpp), its feathered masks (mask_blur.hpp),
+// the colour conversion to and from YUV 4:2:0 (yuv_frames.hpp) and the labels of a clip with a crop per frame (track_labels.hpp).  engine.cpp includes this file once, last, after its own entries and op_entries.hpp: it is part of that translation
 // unit and of no other.  HOST code.
 #pragma once
 #ifndef TSNET_ENGINE_CPP
@@ -24,6 +24,7 @@
 #include "postproc.hpp"
 #include "raster.hpp"
 #include "track_labels.hpp"
+#include "yuv_frames.hpp"
 
 using namespace tsnet;
 
@@ -482,6 +483,61 @@ int tsnet_blur_mask(const unsigned char* in, int F, int H, int W, const int* rec
         hipLaunchKernelGGL(mask_blur_cols_kernel, grid_cols, dim3(256), 0, s, a);
         check_launch("mask_blur_cols");
     }
+    OP_END
+}
+
+// ---- video in and out as YUV 4:2:0 (yuv_frames.hpp): integer colour conversion on 16-bit fixed-point tables, I420 or NV12
+int tsnet_yuv_coeffs(int standard, int full_range, int* fwd, int* inv) {
+    OP_BEGIN
+    if (!fwd || !inv) throw ArgError("yuv_coeffs: null table");
+    if (!yuv_tables(standard, full_range != 0, fwd, inv)) throw ArgError("yuv_coeffs: unknown standard " + std::to_string(standard) + " (601 = BT.601, 709 = BT.709)");
+    OP_END
+}
+
+// what the two conversions check alike; the table is checked by the caller.  Returns the launch's arguments but for the table.
+static YuvArgs yuv_checked_args(const std::string& who, const void* src, void* dst, const int* table, int F, int h, int w, int layout) {
+    if (!src || !dst) throw ArgError(who + ": null tensor");
+    if (!table) throw ArgError(who + ": null table");
+    if (F < 1 || h < 1 || w < 1) throw ArgError(who + ": bad shape");
+    if (F > kYuvMaxFrames) throw ArgError(who + ": " + std::to_string(F) + " frames, over kYuvMaxFrames = " + std::to_string(kYuvMaxFrames) + " (the grid's second dimension)");
+    if ((long long)h * w * 3 > 2147483647LL)
+        throw ArgError(who + ": a frame of " + std::to_string(h) + " x " + std::to_string(w) + " (h x w) is over 2^31 - 1 RGB bytes, the 32-bit index inside a frame");
+    if (layout != 0 && layout != 1) throw ArgError(who + ": unknown layout " + std::to_string(layout) + " (0 = I420, 1 = NV12)");
+    if (src == dst) throw ArgError(who + ": yuv and rgb must not be the same buffer");
+    YuvArgs a{};
+    a.src = (const unsigned char*)src; a.dst = (unsigned char*)dst;
+    a.h = h; a.w = w; a.ch = (h + 1) / 2; a.cw = (w + 1) / 2;
+    a.nbx = (w + kYuvBlockW - 1) / kYuvBlockW;
+    a.nv12 = layout;
+    return a;
+}
+
+static dim3 yuv_grid(const YuvArgs& a, int F) { return dim3((unsigned)(((long long)a.nbx * a.ch + 255) / 256), (unsigned)F); }
+
+int tsnet_rgb_to_yuv420(const unsigned char* rgb, int F, int h, int w, const int* fwd, int layout, unsigned char* yuv, void* stream) {
+    OP_BEGIN
+    YuvArgs a = yuv_checked_args("rgb_to_yuv420", rgb, yuv, fwd, F, h, w, layout);
+    for (int r = 0; r < 3; ++r) {
+        if (!yuv_fwd_row_fits(fwd + 4 * r))
+            throw ArgError("rgb_to_yuv420: table row " + std::to_string(r) + " has a sum of |c| over kYuvRowSumMax = " + std::to_string(kYuvRowSumMax) + ": the sums would overflow 32 bits");
+        if (fwd[4 * r + 3] < 0 || fwd[4 * r + 3] > 255) throw ArgError("rgb_to_yuv420: table offset " + std::to_string(fwd[4 * r + 3]) + " outside 0 .. 255");
+    }
+    for (int i = 0; i < 12; ++i) a.c[i] = fwd[i];
+    hipLaunchKernelGGL(rgb_to_yuv420_kernel, yuv_grid(a, F), dim3(256), 0, (hipStream_t)stream, a);
+    check_launch("rgb_to_yuv420");
+    OP_END
+}
+
+int tsnet_yuv420_to_rgb(const unsigned char* yuv, int F, int h, int w, const int* inv, int layout, unsigned char* rgb, void* stream) {
+    OP_BEGIN
+    YuvArgs a = yuv_checked_args("yuv420_to_rgb", yuv, rgb, inv, F, h, w, layout);
+    for (int i = 0; i < 5; ++i)
+        if (!yuv_inv_coef_fits(inv[i]))
+            throw ArgError("yuv420_to_rgb: table entry " + std::to_string(i) + " is over kYuvInvCoefMax = " + std::to_string(kYuvInvCoefMax) + " in size: the sums would overflow 32 bits");
+    if (inv[5] < 0 || inv[5] > 255) throw ArgError("yuv420_to_rgb: table offset " + std::to_string(inv[5]) + " outside 0 .. 255");
+    for (int i = 0; i < 6; ++i) a.c[i] = inv[i];
+    hipLaunchKernelGGL(yuv420_to_rgb_kernel, yuv_grid(a, F), dim3(256), 0, (hipStream_t)stream, a);
+    check_launch("yuv420_to_rgb");
     OP_END
 }
 

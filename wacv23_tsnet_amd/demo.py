@@ -249,7 +249,8 @@ class ClipRunner:
         return self.frames(tar_lbl, tar_bbox)[0]
 
     def run(self, tar_lbls: torch.Tensor, tar_bboxs: torch.Tensor, out_dir: str = None, tar_imgs: torch.Tensor = None, name: str = "clip",
-            paste_into=None, paste_box=None, paste_src_box=None, paste_mask=None, paste_boxes=None, paste_feather=None, paste_feather_from="box"):
+            paste_into=None, paste_box=None, paste_src_box=None, paste_mask=None, paste_boxes=None, paste_feather=None, paste_feather_from="box",
+            y4m=None, y4m_standard="bt601", y4m_full_range=True):
         """tar_lbls (F,L,H,W), tar_bboxs (F,H,W); returns the generated frames (F,H,W,3) uint8 (host).  With out_dir: strips + GIF.
         paste_into: (F,h,w,3) uint8 video frames, tensor or array -- every group's bytes are resized to paste_box = (x0, y0, x1, y1) (the crop box
         the clip was loaded with; it may leave the frame) and pasted into its frames on the device (`FrameLoader.paste`: Pillow's resize + paste,
@@ -261,10 +262,19 @@ class ClipRunner:
         paste_feather: a radius (or (rx, ry)) for a soft seam (`FrameLoader.feather_mask`: Pillow's GaussianBlur of the mask, byte for byte), None =
         the hard seam.  paste_feather_from="box": the feathered indicator of paste_src_box shrunk by `feather_inset`, made once per run and reused
         for every group; "bbox": every group's tar_bboxs rows (float32 or compact) become that group's mask -- the feathered face region, another
-        for every frame.  With paste_mask the given mask is blurred instead (once, before the first group)."""
+        for every frame.  With paste_mask the given mask is blurred instead (once, before the first group).
+        y4m: a `video.Y4MWriter` (left open) or a path (opened and closed here, size taken from the frames, 25 frames/s) -- every group's
+        output frames, the pasted full frames with paste_into and the generated frames without, are converted on the device
+        (`FrameLoader.to_yuv420`, y4m_standard, y4m_full_range), downloaded as I420, half the bytes of RGB, and appended to the file.  With y4m
+        and no out_dir no RGB byte is downloaded and `run` returns the number of frames written; with both, everything above is as without y4m."""
         import os
         n = tar_lbls.shape[0]
         full = None
+        if y4m is not None:
+            from .frames import FrameLoader
+            from .video import Y4MWriter
+            yld = FrameLoader(self.src_img[0].device, lib=self.eng.lib)
+            writer, written = (y4m if isinstance(y4m, Y4MWriter) else None), 0
         if paste_feather_from not in ("box", "bbox"):
             raise ValueError(f"paste_feather_from must be 'box' or 'bbox', not {paste_feather_from!r}")
         if paste_feather is not None and paste_into is None:
@@ -291,21 +301,33 @@ class ClipRunner:
             if paste_feather is not None and paste_mask is not None:
                 paste_mask = ld._paste_mask(paste_mask, paste_feather, None, None)
         groups, box_mask = [], None
-        for i in range(0, n, self.batch):
-            g = self.frames(tar_lbls[i:i + self.batch], tar_bboxs[i:i + self.batch])
-            if full is not None:
-                mask = None if paste_mask is None else paste_mask[i:i + self.batch]
-                if paste_feather is not None and paste_mask is None:
-                    if paste_feather_from == "bbox":                # 0 / 1 rows in either form: every non-zero byte counts as 255
-                        tb = tar_bboxs[i:i + self.batch].to(dev)
-                        mask = ld.feather_mask(tb if tb.dtype == torch.uint8 else (tb != 0).to(torch.uint8), paste_feather, binary=True)
-                    else:
-                        if box_mask is None:                        # one mask for the run: the first group is the largest
-                            box_mask = ld._paste_mask(None, paste_feather, tuple(g.shape[:3]), paste_src_box)
-                        mask = box_mask[:g.shape[0]]
-                ld.paste(g, full[i:i + self.batch], paste_box if paste_boxes is None else paste_boxes[i:i + self.batch], src_box=paste_src_box,
-                         mask=mask, inplace=True)
-            groups.append(g)
+        try:
+            for i in range(0, n, self.batch):
+                g = self.frames(tar_lbls[i:i + self.batch], tar_bboxs[i:i + self.batch])
+                if full is not None:
+                    mask = None if paste_mask is None else paste_mask[i:i + self.batch]
+                    if paste_feather is not None and paste_mask is None:
+                        if paste_feather_from == "bbox":                # 0 / 1 rows in either form: every non-zero byte counts as 255
+                            tb = tar_bboxs[i:i + self.batch].to(dev)
+                            mask = ld.feather_mask(tb if tb.dtype == torch.uint8 else (tb != 0).to(torch.uint8), paste_feather, binary=True)
+                        else:
+                            if box_mask is None:                        # one mask for the run: the first group is the largest
+                                box_mask = ld._paste_mask(None, paste_feather, tuple(g.shape[:3]), paste_src_box)
+                            mask = box_mask[:g.shape[0]]
+                    ld.paste(g, full[i:i + self.batch], paste_box if paste_boxes is None else paste_boxes[i:i + self.batch], src_box=paste_src_box,
+                             mask=mask, inplace=True)
+                if y4m is not None:
+                    o = g if full is None else full[i:i + self.batch]
+                    if writer is None:
+                        writer = Y4MWriter(y4m, o.shape[2], o.shape[1], full_range=y4m_full_range)
+                    written += writer.write(yld.to_yuv420(o, "i420", y4m_standard, y4m_full_range).cpu())
+                if y4m is None or out_dir:
+                    groups.append(g)
+        finally:
+            if y4m is not None and writer is not None and writer is not y4m:     # opened here from a path
+                writer.close()
+        if y4m is not None and not out_dir:
+            return written
         out = torch.cat(groups).cpu().numpy()
         if out_dir:
             os.makedirs(out_dir, exist_ok=True)

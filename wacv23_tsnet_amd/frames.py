@@ -12,6 +12,10 @@ pastes them into the full frames (csrc/paste.hpp, `tsnet_paste_frames`) -- Pillo
 for byte (tests/test_paste_frames.py).  `FrameLoader.feather_mask` makes the mask of a soft seam (csrc/mask_blur.hpp, `tsnet_blur_mask`): Pillow's
 `Image.filter(ImageFilter.GaussianBlur(r))` on "L" images, byte for byte (tests/test_feather_mask.py); `paste(..., feather=r)` uses it.
 
+Both ends can cross PCIe as YUV 4:2:0, 1.5 bytes per pixel instead of 3, in the form encoders and decoders speak: `FrameLoader.to_yuv420` /
+`from_yuv420` (csrc/yuv_frames.hpp, `tsnet_rgb_to_yuv420` / `tsnet_yuv420_to_rgb`; I420 or NV12, BT.601 or BT.709, full or limited range) --
+integer arithmetic on the tables of `tsnet_yuv_coeffs`, held to equality with a numpy restatement (tests/test_yuv_frames.py).
+
 Decoding PNG / JPEG files stays with PIL on the host; the training loaders' random crop / scale / flip are out of scope."""
 from __future__ import annotations
 
@@ -400,6 +404,101 @@ class FrameLoader:
             raise ValueError(f"expected generated frames of {S} x {S} (img_size {tuple(img_size)} padded square), got {gw} x {gh}")
         px, py = (S - int(img_size[0])) // 2, (S - int(img_size[1])) // 2
         return self.paste(gen, frames, crop, src_box=(px, py, px + int(img_size[0]), py + int(img_size[1])), mask=mask, inplace=inplace, feather=feather)
+
+
+    # ------------------------------------------------------------------------------------------------------------------ YUV 4:2:0 in and out
+    def yuv_tables(self, standard: str = "bt601", full_range: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """(fwd int32[12], inv int32[6]) of `tsnet_yuv_coeffs`, cached per (standard, range)"""
+        key = (str(standard).lower(), bool(full_range))
+        cache = self.__dict__.setdefault("_yuv_tables", {})
+        if key not in cache:
+            if key[0] not in YUV_STANDARDS:
+                raise ValueError(f"standard must be one of {sorted(YUV_STANDARDS)}, not {standard!r}")
+            fwd, inv = np.zeros(12, np.int32), np.zeros(6, np.int32)
+            if self.lib.tsnet_yuv_coeffs(YUV_STANDARDS[key[0]], int(key[1]), fwd.ctypes.data, inv.ctypes.data) != 0:
+                raise RuntimeError(f"tsnet_yuv_coeffs failed: {self.lib.tsnet_op_last_error().decode()}")
+            cache[key] = (fwd, inv)
+        return cache[key]
+
+    def _yuv_out(self, out, shape) -> torch.Tensor:
+        if out is None:
+            return torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device.type != self.device.type \
+                or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(shape)} on {self.device}")
+        return out
+
+    def to_yuv420(self, frames, layout: str = "i420", standard: str = "bt601", full_range: bool = True, out=None) -> torch.Tensor:
+        """(F,h,w,3) uint8 RGB, tensor or array (uploaded when on the host) -> (F, h*w + 2*ch*cw) uint8 on the device, ch = (h+1)//2,
+        cw = (w+1)//2 (`tsnet_rgb_to_yuv420`, csrc/yuv_frames.hpp): 8-bit Y'CbCr 4:2:0, half the bytes of the RGB frames.  layout "i420": the Y
+        plane, then Cb, then Cr -- a Y4M frame's payload (`video.Y4MWriter`); "nv12": the Y plane, then rows of interleaved (Cb, Cr) pairs.
+        standard "bt601" / "bt709", full_range True (JFIF) / False (16 .. 235 / 240): the integer tables of `tsnet_yuv_coeffs`; one chroma sample
+        is one rounding of the mean over its 2 x 2 block (centred siting), odd sizes included.  out: the tensor to write, else a new one.
+        On device tensors the call enqueues one kernel on the current stream: no allocation in the library, no synchronisation."""
+        fr = self._u8(frames, "frames", 4).to(self.device).contiguous()
+        F, h, w, _ = fr.shape
+        fwd, _ = self.yuv_tables(standard, full_range)
+        out = self._yuv_out(out, (F, yuv_frame_bytes(h, w)))
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        with ctx:
+            rc = self.lib.tsnet_rgb_to_yuv420(fr.data_ptr(), F, h, w, fwd.ctypes.data, _yuv_layout(layout), out.data_ptr(), self._stream())
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"tsnet_rgb_to_yuv420 failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep_yuv = [fr]                                        # alive until the stream has consumed it
+        return out
+
+    def from_yuv420(self, yuv, size: Tuple[int, int], layout: str = "i420", standard: str = "bt601", full_range: bool = True, out=None) -> torch.Tensor:
+        """The inverse (`tsnet_yuv420_to_rgb`): (F, h*w + 2*ch*cw) uint8 frames as a decoder or `video.Y4MReader` hands them out, size = (h, w)
+        -> (F,h,w,3) uint8 RGB on the device, the chroma samples replicated over their 2 x 2 blocks.  rgb -> yuv -> rgb is not the identity:
+        on constant 2 x 2 blocks it comes back within 1 per byte with the full-range tables and within 2 with the limited ones."""
+        h, w = (int(v) for v in size)
+        if isinstance(yuv, np.ndarray):
+            yuv = torch.from_numpy(np.ascontiguousarray(yuv))
+        if not isinstance(yuv, torch.Tensor) or yuv.dtype != torch.uint8 or yuv.dim() != 2 or h < 1 or w < 1 or yuv.shape[1] != yuv_frame_bytes(h, w):
+            raise ValueError(f"expected uint8 frames of shape (F, {yuv_frame_bytes(max(h, 1), max(w, 1))}) for size {(h, w)}, got "
+                             f"{tuple(getattr(yuv, 'shape', ()))} {getattr(yuv, 'dtype', type(yuv))}")
+        src = yuv.to(self.device).contiguous()
+        F = src.shape[0]
+        _, inv = self.yuv_tables(standard, full_range)
+        out = self._yuv_out(out, (F, h, w, 3))
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
+        with ctx:
+            rc = self.lib.tsnet_yuv420_to_rgb(src.data_ptr(), F, h, w, inv.ctypes.data, _yuv_layout(layout), out.data_ptr(), self._stream())
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"tsnet_yuv420_to_rgb failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        self._keep_yuv = [src]                                       # alive until the stream has consumed it
+        return out
+
+    yuv_planes = staticmethod(lambda buf, h, w, layout="i420": yuv_planes(buf, h, w, layout))
+
+
+YUV_STANDARDS = {"bt601": 601, "bt709": 709}
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+
+
+def _yuv_layout(layout) -> int:
+    if str(layout).lower() not in YUV_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}, not {layout!r}")
+    return YUV_LAYOUTS[str(layout).lower()]
+
+
+def yuv_frame_bytes(h: int, w: int) -> int:
+    """bytes of one 4:2:0 frame of h x w pixels, either layout"""
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+def yuv_planes(buf, h: int, w: int, layout: str = "i420"):
+    """Views of the planes of (F, yuv_frame_bytes(h, w)) frames, tensor or array: (Y (F,h,w), Cb (F,ch,cw), Cr (F,ch,cw)); in "nv12" the two
+    chroma views are the strided halves of the interleaved plane."""
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    if buf.ndim != 2 or buf.shape[1] != yuv_frame_bytes(h, w):
+        raise ValueError(f"expected frames of shape (F, {yuv_frame_bytes(h, w)}) for size {(h, w)}, got {tuple(buf.shape)}")
+    F = buf.shape[0]
+    y = buf[:, :h * w].reshape(F, h, w)
+    if _yuv_layout(layout) == 0:
+        return y, buf[:, h * w:h * w + ch * cw].reshape(F, ch, cw), buf[:, h * w + ch * cw:].reshape(F, ch, cw)
+    uv = buf[:, h * w:].reshape(F, ch, cw, 2)
+    return y, uv[..., 0], uv[..., 1]
 
 
 class _Null:
