@@ -239,7 +239,7 @@ def test_feather_none_is_the_existing_call(emu_lib):
     mask = pc.make_mask("none", "bands", 2, 64, 64)
     assert np.array_equal(ld.paste(gen, fr, box, feather=None).numpy(), pc.expect_numpy(fr, gen, box))
     assert np.array_equal(ld.paste(gen, fr, box, mask=mask, feather=None).numpy(), pc.expect_numpy(fr, gen, box, None, mask))
-    assert not hasattr(ld, "_feather_tmp")                                 # nothing of the feather path ran
+    assert ld._feather_tmp is None and "feather_mask" not in ld._held      # nothing of the feather path ran
 
 
 def test_box_too_small_for_its_inset(emu_lib):

@@ -152,7 +152,7 @@ def test_pool_is_reused_and_grows(emu_lib):
     assert len(ld._pool_host) == n and ld._pool is pool and torch.equal(a, b)
     more = boxes.copy(); more[1] = (2, 3, 51, 57); more[3] = (1, 1, 80, 59)
     c = ld.prepare(fr, more, (32, 28), as_bytes=True)                # new sizes: the pool grows, the old one is kept for what may still read it
-    assert len(ld._pool_host) > n and ld._pool is not pool and any(k is pool for k in ld._keep)
+    assert len(ld._pool_host) > n and ld._pool is not pool and ld._held["prepare"]["old_pool"] is pool
     assert torch.equal(c, frames.FrameLoader("cpu", lib=emu_lib).prepare(fr, more, (32, 28), as_bytes=True))
     assert torch.equal(ld.prepare(fr, boxes, (32, 28), as_bytes=True), a)
     assert np.array_equal(c.numpy(), tc.expect_prepare_numpy(fr, [tuple(r) for r in more.tolist()], (32, 28), False))

@@ -124,7 +124,8 @@ def test_pool_and_workspace_are_reused_and_grow(emu_lib):
     assert rs._wpool is pool and rs._ws is ws and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     c = rs.clip_labels(list(kp[more]), size=size, crop=crops[more], relative=True, compact=True, bw=1)    # new sizes, a longer clip: both are replaced
     assert rs._wpool is not pool and rs._ws is not ws and len(rs._wpool_host) > n and rs._ws.numel() > ws.numel()
-    assert any(k is pool for k in rs._keep_t) and any(k is ws for k in rs._keep_t)                        # kept for what may still read them
+    held = rs._held["clip_labels"]
+    assert held["old_pool"] is pool and held["old_workspace"] is ws                                       # kept for what may still read them
     pool, ws = rs._wpool, rs._ws
     d = rs.clip_labels(list(kp[few]), size=size, crop=crops[few], relative=True, compact=True, bw=1)      # a smaller clip again: nothing shrinks
     assert rs._wpool is pool and rs._ws is ws and torch.equal(d[0], a[0]) and torch.equal(d[1], a[1])

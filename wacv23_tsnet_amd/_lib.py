@@ -21,30 +21,6 @@ MAX_SOURCES = 8
 TIMING_CLASSES = 9
 TIMING_NAMES = ("conv", "stats", "elementwise", "flow", "warp", "pack", "upsample", "other", "conv_res")
 
-# every symbol include/tsnet_abi.h declares (tests/test_abi.py checks header <-> library <-> this list)
-ABI_SYMBOLS = (
-    "tsnet_abi_version", "tsnet_create", "tsnet_load_weights", "tsnet_finalize", "tsnet_destroy",
-    "tsnet_last_error", "tsnet_num_params", "tsnet_param_info", "tsnet_packed_weights",
-    "tsnet_forward", "tsnet_set_source_divisors", "tsnet_set_sources", "tsnet_set_sources_shared", "tsnet_forward_target", "tsnet_train_extras", "tsnet_stage_ptr",
-    "tsnet_forward_macs", "tsnet_timing_enable", "tsnet_timing_read",
-    "tsnet_op_conv2d", "tsnet_op_conv2d_cat", "tsnet_op_head", "tsnet_op_instnorm_stats", "tsnet_op_norm_act", "tsnet_op_upsample2x",
-    "tsnet_op_flow", "tsnet_op_flow_k", "tsnet_flow_plan", "tsnet_op_warp", "tsnet_op_warp_k", "tsnet_op_warp_k_shared", "tsnet_op_add_stats", "tsnet_op_finalize_stats", "tsnet_op_fuse_tail", "tsnet_op_pack_input", "tsnet_op_upsample2x_st", "tsnet_op_last_error", "tsnet_frame_stats", "tsnet_demo_postprocess", "tsnet_fit_face_curves", "tsnet_raster_face", "tsnet_vl2ch", "tsnet_fit_pose_curves", "tsnet_raster_pose", "tsnet_label_bbox", "tsnet_resize_pad", "tsnet_resize_label", "tsnet_bench_conv", "tsnet_debug_counters", "tsnet_linspace", "tsnet_coord_table",
-    "tsnet_bicubic_taps", "tsnet_bicubic_table", "tsnet_prepare_frames",
-    "tsnet_face_adapt_stats", "tsnet_face_adapt_apply", "tsnet_smooth_keypoints",
-    "tsnet_bank_capacity", "tsnet_bank_put", "tsnet_forward_bank",
-    "tsnet_op_flow_k_slots", "tsnet_op_warp_k_slots", "tsnet_op_add_stats_slots", "tsnet_op_fuse_tail_slots",
-    "tsnet_forward_u8", "tsnet_set_sources_u8", "tsnet_forward_target_u8", "tsnet_bank_put_u8", "tsnet_forward_bank_u8",
-    "tsnet_op_pack_input_u8", "tsnet_prepare_frames_u8",
-    "tsnet_paste_frames",
-    "tsnet_prepare_frames_boxes", "tsnet_prepare_frames_boxes_u8", "tsnet_paste_frames_boxes",
-    "tsnet_face_labels_boxes", "tsnet_face_labels_boxes_u8",
-    "tsnet_op_upconv2d", "tsnet_op_conv2d_epi",
-    "tsnet_op_patch_warp", "tsnet_op_train_tail",
-    "tsnet_gaussian_box_params", "tsnet_blur_mask",
-    "tsnet_yuv_coeffs", "tsnet_rgb_to_yuv420", "tsnet_yuv420_to_rgb",
-)
-
-
 class TsnetCfg(C.Structure):
     """struct tsnet_cfg (include/tsnet_abi.h)."""
     _fields_ = [
@@ -68,118 +44,114 @@ class TsnetConvEpi(C.Structure):
     ]
 
 
+_i, _pp, _ip = C.c_int, C.POINTER(_vp), C.POINTER(C.c_int)
+_conv2d = [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, C.c_float, _i, _i, _i, _vp, _vp]
+_prepare = [_vp] + [_i] * 7 + [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i] + [_i] * 6        # frames, one box, two axis tables, output geometry
+_prepare_boxes = [_vp] + [_i] * 3 + [_vp, _vp, _vp, _i] + [_i] * 6                      # frames, descriptors + pool, output geometry
+_face_labels = [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, C.c_longlong, _i, _i, _vp, _vp, _vp]
+_yuv = [_vp, _i, _i, _i, _vp, _i, _vp, _vp]
+
+# Every symbol include/tsnet_abi.h declares (tests/test_abi.py checks header <-> library <-> this table): name -> argtypes, or
+# (argtypes, restype) where the entry does not return an int (restype None: void); argtypes None: the entry takes nothing.
+ABI = {
+    "tsnet_abi_version": None,
+    "tsnet_create": [C.POINTER(TsnetCfg), _pp],
+    "tsnet_load_weights": [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), _i],
+    "tsnet_finalize": [_vp, _vp],
+    "tsnet_destroy": ([_vp], None),
+    "tsnet_last_error": ([_vp], C.c_char_p),
+    "tsnet_num_params": [_vp],
+    "tsnet_param_info": [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _ip],
+    "tsnet_packed_weights": [_vp, _pp, C.POINTER(C.c_size_t)],
+    "tsnet_forward": [_vp, _pp, _pp, _pp, _vp, _vp, _vp, _vp, _i, _vp],
+    "tsnet_set_source_divisors": [_vp, _fp, _i],
+    "tsnet_set_sources": [_vp, _pp, _pp, _pp, _i, _vp],
+    "tsnet_set_sources_shared": [_vp, _pp, _pp, _pp, _vp],
+    "tsnet_forward_target": [_vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "tsnet_train_extras": [_vp, _pp, _vp, _i, _vp, _vp, _vp],
+    "tsnet_stage_ptr": [_vp, C.c_char_p, _pp, C.POINTER(C.c_size_t)],
+    "tsnet_forward_macs": ([_vp, _i], C.c_double),
+    "tsnet_timing_enable": [_vp, _i],
+    "tsnet_timing_read": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), _i],
+    "tsnet_op_conv2d": _conv2d,
+    "tsnet_op_conv2d_cat": [_vp, _vp] + [_i] * 6 + [_vp, _vp] + [_i] * 5 + [C.c_float, _i, _vp, _vp],
+    "tsnet_op_head": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _fp, _vp, _vp],
+    "tsnet_op_instnorm_stats": [_vp, _i, _i, _i, _vp, _vp, _vp],
+    "tsnet_op_norm_act": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp],
+    "tsnet_op_upsample2x": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "tsnet_op_flow": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "tsnet_op_flow_k": [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _i, _i, _fp, _vp],
+    "tsnet_flow_plan": [_i] * 4,
+    "tsnet_op_warp": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "tsnet_op_warp_k": [_vp, _vp] + [_i] * 5 + [_vp, _i, _fp, _vp],
+    "tsnet_op_warp_k_shared": [_vp, _vp] + [_i] * 6 + [_vp, _vp],
+    "tsnet_op_add_stats": [_vp, _vp] + [_i] * 5 + [_vp, _vp, _vp, _vp],
+    "tsnet_op_finalize_stats": [_vp] + [_i] * 4 + [_vp, _vp, _vp],
+    "tsnet_op_fuse_tail": [_vp] * 5 + [_i] * 5 + [_vp, _vp],
+    "tsnet_op_pack_input": [_pp, _pp] + [_i] * 8 + [_fp, _vp, _vp, _vp],
+    "tsnet_op_upsample2x_st": [_vp, _vp, _vp] + [_i] * 7 + [_vp, _vp],
+    "tsnet_op_last_error": (None, C.c_char_p),
+    "tsnet_frame_stats": [_vp, _i, _i, _i, C.c_float, _vp, _vp, _vp],
+    "tsnet_demo_postprocess": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _fp, _vp, _vp],
+    "tsnet_fit_face_curves": [_vp, _i, _vp],
+    "tsnet_raster_face": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "tsnet_vl2ch": [_vp, _i, _i, _i, _vp, _vp],
+    "tsnet_fit_pose_curves": [_vp, _i, _i, _vp],
+    "tsnet_raster_pose": [_vp, _vp] + [_i] * 8 + [_vp, _vp],
+    "tsnet_label_bbox": [_vp, _i, _i, _i, _vp, _vp],
+    "tsnet_resize_pad": [_vp, _i, _i, _i, _vp, _vp] + [_i] * 7 + [_vp, _vp],
+    "tsnet_resize_label": [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp],
+    "tsnet_bench_conv": [_i] * 12 + [_fp, _vp],
+    "tsnet_debug_counters": ([C.POINTER(C.c_int64), _i], None),
+    "tsnet_linspace": ([_i, _fp], None),
+    "tsnet_coord_table": ([_i, _i, _fp], None),
+    "tsnet_bicubic_taps": [_i, _i],
+    "tsnet_bicubic_table": [_i, _i, _vp, _vp, _vp],
+    "tsnet_prepare_frames": _prepare + [_fp, _vp, _vp],
+    "tsnet_face_adapt_stats": [_vp, _i, _vp],
+    "tsnet_face_adapt_apply": [_vp, _vp, _i],
+    "tsnet_smooth_keypoints": [_vp, _i, _i, _vp],
+    "tsnet_bank_capacity": [_vp],
+    "tsnet_bank_put": [_vp, _i, _i, _pp, _pp, _pp, _fp, _vp],
+    "tsnet_forward_bank": [_vp, _ip, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "tsnet_op_flow_k_slots": [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _i, _i, _fp, _ip, _i, _vp],
+    "tsnet_op_warp_k_slots": [_vp, _vp] + [_i] * 5 + [_vp, _ip, _i, _vp],
+    "tsnet_op_add_stats_slots": [_vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _ip, _i, _vp],
+    "tsnet_op_fuse_tail_slots": [_vp] * 5 + [_i] * 4 + [_vp, _ip, _i, _vp],
+    "tsnet_forward_u8": [_vp, _pp, _pp, _pp, _vp, _vp, _fp, _vp, _vp, _i, _vp],
+    "tsnet_set_sources_u8": [_vp, _pp, _pp, _pp, _fp, _i, _i, _vp],
+    "tsnet_forward_target_u8": [_vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "tsnet_bank_put_u8": [_vp, _i, _i, _pp, _pp, _pp, _fp, _fp, _vp],
+    "tsnet_forward_bank_u8": [_vp, _ip, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "tsnet_op_pack_input_u8": [_pp, _pp, _pp] + [_i] * 8 + [_fp, _fp, _vp, _vp, _vp, _vp],
+    "tsnet_prepare_frames_u8": _prepare + [_vp, _vp],
+    "tsnet_paste_frames": [_vp, _vp] + [_i] * 7 + [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i] + [_vp] + [_i] * 6 + [_vp],
+    "tsnet_prepare_frames_boxes": _prepare_boxes + [_fp, _vp, _vp],
+    "tsnet_prepare_frames_boxes_u8": _prepare_boxes + [_vp, _vp],
+    "tsnet_paste_frames_boxes": [_vp, _vp] + [_i] * 7 + [_vp, _vp, _vp, _i] + [_vp, _i, _i, _vp],
+    "tsnet_face_labels_boxes": _face_labels,
+    "tsnet_face_labels_boxes_u8": _face_labels,
+    "tsnet_op_upconv2d": _conv2d,
+    "tsnet_op_conv2d_epi": _conv2d[:-1] + [C.POINTER(TsnetConvEpi), _vp],
+    "tsnet_op_patch_warp": [_pp, _fp, _vp] + [_i] * 6 + [_vp, _vp],
+    "tsnet_op_train_tail": [_vp] * 4 + [_i] * 8 + [_fp] + [_vp] * 6,
+    "tsnet_gaussian_box_params": [C.c_float, _i, _ip, C.POINTER(C.c_uint), C.POINTER(C.c_uint)],
+    "tsnet_blur_mask": [_vp, _i, _i, _i, _vp, C.c_float, C.c_float, _i, _vp, _vp, _vp],
+    "tsnet_yuv_coeffs": [_i, _i, _vp, _vp],
+    "tsnet_rgb_to_yuv420": _yuv,
+    "tsnet_yuv420_to_rgb": _yuv,
+}
+ABI_SYMBOLS = tuple(ABI)
+
+
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Attach argtypes/restypes for every ABI entry point."""
-    lib.tsnet_abi_version.restype = C.c_int
-    lib.tsnet_create.argtypes = [C.POINTER(TsnetCfg), C.POINTER(_vp)]
-    lib.tsnet_load_weights.argtypes = [_vp, C.c_char_p, _vp, C.POINTER(C.c_int64), C.c_int]
-    lib.tsnet_finalize.argtypes = [_vp, _vp]
-    lib.tsnet_destroy.argtypes = [_vp]
-    lib.tsnet_destroy.restype = None
-    lib.tsnet_last_error.argtypes = [_vp]
-    lib.tsnet_last_error.restype = C.c_char_p
-    lib.tsnet_num_params.argtypes = [_vp]
-    lib.tsnet_param_info.argtypes = [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
-    lib.tsnet_packed_weights.argtypes = [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]
-    pp = C.POINTER(_vp)
-    lib.tsnet_forward.argtypes = [_vp, pp, pp, pp, _vp, _vp, _vp, _vp, C.c_int, _vp]
-    lib.tsnet_set_source_divisors.argtypes = [_vp, _fp, C.c_int]
-    lib.tsnet_set_sources.argtypes = [_vp, pp, pp, pp, C.c_int, _vp]
-    if hasattr(lib, "tsnet_set_sources_shared"):   # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_set_sources_shared.argtypes = [_vp, pp, pp, pp, _vp]
-    lib.tsnet_forward_target.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
-    lib.tsnet_train_extras.argtypes = [_vp, pp, _vp, C.c_int, _vp, _vp, _vp]
-    lib.tsnet_stage_ptr.argtypes = [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(C.c_size_t)]
-    lib.tsnet_forward_macs.argtypes = [_vp, C.c_int]
-    lib.tsnet_forward_macs.restype = C.c_double
-    lib.tsnet_timing_enable.argtypes = [_vp, C.c_int]
-    lib.tsnet_timing_read.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
-    lib.tsnet_op_conv2d.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _vp, _vp]
-    lib.tsnet_op_conv2d_cat.argtypes = [_vp, _vp] + [C.c_int] * 6 + [_vp, _vp] + [C.c_int] * 5 + [C.c_float, C.c_int, _vp, _vp]
-    lib.tsnet_op_head.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _fp, _vp, _vp]
-    lib.tsnet_op_instnorm_stats.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
-    lib.tsnet_op_norm_act.argtypes = [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]
-    lib.tsnet_op_upsample2x.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]
-    lib.tsnet_resize_label.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
-    lib.tsnet_op_flow.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]
-    lib.tsnet_op_flow_k.argtypes = [_vp, _vp, _vp, _vp] + [C.c_int] * 7 + [_vp, C.c_int, C.c_int, _fp, _vp]
-    lib.tsnet_flow_plan.argtypes = [C.c_int] * 4
-    lib.tsnet_op_warp.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]
-    if hasattr(lib, "tsnet_op_warp_k"):          # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_op_warp_k.argtypes = [_vp, _vp] + [C.c_int] * 5 + [_vp, C.c_int, _fp, _vp]
-    if hasattr(lib, "tsnet_op_fuse_tail"):       # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_op_warp_k_shared.argtypes = [_vp, _vp] + [C.c_int] * 6 + [_vp, _vp]
-        lib.tsnet_op_add_stats.argtypes = [_vp, _vp] + [C.c_int] * 5 + [_vp, _vp, _vp, _vp]
-        lib.tsnet_op_finalize_stats.argtypes = [_vp] + [C.c_int] * 4 + [_vp, _vp, _vp]
-        lib.tsnet_op_fuse_tail.argtypes = [_vp] * 5 + [C.c_int] * 5 + [_vp, _vp]
-        lib.tsnet_op_pack_input.argtypes = [pp, pp] + [C.c_int] * 8 + [_fp, _vp, _vp, _vp]
-        lib.tsnet_op_upsample2x_st.argtypes = [_vp, _vp, _vp] + [C.c_int] * 7 + [_vp, _vp]
-    lib.tsnet_op_last_error.restype = C.c_char_p
-    lib.tsnet_frame_stats.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp]
-    lib.tsnet_demo_postprocess.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _fp, _vp, _vp]
-    lib.tsnet_fit_face_curves.argtypes = [_vp, C.c_int, _vp]
-    lib.tsnet_fit_pose_curves.argtypes = [_vp, C.c_int, C.c_int, _vp]
-    lib.tsnet_raster_face.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
-    lib.tsnet_vl2ch.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]
-    lib.tsnet_raster_pose.argtypes = [_vp, _vp] + [C.c_int] * 8 + [_vp, _vp]
-    lib.tsnet_label_bbox.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]
-    lib.tsnet_resize_pad.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp] + [C.c_int] * 7 + [_vp, _vp]
-    lib.tsnet_bench_conv.argtypes = [C.c_int] * 12 + [_fp, _vp]
-    lib.tsnet_debug_counters.argtypes = [C.POINTER(C.c_int64), C.c_int]
-    lib.tsnet_debug_counters.restype = None
-    lib.tsnet_linspace.argtypes = [C.c_int, _fp]
-    lib.tsnet_linspace.restype = None
-    lib.tsnet_coord_table.argtypes = [C.c_int, C.c_int, _fp]
-    lib.tsnet_coord_table.restype = None
-    if hasattr(lib, "tsnet_prepare_frames"):     # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_bicubic_taps.argtypes = [C.c_int, C.c_int]
-        lib.tsnet_bicubic_table.argtypes = [C.c_int, C.c_int, _vp, _vp, _vp]
-        lib.tsnet_prepare_frames.argtypes = [_vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_fp, _vp, _vp]
-    if hasattr(lib, "tsnet_face_adapt_stats"):   # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_face_adapt_stats.argtypes = [_vp, C.c_int, _vp]
-        lib.tsnet_face_adapt_apply.argtypes = [_vp, _vp, C.c_int]
-        lib.tsnet_smooth_keypoints.argtypes = [_vp, C.c_int, C.c_int, _vp]
-    if hasattr(lib, "tsnet_forward_bank"):       # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        _ip = C.POINTER(C.c_int)
-        lib.tsnet_bank_capacity.argtypes = [_vp]
-        lib.tsnet_bank_put.argtypes = [_vp, C.c_int, C.c_int, pp, pp, pp, _fp, _vp]
-        lib.tsnet_forward_bank.argtypes = [_vp, _ip, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]
-        lib.tsnet_op_flow_k_slots.argtypes = [_vp, _vp, _vp, _vp] + [C.c_int] * 7 + [_vp, C.c_int, C.c_int, _fp, _ip, C.c_int, _vp]
-        lib.tsnet_op_warp_k_slots.argtypes = [_vp, _vp] + [C.c_int] * 5 + [_vp, _ip, C.c_int, _vp]
-        lib.tsnet_op_add_stats_slots.argtypes = [_vp, _vp] + [C.c_int] * 4 + [_vp, _vp, _vp, _ip, C.c_int, _vp]
-        lib.tsnet_op_fuse_tail_slots.argtypes = [_vp] * 5 + [C.c_int] * 4 + [_vp, _ip, C.c_int, _vp]
-    if hasattr(lib, "tsnet_forward_u8"):         # absent from an older build opened beside this one (tools/clip_bench.py --lib2)
-        _ip = C.POINTER(C.c_int)
-        lib.tsnet_forward_u8.argtypes = [_vp, pp, pp, pp, _vp, _vp, _fp, _vp, _vp, C.c_int, _vp]
-        lib.tsnet_set_sources_u8.argtypes = [_vp, pp, pp, pp, _fp, C.c_int, C.c_int, _vp]
-        lib.tsnet_forward_target_u8.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
-        lib.tsnet_bank_put_u8.argtypes = [_vp, C.c_int, C.c_int, pp, pp, pp, _fp, _fp, _vp]
-        lib.tsnet_forward_bank_u8.argtypes = [_vp, _ip, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]
-        lib.tsnet_op_pack_input_u8.argtypes = [pp, pp, pp] + [C.c_int] * 8 + [_fp, _fp, _vp, _vp, _vp, _vp]
-        lib.tsnet_prepare_frames_u8.argtypes = [_vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_vp, _vp]
-    if hasattr(lib, "tsnet_paste_frames"):       # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_paste_frames.argtypes = [_vp, _vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int] + [_vp] + [C.c_int] * 6 + [_vp]
-    if hasattr(lib, "tsnet_paste_frames_boxes"): # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_prepare_frames_boxes.argtypes = [_vp] + [C.c_int] * 3 + [_vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_fp, _vp, _vp]
-        lib.tsnet_prepare_frames_boxes_u8.argtypes = [_vp] + [C.c_int] * 3 + [_vp, _vp, _vp, C.c_int] + [C.c_int] * 6 + [_vp, _vp]
-        lib.tsnet_paste_frames_boxes.argtypes = [_vp, _vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int] + [_vp, C.c_int, C.c_int, _vp]
-    if hasattr(lib, "tsnet_face_labels_boxes"):  # absent from an older build opened beside this one (tools/track_labels_bench.py --lib2)
-        for fn in (lib.tsnet_face_labels_boxes, lib.tsnet_face_labels_boxes_u8):
-            fn.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, C.c_int, _vp, _vp, _vp]
-    if hasattr(lib, "tsnet_op_upconv2d"):        # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_op_upconv2d.argtypes = lib.tsnet_op_conv2d.argtypes
-    if hasattr(lib, "tsnet_op_conv2d_epi"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_op_conv2d_epi.argtypes = lib.tsnet_op_conv2d.argtypes[:-1] + [C.POINTER(TsnetConvEpi), _vp]
-    if hasattr(lib, "tsnet_op_train_tail"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_op_patch_warp.argtypes = [pp, _fp, _vp] + [C.c_int] * 6 + [_vp, _vp]
-        lib.tsnet_op_train_tail.argtypes = [_vp] * 4 + [C.c_int] * 8 + [_fp] + [_vp] * 6
-    if hasattr(lib, "tsnet_blur_mask"):          # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_gaussian_box_params.argtypes = [C.c_float, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-        lib.tsnet_blur_mask.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]
-    if hasattr(lib, "tsnet_rgb_to_yuv420"):      # absent from an older build opened beside this one (tools/forward_ab.py --lib2)
-        lib.tsnet_yuv_coeffs.argtypes = [C.c_int, C.c_int, _vp, _vp]
-        lib.tsnet_rgb_to_yuv420.argtypes = lib.tsnet_yuv420_to_rgb.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]
+    """Attach argtypes/restypes for every ABI entry point the library has."""
+    for name, sig in ABI.items():
+        if hasattr(lib, name):                     # newer entries are absent from an older build opened beside this one (tools/*.py --lib2)
+            fn = getattr(lib, name)
+            argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
+            if argtypes is not None:
+                fn.argtypes = argtypes
     return lib
 
 

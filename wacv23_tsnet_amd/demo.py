@@ -11,18 +11,13 @@ from __future__ import annotations
 import ctypes as C
 from typing import Sequence
 
-import contextlib
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._call import call
 
 IMG_MEAN = np.array((101.84807705937696, 112.10832843463207, 111.65973036298041), dtype=np.float32)   # demo_face.py:27
-
-
-def _stream_of(t: torch.Tensor):
-    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else None
 
 
 class DemoPostprocessor:
@@ -34,15 +29,10 @@ class DemoPostprocessor:
         ref = ref_img.reshape(1, 3, -1).contiguous().float()
         self.ref_mean = torch.empty(3, dtype=torch.float32, device=ref.device)
         self.ref_std = torch.empty(3, dtype=torch.float32, device=ref.device)
-        rc = self.lib.tsnet_frame_stats(ref.data_ptr(), 1, 3, ref.shape[2], 255.0, self.ref_mean.data_ptr(),
-                                        self.ref_std.data_ptr(), _stream_of(ref))
-        self._check(rc, "tsnet_frame_stats")
+        call(self.lib, "tsnet_frame_stats", ref.data_ptr(), 1, 3, ref.shape[2], 255.0, self.ref_mean.data_ptr(), self.ref_std.data_ptr(),
+             device=ref.device)
         # IMG_MEAN / 255 in float32, as `torch.from_numpy(IMG_MEAN).cuda() / 255` (demo_face.py:98)
         self._img_mean = (C.c_float * 3)(*[float(v) for v in (torch.from_numpy(IMG_MEAN) / 255).tolist()])
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
 
     def __call__(self, rec: torch.Tensor) -> torch.Tensor:
         if rec.dim() != 4 or rec.shape[1] != 3 or rec.dtype != torch.float32:
@@ -54,10 +44,9 @@ class DemoPostprocessor:
         gm = torch.empty(B * 3, dtype=torch.float32, device=rec.device)
         gs = torch.empty(B * 3, dtype=torch.float32, device=rec.device)
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=rec.device)
-        st = _stream_of(rec)
-        self._check(self.lib.tsnet_frame_stats(rec.data_ptr(), B, 3, H * W, 1.0, gm.data_ptr(), gs.data_ptr(), st), "tsnet_frame_stats")
-        self._check(self.lib.tsnet_demo_postprocess(rec.data_ptr(), B, H, W, gm.data_ptr(), gs.data_ptr(), self.ref_mean.data_ptr(),
-                                                    self.ref_std.data_ptr(), self._img_mean, out.data_ptr(), st), "tsnet_demo_postprocess")
+        call(self.lib, "tsnet_frame_stats", rec.data_ptr(), B, 3, H * W, 1.0, gm.data_ptr(), gs.data_ptr(), device=rec.device)
+        call(self.lib, "tsnet_demo_postprocess", rec.data_ptr(), B, H, W, gm.data_ptr(), gs.data_ptr(), self.ref_mean.data_ptr(),
+             self.ref_std.data_ptr(), self._img_mean, out.data_ptr(), device=rec.device)
         return out
 
 
@@ -111,20 +100,14 @@ def resize_label(x: torch.Tensor, size=(256, 256), lib=None) -> torch.Tensor:
     bilinear sampling at f (o + 0.5) - 0.5 with mirrored borders in float64, threshold 0.5.  PARITY UNPINNED (RESIZE_NOTE): the kernels
     follow oracle/skimage_resize.py, which tests/test_resize.py holds them equal to, but neither can be run against scikit-image here.
     lib: tests pass the CPU emulation build; product code leaves it None (the in-tree HIP library, no fallback)."""
-    from . import _lib
     lib = lib if lib is not None else _lib.load()
     F_, h, w = x.shape
     H, W = size
     src = x.to(torch.uint8).contiguous()
     out = torch.empty((F_, H, W), dtype=torch.float32, device=src.device)
     (lr, wr), (lc, wc) = _aa_kernel(h, H), _aa_kernel(w, W)
-    cuda = src.device.type == "cuda"
-    stream = torch.cuda.current_stream(src.device).cuda_stream if cuda else None
-    with (torch.cuda.device(src.device) if cuda else contextlib.nullcontext()):
-        rc = lib.tsnet_resize_label(src.data_ptr(), F_, h, w, H, W, wr.ctypes.data if wr is not None else None, lr,
-                                    wc.ctypes.data if wc is not None else None, lc, out.data_ptr(), stream)
-    if rc != 0:
-        raise RuntimeError(f"tsnet_resize_label failed ({rc}): {lib.tsnet_op_last_error().decode()}")
+    call(lib, "tsnet_resize_label", src.data_ptr(), F_, h, w, H, W, wr.ctypes.data if wr is not None else None, lr,
+         wc.ctypes.data if wc is not None else None, lc, out.data_ptr(), device=src.device)
     return out
 
 

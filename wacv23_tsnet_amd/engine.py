@@ -11,26 +11,13 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _lib
+from ._call import call
 
 POSE_MEAN = (101.84807705937696, 112.10832843463207, 111.65973036298041)  # reference model/TSNet_pose.py:215
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
-
-
-def _stream_of(t: torch.Tensor) -> Optional[int]:
-    if t.is_cuda:
-        return torch.cuda.current_stream(t.device).cuda_stream
-    return None
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 class TSNetEngine:
@@ -62,35 +49,25 @@ class TSNetEngine:
         self.w = width >> n_downsampling
         self.C = ngf << n_downsampling
         self._h = C.c_void_p()
-        rc = self.lib.tsnet_create(C.byref(cfg), C.byref(self._h))
-        if rc != 0:
-            raise RuntimeError(f"tsnet_create failed ({rc}): {self.lib.tsnet_last_error(None).decode()}")
+        call(self.lib, "tsnet_create", C.byref(cfg), C.byref(self._h), handle=None)
         self.finalized = False
         self.device: Optional[torch.device] = None     # fixed at finalize(): every allocation, stream and launch of this handle lives there
+        self._held = {}                                 # method -> the tensors its last call launched on ("what a wrapper keeps")
 
     # ------------------------------------------------------------------ helpers
-    def _on_device(self, dev=None):
-        """Context that makes the engine's GPU the current HIP device for the duration of an ABI call.  The library allocates
-        (hipMalloc), creates its side stream / events and launches on the CURRENT device; the caller's current device may be
-        another one (model on cuda:1, torch.cuda.current_device() == 0)."""
-        d = torch.device(dev) if dev is not None else self.device
-        if d is not None and d.type == "cuda":
-            return torch.cuda.device(d)
-        return _NullCtx()
+    def _call(self, entry: str, *args, dev=None, stream: bool = False, **kw) -> int:
+        """An entry of this handle through `_call.call`: the engine's GPU (or `dev`, before finalize() has fixed it) is current for the
+        duration of the call, stream=True appends torch's current stream there, failures read tsnet_last_error(handle)."""
+        return call(self.lib, entry, self._h, *args, device=dev if dev is not None else self.device, stream=stream, handle=self._h, **kw)
 
     def _same_device(self, *tensors):
         for t in tensors:
             if t is not None and self.device is not None and t.device != self.device:
                 raise ValueError(f"tensor on {t.device}, engine finalized on {self.device}")
 
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self.lib.tsnet_last_error(self._h).decode()}")
-
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            with self._on_device():
-                self.lib.tsnet_destroy(self._h)
+            self._call("tsnet_destroy", check=False)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -100,13 +77,13 @@ class TSNetEngine:
             pass
 
     def param_shapes(self) -> Dict[str, tuple]:
-        n = self.lib.tsnet_num_params(self._h)
+        n = self._call("tsnet_num_params", check=False)
         out = {}
         name = C.c_char_p()
         shape = (C.c_int64 * 4)()
         rank = C.c_int()
         for i in range(n):
-            self._check(self.lib.tsnet_param_info(self._h, i, C.byref(name), shape, C.byref(rank)), "tsnet_param_info")
+            self._call("tsnet_param_info", i, C.byref(name), shape, C.byref(rank))
             out[name.value.decode()] = tuple(int(shape[j]) for j in range(rank.value))
         return out
 
@@ -124,17 +101,14 @@ class TSNetEngine:
             shp = (C.c_int64 * t.dim())(*t.shape)
             if t.is_cuda:      # the cast / copy above is queued on torch's stream; tsnet_load_weights does a blocking hipMemcpy on the null stream
                 torch.cuda.current_stream(t.device).synchronize()
-            with self._on_device(t.device if t.is_cuda else None):
-                self._check(self.lib.tsnet_load_weights(self._h, k.encode(), t.data_ptr(), shp, t.dim()), f"load_weights({k})")
+            self._call("tsnet_load_weights", k.encode(), t.data_ptr(), shp, t.dim(), dev=t.device if t.is_cuda else None, what=f"load_weights({k})")
         return self
 
     def finalize(self, device: Optional[torch.device] = None):
         dev = torch.device(device) if device is not None else None
         if dev is not None and dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        stream = torch.cuda.current_stream(dev).cuda_stream if (dev is not None and dev.type == "cuda") else None
-        with self._on_device(dev):
-            self._check(self.lib.tsnet_finalize(self._h, stream), "tsnet_finalize")
+        self._call("tsnet_finalize", dev=dev, stream=True)
         self.device = dev
         self.finalized = True
         return self
@@ -143,8 +117,7 @@ class TSNetEngine:
         """Alias the engine's packed weight buffer as a flat uint8 torch tensor (for the RCCL broadcast)."""
         p = C.c_void_p()
         n = C.c_size_t()
-        with self._on_device():
-            self._check(self.lib.tsnet_packed_weights(self._h, C.byref(p), C.byref(n)), "tsnet_packed_weights")
+        self._call("tsnet_packed_weights", C.byref(p), C.byref(n))
         return _alias_device_bytes(p.value, n.value, device)
 
     # ------------------------------------------------------------------ forward
@@ -216,15 +189,12 @@ class TSNetEngine:
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=tl.device)
         flow = torch.empty((K, B, self.h, self.w, 2), dtype=torch.float32, device=tl.device) if return_flow else None
         self._same_device(*si, *sl, *sb, tl, tb)
-        with self._on_device():
-            if u8:
-                rc = self.lib.tsnet_forward_u8(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb),
-                                               tl.data_ptr(), tb.data_ptr(), m, out.data_ptr(), _ptr(flow), B, _stream_of(tl))
-            else:
-                rc = self.lib.tsnet_forward(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb),
-                                            tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
-        self._check(rc, "tsnet_forward_u8" if u8 else "tsnet_forward")
-        self._keep = (si, sl, sb, tl, tb)   # keep inputs alive until the stream has consumed them
+        src = (self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), tl.data_ptr(), tb.data_ptr())
+        if u8:
+            self._call("tsnet_forward_u8", *src, m, out.data_ptr(), _ptr(flow), B, stream=True)
+        else:
+            self._call("tsnet_forward", *src, out.data_ptr(), _ptr(flow), B, stream=True)
+        self._held["forward"] = (si, sl, sb, tl, tb)
         return out, ([flow[i] for i in range(K)] if return_flow else None)
 
     def set_source_divisors(self, divisors: Optional[Sequence[float]] = None):
@@ -232,8 +202,7 @@ class TSNetEngine:
         TSNet.py:267,286) or 1 for `use_prev` sources that are already in [0,1] (TSNet.py:269-276).  None resets all to 255."""
         d = list(divisors or [])
         arr = (C.c_float * max(len(d), 1))(*([float(x) for x in d] or [255.0]))
-        with self._on_device():
-            self._check(self.lib.tsnet_set_source_divisors(self._h, arr, len(d)), "tsnet_set_source_divisors")
+        self._call("tsnet_set_source_divisors", arr, len(d))
 
     def set_sources(self, src_img, src_lbl, src_bbox, shared: bool = False, mean=None):
         """tsnet_set_sources: encode and cache the K sources of a batch; forward_target then takes driving frames of that batch.
@@ -249,15 +218,14 @@ class TSNetEngine:
         sb = [prep(src_bbox[i], bshape, f"src_bbox[{i}]") for i in range(K)]
         m = self._mean_arg(mean, u8, "set_sources")
         self._same_device(*si, *sl, *sb)
-        with self._on_device():
-            if u8:
-                rc = self.lib.tsnet_set_sources_u8(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), m, B, int(shared), _stream_of(si[0]))
-            elif shared:
-                rc = self.lib.tsnet_set_sources_shared(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), _stream_of(si[0]))
-            else:
-                rc = self.lib.tsnet_set_sources(self._h, self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb), B, _stream_of(si[0]))
-        self._check(rc, "tsnet_set_sources_u8" if u8 else ("tsnet_set_sources_shared" if shared else "tsnet_set_sources"))
-        self._keep_src = (si, sl, sb)
+        src = (self._ptr_array(si), self._ptr_array(sl), self._ptr_array(sb))
+        if u8:
+            self._call("tsnet_set_sources_u8", *src, m, B, int(shared), stream=True)
+        elif shared:
+            self._call("tsnet_set_sources_shared", *src, stream=True)
+        else:
+            self._call("tsnet_set_sources", *src, B, stream=True)
+        self._held["set_sources"] = (si, sl, sb)
 
     def forward_target(self, tar_lbl, tar_bbox, return_flow: bool = False):
         B = tar_lbl.shape[0]
@@ -268,18 +236,15 @@ class TSNetEngine:
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=tl.device)
         flow = torch.empty((K, B, self.h, self.w, 2), dtype=torch.float32, device=tl.device) if return_flow else None
         self._same_device(tl, tb)
-        with self._on_device():
-            fn = self.lib.tsnet_forward_target_u8 if u8 else self.lib.tsnet_forward_target
-            rc = fn(self._h, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
-        self._check(rc, "tsnet_forward_target_u8" if u8 else "tsnet_forward_target")
-        self._keep = (tl, tb)
+        self._call("tsnet_forward_target_u8" if u8 else "tsnet_forward_target", tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, stream=True)
+        self._held["forward_target"] = (tl, tb)
         return out, ([flow[i] for i in range(K)] if return_flow else None)
 
     # ------------------------------------------------------------------ source bank
     @property
     def bank_capacity(self) -> int:
         """tsnet_bank_capacity: slots of the source bank, n_source * max_batch."""
-        return int(self.lib.tsnet_bank_capacity(self._h))
+        return int(self._call("tsnet_bank_capacity", check=False))
 
     def bank_put(self, slots, src_img, src_lbl, src_bbox, divisors: Optional[Sequence[float]] = None, mean=None):
         """tsnet_bank_put: encode sources of batch 1 into slots of the bank, one tsnet_set_sources' worth of work per n_source slots.
@@ -306,14 +271,12 @@ class TSNetEngine:
             c = hi - lo
             arr = lambda ts: (C.c_void_p * c)(*[t.data_ptr() for t in ts[lo:hi]])
             div = None if divisors is None else (C.c_float * c)(*[float(x) for x in divisors[lo:hi]])
-            with self._on_device():
-                if u8:
-                    rc = self.lib.tsnet_bank_put_u8(self._h, sl[lo], c, arr(si), arr(sl_), arr(sb_), m, div, _stream_of(si[0]))
-                else:
-                    rc = self.lib.tsnet_bank_put(self._h, sl[lo], c, arr(si), arr(sl_), arr(sb_), div, _stream_of(si[0]))
-            self._check(rc, "tsnet_bank_put_u8" if u8 else "tsnet_bank_put")
+            if u8:
+                self._call("tsnet_bank_put_u8", sl[lo], c, arr(si), arr(sl_), arr(sb_), m, div, stream=True)
+            else:
+                self._call("tsnet_bank_put", sl[lo], c, arr(si), arr(sl_), arr(sb_), div, stream=True)
             lo = hi
-        self._keep_bank = (si, sl_, sb_)
+        self._held["bank_put"] = (si, sl_, sb_)
 
     def forward_bank(self, index, tar_lbl, tar_bbox, return_flow: bool = False):
         """tsnet_forward_bank.  index: (B, Kc) integers on the host (nested lists, numpy, a CPU tensor) -- row b lists the slots of
@@ -344,11 +307,9 @@ class TSNetEngine:
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=tl.device)
         flow = torch.empty((Kc, B, self.h, self.w, 2), dtype=torch.float32, device=tl.device) if return_flow else None
         self._same_device(tl, tb)
-        with self._on_device():
-            fn = self.lib.tsnet_forward_bank_u8 if u8 else self.lib.tsnet_forward_bank
-            rc = fn(self._h, table, Kc, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B, _stream_of(tl))
-        self._check(rc, "tsnet_forward_bank_u8" if u8 else "tsnet_forward_bank")
-        self._keep = (tl, tb)
+        self._call("tsnet_forward_bank_u8" if u8 else "tsnet_forward_bank", table, Kc, tl.data_ptr(), tb.data_ptr(), out.data_ptr(), _ptr(flow), B,
+                   stream=True)
+        self._held["forward_bank"] = (tl, tb)
         return out, ([flow[i] for i in range(Kc)] if return_flow else None)
 
     def train_extras(self, src_img: List[torch.Tensor], tar_img: torch.Tensor):
@@ -363,10 +324,8 @@ class TSNetEngine:
         warp = torch.empty((K, B, 3, H, W), dtype=torch.float32, device=ti.device)
         losses = torch.empty(2, dtype=torch.float32, device=ti.device)
         self._same_device(*si, ti)
-        with self._on_device():
-            rc = self.lib.tsnet_train_extras(self._h, self._ptr_array(si), ti.data_ptr(), B, warp.data_ptr(), losses.data_ptr(), _stream_of(ti))
-        self._check(rc, "tsnet_train_extras")
-        self._keep_train = (si, ti)
+        self._call("tsnet_train_extras", self._ptr_array(si), ti.data_ptr(), B, warp.data_ptr(), losses.data_ptr(), stream=True)
+        self._held["train_extras"] = (si, ti)
         return [warp[i] for i in range(K)], losses[0], (None if self.cfg.pose_composite else losses[1])
 
     def stage(self, name: str, device, shape=None) -> torch.Tensor:
@@ -374,20 +333,20 @@ class TSNetEngine:
         for stages that are not at the feature resolution ("dec_up<i>")."""
         p = C.c_void_p()
         n = C.c_size_t()
-        self._check(self.lib.tsnet_stage_ptr(self._h, name.encode(), C.byref(p), C.byref(n)), "tsnet_stage_ptr")
+        self._call("tsnet_stage_ptr", name.encode(), C.byref(p), C.byref(n))
         flat = _alias_device_bytes(p.value, n.value * 4, device).view(torch.float32).clone()
         return flat.view(-1, *(shape if shape is not None else (self.h, self.w, self.C)))
 
     def forward_macs(self, B: int) -> float:
-        return float(self.lib.tsnet_forward_macs(self._h, B))
+        return float(self._call("tsnet_forward_macs", B, check=False))
 
     def timing_enable(self, on: bool):
-        self._check(self.lib.tsnet_timing_enable(self._h, int(on)), "tsnet_timing_enable")
+        self._call("tsnet_timing_enable", int(on))
 
     def timing_read(self, reset: bool = True):
         ms = (C.c_double * _lib.TIMING_CLASSES)()
         cnt = (C.c_int64 * _lib.TIMING_CLASSES)()
-        self._check(self.lib.tsnet_timing_read(self._h, ms, cnt, int(reset)), "tsnet_timing_read")
+        self._call("tsnet_timing_read", ms, cnt, int(reset))
         return {n: (ms[i], int(cnt[i])) for i, n in enumerate(_lib.TIMING_NAMES)}
 
 

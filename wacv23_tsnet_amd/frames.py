@@ -26,7 +26,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from ._call import Wrapper, call, fail, last_error
 from .demo import IMG_MEAN
 
 PRECISION_BITS = 22
@@ -71,17 +71,44 @@ def bicubic_table(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.nda
 
 def bicubic_table_c(lib, n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The same table from the library's host entry `tsnet_bicubic_table`."""
-    taps = lib.tsnet_bicubic_taps(n_in, n_out)
+    taps = call(lib, "tsnet_bicubic_taps", n_in, n_out, check=False)
     if taps < 0:
-        raise RuntimeError(f"tsnet_bicubic_taps failed ({taps}): {lib.tsnet_op_last_error().decode()}")
+        fail(lib, "tsnet_bicubic_taps", taps)
     first, count, coef = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32), np.zeros((n_out, taps), np.int32)
-    rc = lib.tsnet_bicubic_table(n_in, n_out, first.ctypes.data, count.ctypes.data, coef.ctypes.data)
-    if rc != 0:
-        raise RuntimeError(f"tsnet_bicubic_table failed ({rc}): {lib.tsnet_op_last_error().decode()}")
+    call(lib, "tsnet_bicubic_table", n_in, n_out, first.ctypes.data, count.ctypes.data, coef.ctypes.data)
     return first, count, coef
 
 
-class FrameLoader:
+YUV_STANDARDS = {"bt601": 601, "bt709": 709}
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+
+
+def _yuv_layout(layout) -> int:
+    if str(layout).lower() not in YUV_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}, not {layout!r}")
+    return YUV_LAYOUTS[str(layout).lower()]
+
+
+def yuv_frame_bytes(h: int, w: int) -> int:
+    """bytes of one 4:2:0 frame of h x w pixels, either layout"""
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+def yuv_planes(buf, h: int, w: int, layout: str = "i420"):
+    """Views of the planes of (F, yuv_frame_bytes(h, w)) frames, tensor or array: (Y (F,h,w), Cb (F,ch,cw), Cr (F,ch,cw)); in "nv12" the two
+    chroma views are the strided halves of the interleaved plane."""
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    if buf.ndim != 2 or buf.shape[1] != yuv_frame_bytes(h, w):
+        raise ValueError(f"expected frames of shape (F, {yuv_frame_bytes(h, w)}) for size {(h, w)}, got {tuple(buf.shape)}")
+    F = buf.shape[0]
+    y = buf[:, :h * w].reshape(F, h, w)
+    if _yuv_layout(layout) == 0:
+        return y, buf[:, h * w:h * w + ch * cw].reshape(F, ch, cw), buf[:, h * w + ch * cw:].reshape(F, ch, cw)
+    uv = buf[:, h * w:].reshape(F, ch, cw, 2)
+    return y, uv[..., 0], uv[..., 1]
+
+
+class FrameLoader(Wrapper):
     """Network-input image tensors of a clip's frames on `device`.
 
     lib: tests pass the CPU emulation build; product code leaves it None (the in-tree HIP library, no fallback).
@@ -89,17 +116,13 @@ class FrameLoader:
     already on the device only enqueues one kernel on the current stream (no allocation inside the library, no synchronisation)."""
 
     def __init__(self, device, lib=None):
-        self.lib = lib if lib is not None else _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device, lib)
         self._tables = {}
-        self._keep = []
         self._pool_host = np.zeros(0, np.int32)                      # the tables of the per-frame-box calls, one after the other
         self._pool_at = {}                                           # (n_in, n_out) -> (offset in ints, taps)
-        self._pool = None                                            # the device copy; replaced (never written) when the pool grows
-        self._pool_prev = None
-
-    def _stream(self) -> Optional[int]:
-        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
+        self._pool = None                                            # the device copy; replaced (never written) when the pool has grown
+        self._feather_tmp = None                                     # the intermediate between feather_mask's two kernels; grows, never shrinks
+        self._yuv_tables = {}                                        # (standard, full range) -> (fwd, inv) of tsnet_yuv_coeffs
 
     def _axis(self, n_in: int, n_out: int):
         """(device int32 tensor [first | count | coef], taps) of one axis, cached"""
@@ -109,6 +132,11 @@ class FrameLoader:
             flat = torch.from_numpy(np.concatenate([first, count, coef.ravel()])).to(self.device)
             self._tables[key] = (flat, coef.shape[1])
         return self._tables[key]
+
+    def _axis_args(self, n_in: int, n_out: int):
+        """that table as tsnet_prepare_frames / tsnet_paste_frames take it: (first, count, coef, taps)"""
+        flat, taps = self._axis(n_in, n_out)
+        return flat.data_ptr(), flat.data_ptr() + 4 * n_out, flat.data_ptr() + 8 * n_out, taps
 
     # ------------------------------------------------------------------------------------------------------------------ a box per frame
     def _pool_axis(self, n_in: int, n_out: int) -> Tuple[int, int]:
@@ -120,7 +148,6 @@ class FrameLoader:
             first, count, coef = bicubic_table_c(self.lib, n_in, n_out)
             self._pool_at[key] = (len(self._pool_host), coef.shape[1])
             self._pool_host = np.concatenate([self._pool_host, first, count, coef.ravel()])
-            self._pool = None
         return self._pool_at[key]
 
     def _descriptors(self, boxes: np.ndarray, sizes):
@@ -136,9 +163,8 @@ class FrameLoader:
             rows.append((b[0], b[1], b[2], b[3], x[0], x[1], y[0], y[1]))
         desc = np.array(rows, dtype=np.int32).reshape(-1, 8)
         old = None
-        if self._pool is None:                                       # grown: a new device copy; the old one may still be read by an enqueued kernel
-            old, self._pool = self._pool_prev, torch.from_numpy(self._pool_host.copy()).to(self.device)
-            self._pool_prev = self._pool
+        if self._pool is None or self._pool.numel() != len(self._pool_host):     # grown: a new device copy; an enqueued kernel may still read the old one
+            old, self._pool = self._pool, torch.from_numpy(self._pool_host.copy()).to(self.device)
         return desc, torch.from_numpy(desc).to(self.device), self._pool, old
 
     @staticmethod
@@ -150,60 +176,21 @@ class FrameLoader:
             raise ValueError(f"{b.shape[0]} boxes for {F} frames")
         return b.astype(np.int64)[:, list(order)]
 
-    def _prepare_boxes(self, frames, boxes, size, square, mean, as_bytes) -> torch.Tensor:
+    def _prepare_front(self, frames, size, square, mean, as_bytes):
+        """what `prepare` does before it looks at its box: (the frames on the device, (oh, ow, pad_top, pad_left, OH, OW), the mean as the ABI
+        takes it, the output tensor)"""
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
             raise ValueError(f"expected uint8 frames of shape (F,h,w,3), got {tuple(frames.shape)} {frames.dtype}")
         fr = frames.to(self.device).contiguous()
-        F, h, w, _ = fr.shape
         ow, oh = int(size[0]), int(size[1])
         S = max(ow, oh)
         OH, OW = (S, S) if square else (oh, ow)
-        pad_top, pad_left = (OH - oh) // 2, (OW - ow) // 2
-        desc, desc_d, pool, old = self._descriptors(self._boxes(boxes, F), lambda b: ((int(b[2] - b[0]), ow), (int(b[3] - b[1]), oh)))
         m = np.asarray(mean, dtype=np.float32)
         mean_c = (C.c_float * 3)(float(m[0]), float(m[1]), float(m[2]))
-        out = torch.empty((F, 3, OH, OW), dtype=torch.uint8 if as_bytes else torch.float32, device=self.device)
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        geom = (fr.data_ptr(), F, h, w, desc.ctypes.data, desc_d.data_ptr(), pool.data_ptr(), pool.numel(), oh, ow, pad_top, pad_left, OH, OW)
-        with ctx:
-            if as_bytes:
-                rc = self.lib.tsnet_prepare_frames_boxes_u8(*geom, out.data_ptr(), self._stream())
-            else:
-                rc = self.lib.tsnet_prepare_frames_boxes(*geom, mean_c, out.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"tsnet_prepare_frames_boxes{'_u8' if as_bytes else ''} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep = [fr, desc_d, pool, old]                         # alive until the stream has consumed them
-        return out
-
-    def _paste_boxes(self, gen, frames, boxes, src_box, mask, inplace) -> torch.Tensor:
-        g = self._u8(gen, "generated frames", 4)
-        fr = self._u8(frames, "frames", 4)
-        m = None if mask is None else self._u8(mask, "mask", 3)
-        F, GH, GW, _ = g.shape
-        if fr.shape[0] != F:
-            raise ValueError(f"{F} generated frames, {fr.shape[0]} frames to paste into")
-        if m is not None and tuple(m.shape) != (F, GH, GW):
-            raise ValueError(f"mask of shape {tuple(m.shape)}, generated frames {tuple(g.shape)}")
-        sx0, sy0, sx1, sy1 = (0, 0, GW, GH) if src_box is None else (int(v) for v in src_box)
-        if not (0 <= sx0 < sx1 <= GW and 0 <= sy0 < sy1 <= GH):
-            raise ValueError(f"source rectangle {(sx0, sy0, sx1, sy1)} is empty or not inside the {GW} x {GH} generated frames")
-        desc, desc_d, pool, old = self._descriptors(self._boxes(boxes, F), lambda b: ((sx1 - sx0, int(b[2] - b[0])), (sy1 - sy0, int(b[3] - b[1]))))
-        g = g.to(self.device).contiguous()
-        m = None if m is None else m.to(self.device).contiguous()
-        out = fr.to(self.device).contiguous()
-        if not inplace and out.data_ptr() == fr.data_ptr():
-            out = out.clone()
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = self.lib.tsnet_paste_frames_boxes(g.data_ptr(), None if m is None else m.data_ptr(), F, GH, GW, sx0, sy0, sx1, sy1,
-                                                   desc.ctypes.data, desc_d.data_ptr(), pool.data_ptr(), pool.numel(),
-                                                   out.data_ptr(), out.shape[1], out.shape[2], self._stream())
-        if rc != 0:
-            raise RuntimeError(f"tsnet_paste_frames_boxes failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep = [g, m, desc_d, pool, old]                       # alive until the stream has consumed them
-        return out
+        out = torch.empty((fr.shape[0], 3, OH, OW), dtype=torch.uint8 if as_bytes else torch.float32, device=self.device)
+        return fr, (oh, ow, (OH - oh) // 2, (OW - ow) // 2, OH, OW), mean_c, out
 
     def prepare(self, frames, box: Sequence[int], size: Tuple[int, int], square: bool = False, mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """frames: (F,h,w,3) uint8 RGB, tensor or array (uploaded once when on the host).  box: (x0, y0, x1, y1) in PIL order; it may leave the
@@ -213,50 +200,42 @@ class FrameLoader:
         call (Engine.forward(..., mean=)), a quarter of the size; bytes.float() - mean is the float32 result, bit for bit.
         box may be an (F,4) array-like, one box per frame (`tsnet_prepare_frames_boxes`, still one kernel): frame f then has the bytes of
         prepare(frames[f:f+1], box[f], ...)."""
-        if np.ndim(box) == 2:
-            return self._prepare_boxes(frames, box, size, square, mean, as_bytes)
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
-            raise ValueError(f"expected uint8 frames of shape (F,h,w,3), got {tuple(frames.shape)} {frames.dtype}")
-        fr = frames.to(self.device).contiguous()
+        fr, geom, mean_c, out = self._prepare_front(frames, size, square, mean, as_bytes)
         F, h, w, _ = fr.shape
-        x0, y0, x1, y1 = (int(v) for v in box)
-        ow, oh = int(size[0]), int(size[1])
-        S = max(ow, oh)
-        OH, OW = (S, S) if square else (oh, ow)
-        pad_top, pad_left = (OH - oh) // 2, (OW - ow) // 2
-        if x1 <= x0 or y1 <= y0:
-            raise ValueError(f"empty crop box {tuple(box)}")
-        xt, xtaps = self._axis(x1 - x0, ow)
-        yt, ytaps = self._axis(y1 - y0, oh)
-        m = np.asarray(mean, dtype=np.float32)
-        mean_c = (C.c_float * 3)(float(m[0]), float(m[1]), float(m[2]))
-        out = torch.empty((F, 3, OH, OW), dtype=torch.uint8 if as_bytes else torch.float32, device=self.device)
-        p = lambda t, off: t.data_ptr() + 4 * off
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        geom = (fr.data_ptr(), F, h, w, x0, y0, x1, y1, p(xt, 0), p(xt, ow), p(xt, 2 * ow), xtaps, p(yt, 0), p(yt, oh), p(yt, 2 * oh), ytaps,
-                oh, ow, pad_top, pad_left, OH, OW)
-        with ctx:
-            if as_bytes:
-                rc = self.lib.tsnet_prepare_frames_u8(*geom, out.data_ptr(), self._stream())
-            else:
-                rc = self.lib.tsnet_prepare_frames(*geom, mean_c, out.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"tsnet_prepare_frames{'_u8' if as_bytes else ''} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep = [fr]                                            # alive until the stream has consumed it
+        oh, ow = geom[:2]
+        held = {"frames": fr}
+        if np.ndim(box) == 2:
+            desc, desc_d, pool, old = self._descriptors(self._boxes(box, F), lambda b: ((int(b[2] - b[0]), ow), (int(b[3] - b[1]), oh)))
+            entry, where = "tsnet_prepare_frames_boxes", (desc.ctypes.data, desc_d.data_ptr(), pool.data_ptr(), pool.numel())
+            held.update(descriptors=desc_d, pool=pool, old_pool=old)
+        else:
+            x0, y0, x1, y1 = (int(v) for v in box)
+            if x1 <= x0 or y1 <= y0:
+                raise ValueError(f"empty crop box {tuple(box)}")
+            entry, where = "tsnet_prepare_frames", (x0, y0, x1, y1, *self._axis_args(x1 - x0, ow), *self._axis_args(y1 - y0, oh))
+        if as_bytes:
+            call(self.lib, entry + "_u8", fr.data_ptr(), F, h, w, *where, *geom, out.data_ptr(), device=self.device)
+        else:
+            call(self.lib, entry, fr.data_ptr(), F, h, w, *where, *geom, mean_c, out.data_ptr(), device=self.device)
+        self._held["prepare"] = held
         return out
 
     def face(self, frames, crop: Sequence[int], size: Tuple[int, int] = (256, 256), mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """The face loader's image: crop = [min_y, max_y, min_x, max_x] as raster.crop_coords returns it (get_crop_coords, not clipped to the frame)."""
         if np.ndim(crop) == 2:                                       # (F,4): a crop per frame, as raster.crop_coords_clip returns them
-            return self.prepare(frames, self._boxes(crop, len(frames), (2, 0, 3, 1)), size, square=False, mean=mean, as_bytes=as_bytes)
-        min_y, max_y, min_x, max_x = crop
-        return self.prepare(frames, (min_x, min_y, max_x, max_y), size, square=False, mean=mean, as_bytes=as_bytes)
+            box = self._boxes(crop, len(frames), (2, 0, 3, 1))
+        else:
+            min_y, max_y, min_x, max_x = crop
+            box = (min_x, min_y, max_x, max_y)
+        out = self.prepare(frames, box, size, square=False, mean=mean, as_bytes=as_bytes)
+        self._held["face"] = self._held["prepare"]
+        return out
 
     def pose(self, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mean=IMG_MEAN, as_bytes: bool = False) -> torch.Tensor:
         """The pose loader's image: crop = (xs, ys, xe, ye) as raster.pose_crop_coords returns it; 128 x 256, then padded to 256 x 256."""
-        return self.prepare(frames, crop, img_size, square=True, mean=mean, as_bytes=as_bytes)
+        out = self.prepare(frames, crop, img_size, square=True, mean=mean, as_bytes=as_bytes)
+        self._held["pose"] = self._held["prepare"]
+        return out
 
     # ------------------------------------------------------------------------------------------------------------------ the way back
     def _u8(self, t, what: str, ndim: int) -> torch.Tensor:
@@ -271,8 +250,8 @@ class FrameLoader:
     def _box_params(self, radius: float) -> Tuple[int, int, int]:
         """(box_radius, ww, fw) of one axis from `tsnet_gaussian_box_params` (three passes, as Pillow's GaussianBlur)"""
         br, ww, fw = C.c_int(), C.c_uint(), C.c_uint()
-        if self.lib.tsnet_gaussian_box_params(float(radius), 3, C.byref(br), C.byref(ww), C.byref(fw)) != 0:
-            raise ValueError(f"feather radius {radius!r}: {self.lib.tsnet_op_last_error().decode()}")
+        if call(self.lib, "tsnet_gaussian_box_params", float(radius), 3, C.byref(br), C.byref(ww), C.byref(fw), check=False) != 0:
+            raise ValueError(f"feather radius {radius!r}: {last_error(self.lib)}")
         return br.value, ww.value, fw.value
 
     @staticmethod
@@ -309,17 +288,13 @@ class FrameLoader:
             m = self._u8(src, "mask", 3).to(self.device).contiguous()
             F, H, W = m.shape
         n = max(F * H * W, 1)
-        tmp = getattr(self, "_feather_tmp", None)
-        if tmp is None or tmp.numel() < n:
-            tmp = self._feather_tmp = torch.empty(n, dtype=torch.uint8, device=self.device)
+        old = None
+        if self._feather_tmp is None or self._feather_tmp.numel() < n:
+            old, self._feather_tmp = self._feather_tmp, torch.empty(n, dtype=torch.uint8, device=self.device)
         out = torch.empty((max(F, 0), max(H, 0), max(W, 0)), dtype=torch.uint8, device=self.device)
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = self.lib.tsnet_blur_mask(None if m is None else m.data_ptr(), F, H, W, rect_c, rx, ry, 1 if binary else 0,
-                                          out.data_ptr(), tmp.data_ptr(), self._stream())
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"tsnet_blur_mask failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep_feather = [m]                                     # alive until the stream has consumed it
+        call(self.lib, "tsnet_blur_mask", None if m is None else m.data_ptr(), F, H, W, rect_c, rx, ry, 1 if binary else 0, out.data_ptr(),
+             self._feather_tmp.data_ptr(), device=self.device, refusal=ValueError)
+        self._held["feather_mask"] = {"src": m, "old_workspace": old}
         return out
 
     def _paste_mask(self, mask, feather, size, src_box):
@@ -337,6 +312,32 @@ class FrameLoader:
                              f"{sx1 - sx0} x {sy1 - sy0} source rectangle")
         return self.feather_mask(None, feather, size=(F, GH, GW), rect=rect)
 
+    def _paste_front(self, gen, frames, box, src_box, mask, inplace):
+        """what `paste` does before it builds its box arguments: (g, m, out) checked and on the device -- out the frames, or their clone --,
+        the source rectangle, and the call's single box as ints (box=None, a box per frame: None; those are `_descriptors`' to check)."""
+        g = self._u8(gen, "generated frames", 4)
+        fr = self._u8(frames, "frames", 4)
+        m = None if mask is None else self._u8(mask, "mask", 3)
+        F, GH, GW, _ = g.shape
+        if fr.shape[0] != F:
+            raise ValueError(f"{F} generated frames, {fr.shape[0]} frames to paste into")
+        if m is not None and tuple(m.shape) != (F, GH, GW):
+            raise ValueError(f"mask of shape {tuple(m.shape)}, generated frames {tuple(g.shape)}")
+        if box is not None:
+            x0, y0, x1, y1 = (int(v) for v in box)
+            if x1 <= x0 or y1 <= y0:
+                raise ValueError(f"empty box {tuple(box)}")
+            box = (x0, y0, x1, y1)
+        sx0, sy0, sx1, sy1 = (0, 0, GW, GH) if src_box is None else (int(v) for v in src_box)
+        if not (0 <= sx0 < sx1 <= GW and 0 <= sy0 < sy1 <= GH):
+            raise ValueError(f"source rectangle {(sx0, sy0, sx1, sy1)} is empty or not inside the {GW} x {GH} generated frames")
+        g = g.to(self.device).contiguous()
+        m = None if m is None else m.to(self.device).contiguous()
+        out = fr.to(self.device).contiguous()
+        if not inplace and out.data_ptr() == fr.data_ptr():
+            out = out.clone()
+        return g, m, out, (sx0, sy0, sx1, sy1), box
+
     def paste(self, gen, frames, box: Sequence[int], src_box: Optional[Sequence[int]] = None, mask=None, inplace: bool = False, feather=None) -> torch.Tensor:
         """Generated frames back into the video (`tsnet_paste_frames`, csrc/paste.hpp): per frame f, byte for byte,
             g = Image.fromarray(gen[f]).crop(src_box).resize((x1 - x0, y1 - y0)); frame_f.paste(g, (x0, y0), m)
@@ -350,50 +351,36 @@ class FrameLoader:
         indicator of src_box shrunk by `feather_inset` per side -- in Pillow's terms the rectangle image through
         filter(ImageFilter.GaussianBlur(feather)) -- so that the blend reaches exactly 0 on the source rectangle's outermost ring; a
         rectangle too small for the inset is a ValueError.  With a mask, the mask is blurred first (one holding only 0 / 1 as 0 / 255)."""
+        held = {}
         if feather is not None:
             mask = self._paste_mask(mask, feather, tuple(self._u8(gen, "generated frames", 4).shape[:3]), src_box)
-        if np.ndim(box) == 2:
-            return self._paste_boxes(gen, frames, box, src_box, mask, inplace)
-        g = self._u8(gen, "generated frames", 4)
-        fr = self._u8(frames, "frames", 4)
-        m = None if mask is None else self._u8(mask, "mask", 3)
+            held["feather_mask"] = self._held["feather_mask"]
+        per_frame = np.ndim(box) == 2
+        g, m, out, src, one = self._paste_front(gen, frames, None if per_frame else box, src_box, mask, inplace)
         F, GH, GW, _ = g.shape
-        if fr.shape[0] != F:
-            raise ValueError(f"{F} generated frames, {fr.shape[0]} frames to paste into")
-        if m is not None and tuple(m.shape) != (F, GH, GW):
-            raise ValueError(f"mask of shape {tuple(m.shape)}, generated frames {tuple(g.shape)}")
-        x0, y0, x1, y1 = (int(v) for v in box)
-        sx0, sy0, sx1, sy1 = (0, 0, GW, GH) if src_box is None else (int(v) for v in src_box)
-        if x1 <= x0 or y1 <= y0:
-            raise ValueError(f"empty box {tuple(box)}")
-        if not (0 <= sx0 < sx1 <= GW and 0 <= sy0 < sy1 <= GH):
-            raise ValueError(f"source rectangle {(sx0, sy0, sx1, sy1)} is empty or not inside the {GW} x {GH} generated frames")
-        g = g.to(self.device).contiguous()
-        m = None if m is None else m.to(self.device).contiguous()
-        out = fr.to(self.device).contiguous()
-        if not inplace and out.data_ptr() == fr.data_ptr():
-            out = out.clone()
         h, w = out.shape[1], out.shape[2]
-        ow, oh = x1 - x0, y1 - y0
-        xt, xtaps = self._axis(sx1 - sx0, ow)
-        yt, ytaps = self._axis(sy1 - sy0, oh)
-        p = lambda t, off: t.data_ptr() + 4 * off
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = self.lib.tsnet_paste_frames(g.data_ptr(), None if m is None else m.data_ptr(), F, GH, GW, sx0, sy0, sx1, sy1,
-                                             p(xt, 0), p(xt, ow), p(xt, 2 * ow), xtaps, p(yt, 0), p(yt, oh), p(yt, 2 * oh), ytaps,
-                                             out.data_ptr(), h, w, x0, y0, x1, y1, self._stream())
-        if rc != 0:
-            raise RuntimeError(f"tsnet_paste_frames failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep = [g, m]                                          # alive until the stream has consumed them
+        sw, sh = src[2] - src[0], src[3] - src[1]
+        head = (g.data_ptr(), None if m is None else m.data_ptr(), F, GH, GW, *src)
+        held["gen"], held["mask"] = g, m
+        if per_frame:
+            desc, desc_d, pool, old = self._descriptors(self._boxes(box, F), lambda b: ((sw, int(b[2] - b[0])), (sh, int(b[3] - b[1]))))
+            call(self.lib, "tsnet_paste_frames_boxes", *head, desc.ctypes.data, desc_d.data_ptr(), pool.data_ptr(), pool.numel(), out.data_ptr(), h, w, device=self.device)
+            held.update(descriptors=desc_d, pool=pool, old_pool=old)
+        else:
+            call(self.lib, "tsnet_paste_frames", *head, *self._axis_args(sw, one[2] - one[0]), *self._axis_args(sh, one[3] - one[1]), out.data_ptr(), h, w, *one, device=self.device)
+        self._held["paste"] = held
         return out
 
     def paste_face(self, gen, frames, crop: Sequence[int], mask=None, inplace: bool = False, feather=None) -> torch.Tensor:
         """The inverse of `face`: crop = [min_y, max_y, min_x, max_x]; the whole generated image goes back into that box."""
         if np.ndim(crop) == 2:
-            return self.paste(gen, frames, self._boxes(crop, len(frames), (2, 0, 3, 1)), mask=mask, inplace=inplace, feather=feather)
-        min_y, max_y, min_x, max_x = crop
-        return self.paste(gen, frames, (min_x, min_y, max_x, max_y), mask=mask, inplace=inplace, feather=feather)
+            box = self._boxes(crop, len(frames), (2, 0, 3, 1))
+        else:
+            min_y, max_y, min_x, max_x = crop
+            box = (min_x, min_y, max_x, max_y)
+        out = self.paste(gen, frames, box, mask=mask, inplace=inplace, feather=feather)
+        self._held["paste_face"] = self._held["paste"]
+        return out
 
     def paste_pose(self, gen, frames, crop: Sequence[int], img_size: Tuple[int, int] = (128, 256), mask=None, inplace: bool = False,
                    feather=None) -> torch.Tensor:
@@ -403,22 +390,22 @@ class FrameLoader:
         if (gh, gw) != (S, S):
             raise ValueError(f"expected generated frames of {S} x {S} (img_size {tuple(img_size)} padded square), got {gw} x {gh}")
         px, py = (S - int(img_size[0])) // 2, (S - int(img_size[1])) // 2
-        return self.paste(gen, frames, crop, src_box=(px, py, px + int(img_size[0]), py + int(img_size[1])), mask=mask, inplace=inplace, feather=feather)
-
+        out = self.paste(gen, frames, crop, src_box=(px, py, px + int(img_size[0]), py + int(img_size[1])), mask=mask, inplace=inplace, feather=feather)
+        self._held["paste_pose"] = self._held["paste"]
+        return out
 
     # ------------------------------------------------------------------------------------------------------------------ YUV 4:2:0 in and out
     def yuv_tables(self, standard: str = "bt601", full_range: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """(fwd int32[12], inv int32[6]) of `tsnet_yuv_coeffs`, cached per (standard, range)"""
         key = (str(standard).lower(), bool(full_range))
-        cache = self.__dict__.setdefault("_yuv_tables", {})
-        if key not in cache:
+        if key not in self._yuv_tables:
             if key[0] not in YUV_STANDARDS:
                 raise ValueError(f"standard must be one of {sorted(YUV_STANDARDS)}, not {standard!r}")
             fwd, inv = np.zeros(12, np.int32), np.zeros(6, np.int32)
-            if self.lib.tsnet_yuv_coeffs(YUV_STANDARDS[key[0]], int(key[1]), fwd.ctypes.data, inv.ctypes.data) != 0:
-                raise RuntimeError(f"tsnet_yuv_coeffs failed: {self.lib.tsnet_op_last_error().decode()}")
-            cache[key] = (fwd, inv)
-        return cache[key]
+            if call(self.lib, "tsnet_yuv_coeffs", YUV_STANDARDS[key[0]], int(key[1]), fwd.ctypes.data, inv.ctypes.data, check=False) != 0:
+                raise RuntimeError(f"tsnet_yuv_coeffs failed: {last_error(self.lib)}")
+            self._yuv_tables[key] = (fwd, inv)
+        return self._yuv_tables[key]
 
     def _yuv_out(self, out, shape) -> torch.Tensor:
         if out is None:
@@ -439,12 +426,8 @@ class FrameLoader:
         F, h, w, _ = fr.shape
         fwd, _ = self.yuv_tables(standard, full_range)
         out = self._yuv_out(out, (F, yuv_frame_bytes(h, w)))
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = self.lib.tsnet_rgb_to_yuv420(fr.data_ptr(), F, h, w, fwd.ctypes.data, _yuv_layout(layout), out.data_ptr(), self._stream())
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"tsnet_rgb_to_yuv420 failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep_yuv = [fr]                                        # alive until the stream has consumed it
+        call(self.lib, "tsnet_rgb_to_yuv420", fr.data_ptr(), F, h, w, fwd.ctypes.data, _yuv_layout(layout), out.data_ptr(), refusal=ValueError, device=self.device)
+        self._held["to_yuv420"] = {"frames": fr}
         return out
 
     def from_yuv420(self, yuv, size: Tuple[int, int], layout: str = "i420", standard: str = "bt601", full_range: bool = True, out=None) -> torch.Tensor:
@@ -461,49 +444,11 @@ class FrameLoader:
         F = src.shape[0]
         _, inv = self.yuv_tables(standard, full_range)
         out = self._yuv_out(out, (F, h, w, 3))
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = self.lib.tsnet_yuv420_to_rgb(src.data_ptr(), F, h, w, inv.ctypes.data, _yuv_layout(layout), out.data_ptr(), self._stream())
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"tsnet_yuv420_to_rgb failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep_yuv = [src]                                       # alive until the stream has consumed it
+        call(self.lib, "tsnet_yuv420_to_rgb", src.data_ptr(), F, h, w, inv.ctypes.data, _yuv_layout(layout), out.data_ptr(), refusal=ValueError, device=self.device)
+        self._held["from_yuv420"] = {"frames": src}
         return out
 
-    yuv_planes = staticmethod(lambda buf, h, w, layout="i420": yuv_planes(buf, h, w, layout))
-
-
-YUV_STANDARDS = {"bt601": 601, "bt709": 709}
-YUV_LAYOUTS = {"i420": 0, "nv12": 1}
-
-
-def _yuv_layout(layout) -> int:
-    if str(layout).lower() not in YUV_LAYOUTS:
-        raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}, not {layout!r}")
-    return YUV_LAYOUTS[str(layout).lower()]
-
-
-def yuv_frame_bytes(h: int, w: int) -> int:
-    """bytes of one 4:2:0 frame of h x w pixels, either layout"""
-    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
-
-
-def yuv_planes(buf, h: int, w: int, layout: str = "i420"):
-    """Views of the planes of (F, yuv_frame_bytes(h, w)) frames, tensor or array: (Y (F,h,w), Cb (F,ch,cw), Cr (F,ch,cw)); in "nv12" the two
-    chroma views are the strided halves of the interleaved plane."""
-    ch, cw = (h + 1) // 2, (w + 1) // 2
-    if buf.ndim != 2 or buf.shape[1] != yuv_frame_bytes(h, w):
-        raise ValueError(f"expected frames of shape (F, {yuv_frame_bytes(h, w)}) for size {(h, w)}, got {tuple(buf.shape)}")
-    F = buf.shape[0]
-    y = buf[:, :h * w].reshape(F, h, w)
-    if _yuv_layout(layout) == 0:
-        return y, buf[:, h * w:h * w + ch * cw].reshape(F, ch, cw), buf[:, h * w + ch * cw:].reshape(F, ch, cw)
-    uv = buf[:, h * w:].reshape(F, ch, cw, 2)
-    return y, uv[..., 0], uv[..., 1]
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+    @staticmethod
+    def yuv_planes(buf, h: int, w: int, layout: str = "i420"):
+        """the module's `yuv_planes`, for who holds a loader"""
+        return yuv_planes(buf, h, w, layout)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import Wrapper, call
 
 
 def read_keypoints(path: str) -> np.ndarray:
@@ -47,22 +48,68 @@ def crop_coords_clip(keypoints: Sequence[np.ndarray]) -> np.ndarray:
     return np.array([crop_coords(np.asarray(k)) for k in keypoints], dtype=np.int64).reshape(-1, 4)
 
 
-class FaceRasteriser:
+def _clip_array(kps, what: Optional[str] = None) -> np.ndarray:
+    """F arrays (68,2) -> a new contiguous (F,68,2) float64 array"""
+    kp = np.ascontiguousarray(np.stack([np.asarray(k, dtype=np.float64) for k in kps]))
+    if kp.ndim != 3 or kp.shape[1:] != (68, 2):
+        raise ValueError((f"{what}: " if what else "") + f"expected F x 68 x 2 key points, got {kp.shape}")
+    return kp
+
+
+def _face_points(keypoints, crop=None, relative: bool = False, bw: Optional[int] = None, lib=None):
+    """The front half of everything that takes a clip's key points: -> (points (F,68,2) float64 relative to their crop, the crop or (F,4)
+    int64 crops, bw, the fitted curves (F,34,8) -- None when no lib is given).
+    crop: (min_y, max_y, min_x, max_x), default crop_coords of the first frame (fix_crop_pos=True, :294-299), or (F,4), one per frame
+    (fix_crop_pos=False); relative=True: the points are relative already and go on untouched.  bw defaults to max(1, h // 256) of the
+    crop (:295), the FIRST frame's when there is one per frame: the reference computes the brush once per clip (:302, :347)."""
+    kp = _clip_array(keypoints)
+    F = kp.shape[0]
+    if relative and crop is None:
+        raise ValueError("relative=True: key points relative to a crop need that crop")
+    if crop is None:
+        crop = crop_coords(kp[0])
+    if np.ndim(crop) == 2:
+        crop = np.asarray(crop).astype(np.int64)
+        if crop.shape != (F, 4):
+            raise ValueError(f"expected ({F},4) crops for {F} frames, got {crop.shape}")
+        top, left, h = crop[:, 0, None], crop[:, 2, None], int(crop[0, 1] - crop[0, 0])
+    else:
+        top, left, h = crop[0], crop[2], crop[1] - crop[0]
+    if not relative:
+        kp[:, :, 0] -= left                                        # read_keypoints (:497-507): each frame by its crop
+        kp[:, :, 1] -= top
+    if bw is None:
+        bw = max(1, h // 256)
+    curves = None
+    if lib is not None:
+        # interp_points' Levenberg-Marquardt fits run on the host (34 per frame, microseconds each; csrc/lmfit.hpp reproduces scipy's
+        # curve_fit to the last bit); the device samples and draws the fitted curves
+        curves = np.empty((F, 34, 8), dtype=np.float64)
+        call(lib, "tsnet_fit_face_curves", kp.ctypes.data, F, curves.ctypes.data)
+    return kp, crop, bw, curves
+
+
+class FaceRasteriser(Wrapper):
     """Edge maps / bounding-box masks of a clip at crop resolution, and one-hot labels, on `device`.
 
     lib: tests pass the CPU emulation build; product code leaves it None (the in-tree HIP library, no fallback)."""
 
     def __init__(self, device, lib=None):
-        self.lib = lib if lib is not None else _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device, lib)
         self._wpool_host = np.zeros(0, np.float64)                   # the Gaussian half-kernels of the per-frame-crop labels, one after the other
         self._wpool_at = {}                                          # (n_in, n_out) -> (lw, offset in doubles)
-        self._wpool = None                                           # the device copy; replaced (never written) when the pool grows
+        self._wpool = None                                           # the device copy; replaced (never written) when the pool has grown
         self._ws = None                                              # the workspace of tsnet_face_labels_boxes; replaced when a clip needs more
-        self._keep_t = []
 
-    def _stream(self) -> Optional[int]:
-        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
+    def _draw(self, kp: np.ndarray, curves: np.ndarray, h: int, w: int, bw: int):
+        """frames of one size: (edges (F,h,w) uint8, bbox (F,h,w) uint8, the two uploads)"""
+        F = kp.shape[0]
+        kd = torch.from_numpy(kp).to(self.device)
+        cd = torch.from_numpy(curves).to(self.device)
+        edges = torch.empty((F, h, w), dtype=torch.uint8, device=self.device)
+        bbox = torch.empty((F, h, w), dtype=torch.uint8, device=self.device)
+        call(self.lib, "tsnet_raster_face", kd.data_ptr(), cd.data_ptr(), F, h, w, bw, edges.data_ptr(), bbox.data_ptr(), device=self.device)
+        return edges, bbox, (kd, cd)
 
     def rasterise(self, keypoints: Sequence[np.ndarray], crop: Optional[Tuple[int, int, int, int]] = None, relative: bool = False,
                   bw: Optional[int] = None):
@@ -74,40 +121,17 @@ class FaceRasteriser:
         crop may be an (F,4) array, a crop per frame (fix_crop_pos=False, `crop_coords_clip`): every frame is drawn at its own crop's size and the
         result is (edges, bbox, crops, bw) with edges / bbox LISTS of F tensors (h_f, w_f).  bw then defaults to that of the FIRST frame's crop:
         the reference computes the brush once per clip (:302, :347).  Frames of equal size share one call of the kernels."""
-        kp = np.stack([np.asarray(k, dtype=np.float64) for k in keypoints])
-        if kp.ndim != 3 or kp.shape[1:] != (68, 2):
-            raise ValueError(f"expected F x 68 x 2 key points, got {kp.shape}")
-        if relative and crop is None:
-            raise ValueError("relative=True: key points relative to a crop need that crop")
-        if crop is not None and np.ndim(crop) == 2:
-            return self._rasterise_crops(kp, crop, relative, bw)
-        if crop is None:
-            crop = crop_coords(kp[0])
-        kp = kp.copy()
-        if not relative:
-            kp[:, :, 0] -= crop[2]                                 # read_keypoints (:497-505)
-            kp[:, :, 1] -= crop[0]
-        h, w = crop[1] - crop[0], crop[3] - crop[2]
-        if bw is None:
-            bw = max(1, h // 256)                                  # :295
-        F = kp.shape[0]
-        kp = np.ascontiguousarray(kp)
-        # interp_points' Levenberg-Marquardt fits run on the host (34 per frame, microseconds each; csrc/lmfit.hpp reproduces scipy's
-        # curve_fit to the last bit); the device samples and draws the fitted curves
-        curves = np.empty((F, 34, 8), dtype=np.float64)
-        rc = self.lib.tsnet_fit_face_curves(kp.ctypes.data, F, curves.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"tsnet_fit_face_curves failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        kd = torch.from_numpy(kp).to(self.device)
-        cd = torch.from_numpy(curves).to(self.device)
-        edges = torch.empty((F, h, w), dtype=torch.uint8, device=self.device)
-        bbox = torch.empty((F, h, w), dtype=torch.uint8, device=self.device)
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = self.lib.tsnet_raster_face(kd.data_ptr(), cd.data_ptr(), F, h, w, bw, edges.data_ptr(), bbox.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"tsnet_raster_face failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep = (kd, cd)
+        kp, crop, bw, curves = _face_points(keypoints, crop, relative, bw, self.lib)
+        if np.ndim(crop) == 2:                                       # the frames of every size together, and back into frame order
+            edges, bbox, held = [None] * len(kp), [None] * len(kp), []
+            for (h, w), idx in self._size_groups(crop).items():
+                e, b, up = self._draw(kp[idx], curves[idx], h, w, bw)
+                held.append(up)
+                for j, f in enumerate(idx):
+                    edges[f], bbox[f] = e[j], b[j]
+        else:
+            edges, bbox, held = self._draw(kp, curves, crop[1] - crop[0], crop[3] - crop[2], bw)
+        self._held["rasterise"] = {"uploads": held}
         return edges, bbox, crop, bw
 
     @staticmethod
@@ -118,38 +142,13 @@ class FaceRasteriser:
             groups.setdefault((int(c[1] - c[0]), int(c[3] - c[2])), []).append(f)
         return groups
 
-    def _rasterise_crops(self, kp: np.ndarray, crops, relative: bool, bw: Optional[int]):
-        """a crop per frame: the frames of every size go through `rasterise` together and back into frame order"""
-        crops = np.asarray(crops).astype(np.int64)
-        F = kp.shape[0]
-        if crops.shape != (F, 4):
-            raise ValueError(f"expected ({F},4) crops for {F} frames, got {crops.shape}")
-        if bw is None:
-            bw = max(1, int(crops[0, 1] - crops[0, 0]) // 256)      # the first frame's, for the whole clip (:302, :347)
-        kp = kp.copy()
-        if not relative:
-            kp[:, :, 0] -= crops[:, 2, None]                        # read_keypoints(path, None) (:499-507): each frame by its own crop
-            kp[:, :, 1] -= crops[:, 0, None]
-        edges, bbox, keep = [None] * F, [None] * F, []
-        for (h, w), idx in self._size_groups(crops).items():
-            e, b, _, _ = self.rasterise(kp[idx], (0, h, 0, w), relative=True, bw=bw)
-            keep.append(self._keep)
-            for j, f in enumerate(idx):
-                edges[f], bbox[f] = e[j], b[j]
-        self._keep = keep
-        return edges, bbox, crops, bw
-
     def vl2ch(self, labels: torch.Tensor, num_classes: int) -> torch.Tensor:
         """utils/misc.py vl2ch (:50-67): (B,H,W) class indices -> (B,num_classes,H,W) one-hot float32."""
         lab = labels.to(self.device, dtype=torch.float32).contiguous()
         B, H, W = lab.shape
         out = torch.empty((B, num_classes, H, W), dtype=torch.float32, device=self.device)
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = self.lib.tsnet_vl2ch(lab.data_ptr(), B, H * W, num_classes, out.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"tsnet_vl2ch failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep_l = lab
+        call(self.lib, "tsnet_vl2ch", lab.data_ptr(), B, H * W, num_classes, out.data_ptr(), device=self.device)
+        self._held["vl2ch"] = {"labels": lab}
         return out
 
     def clip_labels(self, keypoints: Sequence[np.ndarray], size: Tuple[int, int] = (256, 256), crop=None, relative: bool = False,
@@ -168,12 +167,18 @@ class FaceRasteriser:
         more.  One stream at a time per rasteriser."""
         from .demo import resize_label
         if crop is not None and np.ndim(crop) == 2:
-            return self._clip_labels_crops(keypoints, size, crop, relative, compact, bw)
-        edges, bbox, crop, _ = self.rasterise(keypoints, crop, relative, bw)
-        cls, box = resize_label(edges, size, lib=self.lib), resize_label(bbox, size, lib=self.lib)
-        if compact:
-            return cls.to(torch.uint8), box.to(torch.uint8), crop          # exact: the maps hold 0 / 1
-        return self.vl2ch(cls, 2), box, crop
+            cls, box, crop, held = self._clip_labels_crops(keypoints, size, crop, relative, compact, bw)
+        else:
+            edges, bbox, crop, _ = self.rasterise(keypoints, crop, relative, bw)
+            cls, box = resize_label(edges, size, lib=self.lib), resize_label(bbox, size, lib=self.lib)
+            held = {"rasterise": self._held["rasterise"]}
+            if compact:
+                cls, box = cls.to(torch.uint8), box.to(torch.uint8)          # exact: the maps hold 0 / 1
+        if not compact:
+            cls = self.vl2ch(cls, 2)
+            held["vl2ch"] = self._held["vl2ch"]
+        self._held["clip_labels"] = held
+        return cls, box, crop
 
     def _aa_axis(self, n_in: int, n_out: int) -> Tuple[int, int]:
         """(lw, offset in doubles) of an axis' Gaussian half-kernel (demo._aa_kernel) in the pool, appended on first sight; (-1, 0) for an axis
@@ -187,7 +192,6 @@ class FaceRasteriser:
             else:
                 self._wpool_at[key] = (lw, len(self._wpool_host))
                 self._wpool_host = np.concatenate([self._wpool_host, w])
-                self._wpool = None
         return self._wpool_at[key]
 
     def _label_descriptors(self, crops: np.ndarray, size: Tuple[int, int]):
@@ -208,62 +212,30 @@ class FaceRasteriser:
         return np.array(rows, dtype=np.int32).reshape(-1, 8), off
 
     def _clip_labels_crops(self, keypoints, size, crops, relative: bool, compact: bool, bw: Optional[int]):
-        """clip_labels with a crop per frame: one call of tsnet_face_labels_boxes[_u8]"""
-        kp = np.stack([np.asarray(k, dtype=np.float64) for k in keypoints])
-        if kp.ndim != 3 or kp.shape[1:] != (68, 2):
-            raise ValueError(f"expected F x 68 x 2 key points, got {kp.shape}")
-        crops = np.asarray(crops).astype(np.int64)
+        """clip_labels with a crop per frame, before vl2ch: one call of tsnet_face_labels_boxes[_u8] -> (class map, mask, crops, what it holds)"""
+        kp, crops, bw, curves = _face_points(keypoints, crops, relative, bw, self.lib)
         F = kp.shape[0]
-        if crops.shape != (F, 4):
-            raise ValueError(f"expected ({F},4) crops for {F} frames, got {crops.shape}")
-        if bw is None:
-            bw = max(1, int(crops[0, 1] - crops[0, 0]) // 256)      # the first frame's, for the whole clip (:302, :347)
-        kp = kp.copy()
-        if not relative:
-            kp[:, :, 0] -= crops[:, 2, None]                        # read_keypoints(path, None) (:499-507): each frame by its own crop
-            kp[:, :, 1] -= crops[:, 0, None]
-        kp = np.ascontiguousarray(kp)
         desc, ws_len = self._label_descriptors(crops, size)
-        curves = np.empty((F, 34, 8), dtype=np.float64)              # the fits stay on the host, as in `rasterise`
-        rc = self.lib.tsnet_fit_face_curves(kp.ctypes.data, F, curves.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"tsnet_fit_face_curves failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
         # one upload: key points | curves | descriptors (multiples of 8 bytes, so each part is aligned for its type)
         up = torch.from_numpy(np.concatenate([kp.reshape(-1).view(np.uint8), curves.reshape(-1).view(np.uint8), desc.reshape(-1).view(np.uint8)])).to(self.device)
         kd = up.data_ptr()
         cd, dd = kd + kp.nbytes, kd + kp.nbytes + curves.nbytes
-        old = []
-        if self._wpool is None:                                      # grown: a new device copy; the old one may still be read by an enqueued kernel
-            old.append(self._keep_t[1] if self._keep_t else None)
-            self._wpool = torch.from_numpy(self._wpool_host.copy()).to(self.device)
+        old_pool = old_ws = None                                     # what this call replaces: an enqueued kernel may still read it
+        if self._wpool is None or self._wpool.numel() != len(self._wpool_host):
+            old_pool, self._wpool = self._wpool, torch.from_numpy(self._wpool_host.copy()).to(self.device)
         if self._ws is None or self._ws.numel() < ws_len:
-            old.append(self._ws)
-            self._ws = torch.empty(ws_len, dtype=torch.uint8, device=self.device)
+            old_ws, self._ws = self._ws, torch.empty(ws_len, dtype=torch.uint8, device=self.device)
         OH, OW = int(size[0]), int(size[1])
         dtype = torch.uint8 if compact else torch.float32
         cls = torch.empty((F, OH, OW), dtype=dtype, device=self.device)
         box = torch.empty((F, OH, OW), dtype=dtype, device=self.device)
-        fn = self.lib.tsnet_face_labels_boxes_u8 if compact else self.lib.tsnet_face_labels_boxes
-        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-        with ctx:
-            rc = fn(kd, cd, F, desc.ctypes.data, dd, self._wpool.data_ptr() if self._wpool.numel() else None, self._wpool.numel(), int(bw),
-                    self._ws.data_ptr(), self._ws.numel(), OH, OW, cls.data_ptr(), box.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"tsnet_face_labels_boxes{'_u8' if compact else ''} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
-        self._keep_t = [up, self._wpool, self._ws] + old            # alive until the stream has consumed them
-        if compact:
-            return cls, box, crops
-        return self.vl2ch(cls, 2), box, crops
+        call(self.lib, "tsnet_face_labels_boxes_u8" if compact else "tsnet_face_labels_boxes", kd, cd, F, desc.ctypes.data, dd,
+             self._wpool.data_ptr() if self._wpool.numel() else None, self._wpool.numel(), int(bw), self._ws.data_ptr(), self._ws.numel(),
+             OH, OW, cls.data_ptr(), box.data_ptr(), device=self.device)
+        return cls, box, crops, {"upload": up, "pool": self._wpool, "workspace": self._ws, "old_pool": old_pool, "old_workspace": old_ws}
 
 
 # ------------------------------------------------------------------------------------------------- cross-identity face pairs
-def _clip_array(kps, what: str) -> np.ndarray:
-    kp = np.ascontiguousarray(np.stack([np.asarray(k, dtype=np.float64) for k in kps]))
-    if kp.ndim != 3 or kp.shape[1:] != (68, 2):
-        raise ValueError(f"{what}: expected F x 68 x 2 key points, got {kp.shape}")
-    return kp
-
-
 class FaceAdapter:
     """FaceDatasetTest.normalize_faces (dataset_video_face.py:411-454): `fit` measures the subject clip's face proportions (is_ref=True, :335),
     `apply` re-scales every mirror-symmetric landmark group of a driving clip to them (is_ref=False, :355).  Key points are relative to their
@@ -286,9 +258,7 @@ class FaceAdapter:
     def fit(self, subject_kps_rel) -> "FaceAdapter":
         kp = _clip_array(subject_kps_rel, "FaceAdapter.fit")
         stats = np.empty(77, dtype=np.float64)
-        rc = self.lib.tsnet_face_adapt_stats(kp.ctypes.data, kp.shape[0], stats.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"tsnet_face_adapt_stats failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        call(self.lib, "tsnet_face_adapt_stats", kp.ctypes.data, kp.shape[0], stats.ctypes.data)
         self._stats = stats
         return self
 
@@ -296,10 +266,8 @@ class FaceAdapter:
         """-> (F,68,2) float64, a new array: the driving clip with the subject's proportions"""
         if self._stats is None:
             raise RuntimeError("FaceAdapter: fit() a subject clip first")
-        kp = _clip_array(driving_kps_rel, "FaceAdapter.apply").copy()
-        rc = self.lib.tsnet_face_adapt_apply(self._stats.ctypes.data, kp.ctypes.data, kp.shape[0])
-        if rc != 0:
-            raise RuntimeError(f"tsnet_face_adapt_apply failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
+        kp = _clip_array(driving_kps_rel, "FaceAdapter.apply")
+        call(self.lib, "tsnet_face_adapt_apply", self._stats.ctypes.data, kp.ctypes.data, kp.shape[0])
         return kp
 
 
@@ -311,9 +279,7 @@ def smooth_keypoints(kps, lib=None) -> np.ndarray:
     if kp.ndim != 3 or kp.shape[2] != 2:
         raise ValueError(f"expected F x P x 2 key points, got {kp.shape}")
     out = np.empty_like(kp)
-    rc = lib.tsnet_smooth_keypoints(kp.ctypes.data, kp.shape[0], kp.shape[1], out.ctypes.data)
-    if rc != 0:
-        raise RuntimeError(f"tsnet_smooth_keypoints failed ({rc}): {lib.tsnet_op_last_error().decode()}")
+    call(lib, "tsnet_smooth_keypoints", kp.ctypes.data, kp.shape[0], kp.shape[1], out.ctypes.data)
     return out
 
 
@@ -326,20 +292,10 @@ def face_driving_keypoints(subject_kps, driving_kps, lib=None, fix_crop_pos: boo
     `FaceRasteriser.rasterise(points, crop, relative=True)` takes.
     fix_crop_pos=False: every frame of each clip is made relative to its OWN crop (read_keypoints(path, None), :306-308, :351-353, :499-507);
     adaptation and smoothing then run as above.  Returns (points, crops (F,4) of the driving frames, bw of the FIRST driving frame (:347))."""
-    sub, drv = _clip_array(subject_kps, "subject").copy(), _clip_array(driving_kps, "driving").copy()
-    if not fix_crop_pos:
-        crops = crop_coords_clip(drv)
-        for kp, c in ((sub, crop_coords_clip(sub)), (drv, crops)):
-            kp[:, :, 0] -= c[:, 2, None]
-            kp[:, :, 1] -= c[:, 0, None]
-        points = smooth_keypoints(FaceAdapter(lib).fit(sub).apply(drv), lib)
-        return points, crops, max(1, int(crops[0, 1] - crops[0, 0]) // 256)
-    sub_crop, crop = crop_coords(sub[0]), crop_coords(drv[0])
-    for kp, c in ((sub, sub_crop), (drv, crop)):
-        kp[:, :, 0] -= c[2]                                        # read_keypoints (:497-505)
-        kp[:, :, 1] -= c[0]
-    points = smooth_keypoints(FaceAdapter(lib).fit(sub).apply(drv), lib)
-    return points, crop, max(1, (crop[1] - crop[0]) // 256)       # :347
+    sub, drv = _clip_array(subject_kps, "subject"), _clip_array(driving_kps, "driving")
+    sub = _face_points(sub, None if fix_crop_pos else crop_coords_clip(sub))[0]
+    drv, crop, bw, _ = _face_points(drv, None if fix_crop_pos else crop_coords_clip(drv))
+    return smooth_keypoints(FaceAdapter(lib).fit(sub).apply(drv), lib), crop, bw
 
 
 # ---------------------------------------------------------------------------------------------------------------- pose clips
@@ -415,25 +371,10 @@ def nearest_table(n_in: int, n_out: int) -> np.ndarray:
     return tab
 
 
-class PoseRasteriser:
+class PoseRasteriser(Wrapper):
     """Class-index skeleton labels, bounding-box masks and the model's 256 x 256 label tensors of a pose clip on `device`.
 
     lib: tests pass the CPU emulation build; product code leaves it None (the in-tree HIP library, no fallback)."""
-
-    def __init__(self, device, lib=None):
-        self.lib = lib if lib is not None else _lib.load()
-        self.device = torch.device(device)
-        self._keep = []
-
-    def _stream(self) -> Optional[int]:
-        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
-
-    def _ctx(self):
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else _Null()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self.lib.tsnet_op_last_error().decode()}")
 
     def rasterise(self, points: Sequence[np.ndarray], size: Tuple[int, int], window: Optional[Tuple[int, int, int, int]] = None,
                   basic_point_only: bool = False, remove_face_labels: bool = False) -> torch.Tensor:
@@ -450,14 +391,12 @@ class PoseRasteriser:
         pts = np.ascontiguousarray(pts)
         flags = (1 if basic_point_only else 0) | (2 if remove_face_labels else 0)
         curves = np.empty((F, 118, 8), dtype=np.float64)              # every stroke's line, fitted on the host as the reference fits it (csrc/lmfit.hpp)
-        self._check(self.lib.tsnet_fit_pose_curves(pts.ctypes.data, F, flags, curves.ctypes.data), "tsnet_fit_pose_curves")
+        call(self.lib, "tsnet_fit_pose_curves", pts.ctypes.data, F, flags, curves.ctypes.data)
         pd = torch.from_numpy(pts).to(self.device)
         cd = torch.from_numpy(curves).to(self.device)
         buf = torch.empty((n + 3) // 4 * 4, dtype=torch.uint8, device=self.device)      # whole 32-bit words: the kernel raises bytes with word atomics
-        with self._ctx():
-            rc = self.lib.tsnet_raster_pose(pd.data_ptr(), cd.data_ptr(), F, h, w, xs, ys, xe, ye, flags, buf.data_ptr(), self._stream())
-        self._check(rc, "tsnet_raster_pose")
-        self._keep = [pd, cd, buf]
+        call(self.lib, "tsnet_raster_pose", pd.data_ptr(), cd.data_ptr(), F, h, w, xs, ys, xe, ye, flags, buf.data_ptr(), device=self.device)
+        self._held["rasterise"] = {"points": pd, "curves": cd}
         return buf[:n].view(F, ye - ys, xe - xs)
 
     def bbox(self, labels: torch.Tensor) -> torch.Tensor:
@@ -465,10 +404,8 @@ class PoseRasteriser:
         lab = labels.to(self.device).contiguous()
         F, h, w = lab.shape
         out = torch.empty_like(lab)
-        with self._ctx():
-            rc = self.lib.tsnet_label_bbox(lab.data_ptr(), F, h, w, out.data_ptr(), self._stream())
-        self._check(rc, "tsnet_label_bbox")
-        self._keep += [lab]
+        call(self.lib, "tsnet_label_bbox", lab.data_ptr(), F, h, w, out.data_ptr(), device=self.device)
+        self._held["bbox"] = {"labels": lab}
         return out
 
     def to_square(self, maps: torch.Tensor, img_size: Tuple[int, int] = (128, 256), binarise: bool = False) -> torch.Tensor:
@@ -481,11 +418,9 @@ class PoseRasteriser:
         yt = torch.from_numpy(nearest_table(h, oh)).to(self.device)
         xt = torch.from_numpy(nearest_table(w, ow)).to(self.device)
         out = torch.empty((F, S, S), dtype=torch.float32, device=self.device)
-        with self._ctx():
-            rc = self.lib.tsnet_resize_pad(m.data_ptr(), F, h, w, yt.data_ptr(), xt.data_ptr(), oh, ow, (S - oh) // 2, (S - ow) // 2, S, S,
-                                           int(binarise), out.data_ptr(), self._stream())
-        self._check(rc, "tsnet_resize_pad")
-        self._keep += [m, yt, xt]
+        call(self.lib, "tsnet_resize_pad", m.data_ptr(), F, h, w, yt.data_ptr(), xt.data_ptr(), oh, ow, (S - oh) // 2, (S - ow) // 2, S, S,
+             int(binarise), out.data_ptr(), device=self.device)
+        self._held["to_square"] = {"maps": m, "rows": yt, "columns": xt}
         return out
 
     def clip_labels(self, points: Sequence[np.ndarray], size: Tuple[int, int], window=None, img_size=(128, 256), compact: bool = False):
@@ -497,15 +432,12 @@ class PoseRasteriser:
             window = pose_crop_coords(points[0], size)
         cls = self.rasterise(points, size, window)
         box = self.bbox(cls)
-        cls, box = self.to_square(cls, img_size), self.to_square(box, img_size, binarise=True)
+        held = {"rasterise": self._held["rasterise"], "bbox": self._held["bbox"]}
+        cls = self.to_square(cls, img_size)
+        held["to_square(labels)"] = self._held["to_square"]
+        box = self.to_square(box, img_size, binarise=True)
+        held["to_square(bbox)"] = self._held["to_square"]
+        self._held["clip_labels"] = held
         if compact:
             cls, box = cls.to(torch.uint8), box.to(torch.uint8)             # exact: small integers
         return cls, box, window
-
-
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
