@@ -228,6 +228,8 @@ def refusals(lib, dev):
         msg = lib.tsnet_op_last_error().decode()
         assert rc == oc.TSNET_ERR_ARG and msg, (nprod, kernel, tile, rc, msg)
         assert torch.isnan(y).all()
+        if nprod not in (1, 3, 4, NPROD_F16):       # the entry's own check, ahead of the layer's packing and of the planner's "conv: ..." refusal
+            assert msg.startswith("conv2d op: nprod"), (nprod, msg)
         msgs.append(msg)
     return msgs
 

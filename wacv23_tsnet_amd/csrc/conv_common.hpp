@@ -193,6 +193,13 @@ __device__ __forceinline__ unsigned cvt_pk_one(float a, float b) {
     else return TSNET_CVT_PK_BF16(a, b);
 }
 
+// the sum of v over the 64 lanes of a wave, in every lane (butterfly: the same association in every lane)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // max |v| of the workgroup's values -> ONE atomic per workgroup (atomics on one address serialise at ~12 ns each; non-negative
 // floats order like their bit patterns, and a max is order-independent: deterministic).  Every thread of the workgroup must call it.
 __device__ __forceinline__ void tsnet_publish_amax(unsigned* slot, float m) {
@@ -471,6 +478,22 @@ __device__ __forceinline__ float up2_lerp(float a, float b, float w0, float w1) 
 // The fused staging evaluates the three lerps itself -- two vertical neighbours share the horizontal pair.
 __device__ __forceinline__ float up2_blend(float v00, float v01, float v10, float v11, float wx0, float wx1, float wy0, float wy1) {
     return up2_lerp(up2_lerp(v00, v01, wx0, wx1), up2_lerp(v10, v11, wx0, wx1), wy0, wy1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Lane arithmetic on four channels, for the kernels between the convolutions (norm_elementwise.hpp, flow_warp.hpp): one fp32 operation per
+// channel each, so a kernel reads as the formula it evaluates
+__device__ __forceinline__ float4 add4(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 mul4(const float4& a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
+__device__ __forceinline__ float4 div4(const float4& a, float s) { return make_float4(a.x / s, a.y / s, a.z / s, a.w / s); }
+__device__ __forceinline__ float4 relu4(const float4& a) {
+    return make_float4(a.x > 0.f ? a.x : 0.f, a.y > 0.f ? a.y : 0.f, a.z > 0.f ? a.z : 0.f, a.w > 0.f ? a.w : 0.f);
+}
+__device__ __forceinline__ float4 fma4(const float4& a, const float4& b, const float4& c) {      // a * b + c, fused
+    return make_float4(__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y), __builtin_fmaf(a.z, b.z, c.z), __builtin_fmaf(a.w, b.w, c.w));
+}
+__device__ __forceinline__ float4 fma4(const float4& a, float s, const float4& c) {              // a * s + c, fused
+    return make_float4(__builtin_fmaf(a.x, s, c.x), __builtin_fmaf(a.y, s, c.y), __builtin_fmaf(a.z, s, c.z), __builtin_fmaf(a.w, s, c.w));
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -370,9 +370,9 @@ void tsnet_engine::alloc_all(hipStream_t s) {
     float* slot_f = nullptr;
     want(&slot_f, NB);                                                       // the slot table (ints)
     if (P >= 2048 && P % 64 == 0) want(&flow_part, 2 * flowp_part_words((int)NB, P, flowp_slices(h, w)));   // flow_kernel_p: one softmax state per (image, target tile, slice, column), 8-byte words
-    // InstanceNorm partials (doubles = 2 floats each): the stand-alone pass N*64*C*2, a conv epilogue N * tiles-per-image * Cout * 2
-    // with tiles of at least 64 positions (ceil for ragged images), per lane
-    size_t part_doubles = NB * 64 * 2 * C * 2;
+    // InstanceNorm partials (doubles = 2 floats each): the stand-alone pass (2 C channels at most), a conv epilogue N * tiles-per-image *
+    // Cout * 2 with tiles of at least 64 positions (ceil for ragged images), per lane
+    size_t part_doubles = stat_scratch_doubles(NB, 2 * C);
     for (int l = 0; l <= cfg.n_downsampling; ++l) {
         const size_t hw = (size_t)(H >> l) * (W >> l), tpi = (hw + 63) / 64;
         part_doubles = std::max(part_doubles, stat_part_doubles(NB, tpi, (size_t)std::max(cfg.ngf << l, 2 * C)));

@@ -27,6 +27,12 @@ thread_local std::string g_op_error;    // the last refusal of a handle-free ent
 
 struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct WeightError : std::runtime_error { using std::runtime_error::runtime_error; };
+// f(), with a refusal of the planner or of a launcher (std::invalid_argument: conv_plan.hpp and the *_launch.cpp units know no ArgError)
+// turned into the caller's ArgError, message kept
+template <typename F>
+inline auto arg_checked(F&& f) -> decltype(f()) {
+    try { return f(); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+}
 
 inline void check_launch(const char* what) {
     hipError_t e = hipGetLastError();

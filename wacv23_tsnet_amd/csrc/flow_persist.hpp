@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include "conv_common.hpp"
 #include "flow_args.hpp"
+#include "flow_steps.hpp"
 
 namespace tsnet {
 
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
     const int b = gb % a.B, g = gb / a.B;
     const int tb0 = t * NT;
 
-    {   // the workgroup's target fragments: one contiguous region of the plane buffer
+    {   // the workgroup's target fragments: one contiguous region of the plane buffer (not shared with flow_kernel: flow_steps.hpp)
         const F4* gp = reinterpret_cast<const F4*>(a.tq + ((size_t)(b * (a.P >> 5) + tb0) * KC) * 1024);
         F4* d = reinterpret_cast<F4*>(smem_raw);
         const int cnt = TBYTES / 16;
@@ -86,8 +87,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int tt = (tb0 + j) * 32 + li;
-        const int ty = tt / a.w, tx = tt - ty * a.w;
-        const float m = a.tar_bbox[(size_t)b * a.H * a.W + (size_t)(ty * a.sy) * a.W + tx * a.sx];
+        const float m = flow_mask_at(a.tar_bbox, b, a, tt);
         mtu[j] = m * kFlowUnscale; omtu[j] = (1.0f - m) * kFlowUnscale;
     }
     const float inv_w = 1.0f / (float)a.w;
@@ -108,12 +108,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
         const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.sq) + ((size_t)img * (a.P >> 5) * KC) * 2048 + lane * 16;
         for (int sp = sp_base + wave; sp < sp_base + nps; sp += kFlowWaves) {
             // this lane's share of the pair's source mask (F.interpolate(nearest)): source sp * 64 + lane; lands under the MFMA sweep
-            float msl;
-            {
-                const int p = sp * 64 + lane;
-                const int py = p / a.w, px = p - py * a.w;
-                msl = sb[(size_t)(py * a.sy) * a.W + px * a.sx];
-            }
+            const float msl = flow_mask_at(sb, 0, a, sp * 64 + lane);
             const unsigned char* ap = sbase + (size_t)(sp * 2) * KC * 2048;     // source blocks 2 sp, 2 sp + 1: KC * 2 KiB each
             f32x16 acc[2][NT];
 #pragma unroll
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
                         acc[i][j] = TSNET_MFMA_F16(af[sa][u][i][0], bf[sbt][j][0], acc[i][j]);      // hi * hi
                     }
             };
-            // groups of two steps; source fragments two groups ahead (three register sets), as in flow_kernel
+            // groups of two steps; source fragments two groups ahead (three register sets), as in flow_kernel (not shared: the figures are there)
             const int ngrp = KC >> 1;
             load_a(0, 0);
             load_a(1, ngrp > 1 ? 1 : 0);
@@ -202,7 +197,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
                     }
                 }
             TSNET_WAVE_SYNC();                // (emulator: every lane has read the row before the next pair overwrites it)
-            float m_new[NT];
+            float m_new[NT];                  // (the rescale and the three merges below: not shared with flow_kernel, flow_steps.hpp)
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 m_new[j] = mx[j] > m_run[j] ? mx[j] : m_run[j];
@@ -273,8 +268,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel_p(FlowArgs a) {
         if (a.G > 1) {
             arrived = 0.f;
             if (lane == 0) arrived = (float)__hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) arrived += __shfl_xor(arrived, off);
+            arrived = wave_sum(arrived);        // lane 0's value to every lane (the others hold 0)
         }
         if ((int)arrived == a.G - 1) {
             for (int s_idx = 0; s_idx < a.K; ++s_idx) {

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "conv_common.hpp"
 #include "flow_args.hpp"
+#include "flow_steps.hpp"
 
 namespace tsnet {
 
@@ -36,6 +37,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
     const int tb0 = (item - n * tiles) * NT;
 
     // the workgroup's target fragments: one contiguous region of the plane buffer
+    // (not shared with flow_kernel_p: as a function the copy loop's back branch changes sense in both kernels -- flow_steps.hpp)
     {
         const F4* g = reinterpret_cast<const F4*>(a.tq + ((size_t)(b * (Ppad >> 5) + tb0) * KC) * 1024);
         F4* d = reinterpret_cast<F4*>(smem_raw);
@@ -50,14 +52,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
     }
     const int img = a.slot[n];                                           // the (source, frame) pair's image of the source planes and masks
     const float* sb = a.src_bbox + (size_t)img * a.H * a.W;
-    for (int p = tid; p < Ppad; p += NTH) {
-        float v = 0.f;
-        if (p < a.P) {
-            const int py = p / a.w, px = p - py * a.w;
-            v = sb[(size_t)(py * a.sy) * a.W + px * a.sx];               // F.interpolate(nearest): src = dst*scale
-        }
-        sMs[p] = v;
-    }
+    for (int p = tid; p < Ppad; p += NTH) sMs[p] = p < a.P ? flow_mask_at(sb, 0, a, p) : 0.f;
     for (int p = tid; p < a.w; p += NTH) sGx[p] = a.gx[p];
     for (int p = tid; p < a.h; p += NTH) sGy[p] = a.gy[p];
     __syncthreads();
@@ -66,11 +61,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int t = (tb0 + j) * 32 + li;                                // this lane's target column of block j
-        mt[j] = 0.f;
-        if (t < a.P) {
-            const int ty = t / a.w, tx = t - ty * a.w;
-            mt[j] = a.tar_bbox[(size_t)b * a.H * a.W + (size_t)(ty * a.sy) * a.W + tx * a.sx];
-        }
+        mt[j] = t < a.P ? flow_mask_at(a.tar_bbox, b, a, t) : 0.f;
     }
     const float inv_w = 1.0f / (float)a.w;
 
@@ -82,6 +73,9 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
     const int npair = Ppad >> 6;
     for (int sp = wave; sp < npair; sp += kFlowWaves) {
         const unsigned char* ap = sbase + (size_t)(sp * 2) * KC * 2048;  // source blocks 2 sp, 2 sp + 1: KC * 2 KiB each
+        // The pair sweep, spelled here and in flow_kernel_p (not shared: as flow_pair_sweep<NT>(ap, tbase, KC, acc) it moved all three
+        // kernels -- flow_kernel<1> 143 -> 166 VGPRs, 2843 -> 2978 instructions; returning the accumulators in a struct <1> 2843 -> 2842,
+        // <2> 3593 -> 3603, flow_kernel_p 2919 -> 2928; as a functor holding the register sets <1> 2843 -> 2841, <2> 3593 -> 3602)
         f32x16 acc[2][NT];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -154,7 +148,7 @@ __global__ __launch_bounds__(64 * kFlowWaves) void flow_kernel(FlowArgs a) {
                     mx[j] = lg > mx[j] ? lg : mx[j];
                 }
             }
-        float m_new[NT];
+        float m_new[NT];                                                 // (the rescale and the merge below: not shared, flow_steps.hpp)
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             m_new[j] = mx[j] > m_run[j] ? mx[j] : m_run[j];

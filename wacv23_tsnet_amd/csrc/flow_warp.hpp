@@ -45,8 +45,7 @@ __global__ __launch_bounds__(256) void l2norm_split_kernel(const float* __restri
         const float4 v = *reinterpret_cast<const float4*>(px + c);
         ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    ss = wave_sum(ss);
     float nrm = sqrtf(ss);
     if (nrm < 1e-12f) nrm = 1e-12f;
     unsigned short* dst = q + ((size_t)(n * (Ppad >> 5) + (p >> 5)) * KC) * 1024 + (p & 31) * 8;
@@ -68,6 +67,25 @@ __global__ __launch_bounds__(256) void l2norm_split_kernel(const float* __restri
     }
 }
 
+// F.grid_sample(bilinear, zeros, align_corners=False) at the normalised position (gx, gy) of a w x h map: the four neighbours, their
+// weights and whether each column / row lies inside the map.  For warp_mean_kernel and patch_warp_kernel (train_extras.hpp).
+struct GridTaps {
+    int x0, y0, x1, y1;
+    float wnw, wne, wsw, wse;
+    bool xin0, xin1, yin0, yin1;
+};
+__device__ __forceinline__ GridTaps grid_sample_taps(float gx, float gy, int w, int h) {
+    GridTaps t;
+    const float ix = ((gx + 1.f) * w - 1.f) / 2.f;      // grid_sampler_unnormalize, align_corners=False
+    const float iy = ((gy + 1.f) * h - 1.f) / 2.f;
+    const float fx = floorf(ix), fy = floorf(iy);
+    t.x0 = (int)fx; t.y0 = (int)fy; t.x1 = t.x0 + 1; t.y1 = t.y0 + 1;
+    t.wnw = (t.x1 - ix) * (t.y1 - iy); t.wne = (ix - t.x0) * (t.y1 - iy);
+    t.wsw = (t.x1 - ix) * (iy - t.y0); t.wse = (ix - t.x0) * (iy - t.y0);
+    t.xin0 = t.x0 >= 0 && t.x0 < w; t.xin1 = t.x1 >= 0 && t.x1 < w;
+    t.yin0 = t.y0 >= 0 && t.y0 < h; t.yin1 = t.y1 >= 0 && t.y1 < h;
+    return t;
+}
 
 // grid_sample(bilinear, zeros, align_corners=False) of the UN-normalised source features at the
 // flow, fused with the mean over sources.  NHWC makes every neighbour a contiguous C-float row:
@@ -94,28 +112,16 @@ __global__ __launch_bounds__(256) void warp_mean_kernel(WarpArgs a) {
             const int n = s * a.B + b;
             const float gx = a.flow[((size_t)n * P + p) * 2 + 0];
             const float gy = a.flow[((size_t)n * P + p) * 2 + 1];
-            const float ix = ((gx + 1.f) * a.w - 1.f) / 2.f;    // grid_sampler_unnormalize, align_corners=False
-            const float iy = ((gy + 1.f) * a.h - 1.f) / 2.f;
-            const float fx = floorf(ix), fy = floorf(iy);
-            const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-            const float wnw = (x1 - ix) * (y1 - iy), wne = (ix - x0) * (y1 - iy);
-            const float wsw = (x1 - ix) * (iy - y0), wse = (ix - x0) * (iy - y0);
+            const GridTaps t = grid_sample_taps(gx, gy, a.w, a.h);
             const float* base = a.src + ((size_t)a.slot[n] * P) * a.C + c;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            const bool xin0 = x0 >= 0 && x0 < a.w, xin1 = x1 >= 0 && x1 < a.w;
-            const bool yin0 = y0 >= 0 && y0 < a.h, yin1 = y1 >= 0 && y1 < a.h;
-            if (yin0 && xin0) { const float4 q = *reinterpret_cast<const float4*>(base + ((size_t)y0 * a.w + x0) * a.C);
-                v.x = q.x * wnw; v.y = q.y * wnw; v.z = q.z * wnw; v.w = q.w * wnw; }
-            if (yin0 && xin1) { const float4 q = *reinterpret_cast<const float4*>(base + ((size_t)y0 * a.w + x1) * a.C);
-                v.x = __builtin_fmaf(q.x, wne, v.x); v.y = __builtin_fmaf(q.y, wne, v.y); v.z = __builtin_fmaf(q.z, wne, v.z); v.w = __builtin_fmaf(q.w, wne, v.w); }
-            if (yin1 && xin0) { const float4 q = *reinterpret_cast<const float4*>(base + ((size_t)y1 * a.w + x0) * a.C);
-                v.x = __builtin_fmaf(q.x, wsw, v.x); v.y = __builtin_fmaf(q.y, wsw, v.y); v.z = __builtin_fmaf(q.z, wsw, v.z); v.w = __builtin_fmaf(q.w, wsw, v.w); }
-            if (yin1 && xin1) { const float4 q = *reinterpret_cast<const float4*>(base + ((size_t)y1 * a.w + x1) * a.C);
-                v.x = __builtin_fmaf(q.x, wse, v.x); v.y = __builtin_fmaf(q.y, wse, v.y); v.z = __builtin_fmaf(q.z, wse, v.z); v.w = __builtin_fmaf(q.w, wse, v.w); }
-            sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
+            if (t.yin0 && t.xin0) v = mul4(*reinterpret_cast<const float4*>(base + ((size_t)t.y0 * a.w + t.x0) * a.C), t.wnw);
+            if (t.yin0 && t.xin1) v = fma4(*reinterpret_cast<const float4*>(base + ((size_t)t.y0 * a.w + t.x1) * a.C), t.wne, v);
+            if (t.yin1 && t.xin0) v = fma4(*reinterpret_cast<const float4*>(base + ((size_t)t.y1 * a.w + t.x0) * a.C), t.wsw, v);
+            if (t.yin1 && t.xin1) v = fma4(*reinterpret_cast<const float4*>(base + ((size_t)t.y1 * a.w + t.x1) * a.C), t.wse, v);
+            sum = add4(sum, v);
         }
-        const float kf = (float)a.K;
-        sum.x /= kf; sum.y /= kf; sum.z /= kf; sum.w /= kf;
+        sum = div4(sum, (float)a.K);
         *reinterpret_cast<float4*>(a.out + ((size_t)b * P + p) * a.C + c) = sum;
     }
 }

@@ -66,6 +66,16 @@ struct EventPair {
         return t;
     }
 };
+// launch(0 .. n-1) between two events on s: the mean milliseconds of one launch, once the last has completed (n < 1: nothing launched, 0)
+template <typename F>
+float timed_repeats(hipStream_t s, int n, F&& launch) {
+    if (n < 1) return 0.f;
+    EventPair ev;
+    HIP_TRY(hipEventRecord(ev.a, s));
+    for (int i = 0; i < n; ++i) launch(i);
+    HIP_TRY(hipEventRecord(ev.b, s));
+    return ev.ms() / (float)n;
+}
 
 struct Timing {
     bool on = false;
@@ -238,8 +248,7 @@ void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req =
 #endif
     if (c.up2 && (c.x_bf16 || c.y_bf16 || c.in_amax)) throw ArgError("conv: the fused x2 upsample takes fp32 tensors and an a-priori operand bound");
     const ConvShape sh = conv_shape(L, c);
-    ConvPlan p;
-    try { p = plan_conv(sh, req, ctx.cus); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    const ConvPlan p = arg_checked([&] { return plan_conv(sh, req, ctx.cus); });
     ConvArgs g{};
     g.x = c.x; g.x2 = c.x2; g.in_alpha = c.alpha; g.in_beta = c.alpha ? c.beta : nullptr; g.in_relu = c.relu;
     const int sa = (bf16 || c.in_amax) ? 0 : h2_scale_log2(L.form == 1 ? 2.f * c.bound : c.bound, f16 ? 64 : 24);   // Winograd: |V| <= 2 max |x|
@@ -258,7 +267,7 @@ void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req =
     g.tpi = p.tpi; g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n; g.fin_S = p.tpi; g.xcd_gn = p.xcd_gn;
     g.w1_chunk = p.w1_chunk; g.w1_tab2 = p.w1_tab2; g.fin_counter = p.fin ? c.fin_counter : nullptr;
     TimeScope ts(ctx, c.tclass);
-    try {
+    arg_checked([&] {                                                            // (refused: a tools-build variant that is not instantiated)
         switch (p.family) {
         case ConvFamily::W1: launch_conv_w1(g, c.nprod, req.abl, ctx.stream); break;
         case ConvFamily::H2: launch_conv_h2(g, p, c.nprod, req.abl, req.opt, ctx.stream); break;
@@ -268,7 +277,7 @@ void run_conv(Ctx& ctx, const ConvLayer& L, const ConvCall& c, ConvRequest req =
         case ConvFamily::G64: launch_conv_g64(g, p, c.nprod, ctx.stream); break;
         case ConvFamily::H2R: launch_conv_h2r(g, p, c.nprod, ctx.stream); break;
         }
-    } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }      // a tools-build variant that is not instantiated
+    });
     ++g_launch_counters[p.family == ConvFamily::G64 || p.family == ConvFamily::H2R ? 1 : 0];
     if (c.tclass == TSNET_T_CONV_RES && plan_tile_code(p)) g_launch_counters[3] = plan_tile_code(p);
     check_launch("conv");
@@ -294,17 +303,20 @@ void launch_finalize(const double* part, float* alpha, float* beta, int N, int C
 
 // how the statistics kernels split an image of HW positions x C channels: S partials of rps rows each, and the grid over N images
 struct StatSplit { int S, rps; dim3 grid; };
+constexpr int kStatMaxSplits = 64;
 inline StatSplit stat_split(int N, int HW, int C) {
     const int cq = C / 4, cols = cq < 256 ? cq : 256, R = 256 / cols;
     int S = (HW + R * 8 - 1) / (R * 8);
-    if (S > 64) S = 64;
+    if (S > kStatMaxSplits) S = kStatMaxSplits;
     if (S < 1) S = 1;
     const int rps = (HW + S - 1) / S;
     S = (HW + rps - 1) / rps;
     return {S, rps, dim3(S, N, (cq + 255) / 256)};
 }
+// doubles the `part` scratch of run_stats / run_add_stats must hold, whatever HW is: every split stat_split may choose
+inline size_t stat_scratch_doubles(size_t N, size_t C) { return stat_part_doubles(N, kStatMaxSplits, C); }
 
-// InstanceNorm statistics -> (alpha, beta); `part` must hold N*64*C*2 doubles
+// InstanceNorm statistics -> (alpha, beta); `part` must hold stat_scratch_doubles(N, C) doubles
 void run_stats(Ctx& ctx, const float* x, int N, int HW, int C, double* part, float* alpha, float* beta) {
     if (C & 3) throw ArgError("instnorm: C must be a multiple of 4");
     TimeScope ts(ctx, TSNET_T_STATS);
@@ -315,7 +327,7 @@ void run_stats(Ctx& ctx, const float* x, int N, int HW, int C, double* part, flo
     launch_finalize(part, alpha, beta, N, C, sp.S, HW, ctx.stream);
 }
 
-// y[n] = x[slot[n]] + add[n % add_nmod] with the InstanceNorm statistics of y -> (alpha, beta); `part` must hold N*64*C*2 doubles; slot: device, N ints
+// y[n] = x[slot[n]] + add[n % add_nmod] with the InstanceNorm statistics of y -> (alpha, beta); `part` must hold stat_scratch_doubles(N, C) doubles; slot: device, N ints
 void run_add_stats(Ctx& ctx, const float* x, const int* slot, const float* add, int add_nmod, float* y, int N, int HW, int C, double* part, float* alpha, float* beta) {
     if (C & 3) throw ArgError("add_stats: C must be a multiple of 4");
     TimeScope ts(ctx, TSNET_T_STATS);
@@ -417,9 +429,7 @@ void run_flow(Ctx& ctx, FlowArgs a, int NB, const int* slot, int variant = 0) {
     const int G = (a.part && a.cnt && NB % a.B == 0 && NB / a.B <= 8 && variant != 1) ? flowp_plan(a.B, a.h, a.w, a.C) : 0;
     if (G) {
         a.K = NB / a.B; a.G = G; a.S = flowp_slices(a.h, a.w);
-        try {
-            launch_flow_p(a, variant, ctx.stream);
-        } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+        arg_checked([&] { launch_flow_p(a, variant, ctx.stream); });
         check_launch("flow_p");
         return;
     }
@@ -427,9 +437,7 @@ void run_flow(Ctx& ctx, FlowArgs a, int NB, const int* slot, int variant = 0) {
     const int NT = flow_lds_bytes(2, a.h, a.w, a.C) <= budget ? 2 : 1;
     const size_t lds = flow_lds_bytes(NT, a.h, a.w, a.C);
     if (lds > budget) throw ArgError("flow: feature width / position count exceed the LDS budget");
-    try {
-        launch_flow(a, NT, lds, (unsigned)(flow_ppad(a.P) / (32 * NT) * NB), ctx.stream);
-    } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    arg_checked([&] { launch_flow(a, NT, lds, (unsigned)(flow_ppad(a.P) / (32 * NT) * NB), ctx.stream); });
     check_launch("flow");
 }
 

@@ -27,45 +27,6 @@ struct StatsArgs {
     int HW, C, S, rows_per_split;
 };
 
-__global__ __launch_bounds__(256) void in_stats_partial_kernel(StatsArgs a) {
-    __shared__ double red[256 * 8];
-    const int cq_total = a.C >> 2;
-    const int cols = cq_total < 256 ? cq_total : 256;   // float4 columns handled per block
-    const int R = 256 / cols;                            // row groups
-    const int tid = threadIdx.x;
-    const int cq = tid % cols + blockIdx.z * 256;
-    const int rg = tid / cols;
-    const int n = blockIdx.y, s = blockIdx.x;
-    const int r0 = s * a.rows_per_split;
-    int r1 = r0 + a.rows_per_split;
-    if (r1 > a.HW) r1 = a.HW;
-    double sm[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0};
-    if (rg < R && cq < cq_total) {
-        const float* base = a.x + ((size_t)n * a.HW) * a.C + (size_t)cq * 4;
-        for (int r = r0 + rg; r < r1; r += R) {
-            const float4 v = *reinterpret_cast<const float4*>(base + (size_t)r * a.C);
-            sm[0] += v.x; sq[0] += (double)v.x * v.x;
-            sm[1] += v.y; sq[1] += (double)v.y * v.y;
-            sm[2] += v.z; sq[2] += (double)v.z * v.z;
-            sm[3] += v.w; sq[3] += (double)v.w * v.w;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { red[tid * 8 + e] = sm[e]; red[tid * 8 + 4 + e] = sq[e]; }
-    __syncthreads();
-    if (rg == 0 && cq < cq_total) {
-        double tsm[4] = {0, 0, 0, 0}, tsq[4] = {0, 0, 0, 0};
-        for (int g = 0; g < R; ++g) {
-            const int t = g * cols + tid;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { tsm[e] += red[t * 8 + e]; tsq[e] += red[t * 8 + 4 + e]; }
-        }
-        double* o = a.part + (((size_t)n * a.S + s) * a.C + (size_t)cq * 4) * 2;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { o[e * 2] = tsm[e]; o[e * 2 + 1] = tsq[e]; }
-    }
-}
-
 // The same reduction fused with an addition: y[n] = x[slot[n]] + add[n % add_nmod], statistics of y.  FuseNet's first convolution is split at
 // the channel concat (TSNet.py:195-197: cat(src_fea, tar_fea) -> conv): the per-source half is computed once per source set
 // (tsnet_set_sources, cached in clip mode), the shared target half once per driving frame; this kernel joins them and produces the
@@ -79,11 +40,14 @@ struct AddStatsArgs {
     int HW, C, S, rows_per_split, add_nmod;
 };
 
-__global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) {
+// The body of both statistics kernels: the thread layout, the fp64 accumulation of a float4 per row, the fixed-order LDS fold over the row
+// groups and the partial store.  ADD selects the load alone: the plain tensor, or the sum with its store of y.
+template <bool ADD, typename Args>
+__device__ __forceinline__ void stats_partial_body(const Args& a) {
     __shared__ double red[256 * 8];
     const int cq_total = a.C >> 2;
-    const int cols = cq_total < 256 ? cq_total : 256;
-    const int R = 256 / cols;
+    const int cols = cq_total < 256 ? cq_total : 256;   // float4 columns handled per block
+    const int R = 256 / cols;                            // row groups
     const int tid = threadIdx.x;
     const int cq = tid % cols + blockIdx.z * 256;
     const int rg = tid / cols;
@@ -94,16 +58,18 @@ __global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) 
     double sm[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0};
     if (rg < R && cq < cq_total) {
         const size_t cb = (size_t)cq * 4;
-        const int nb = n % a.add_nmod;
-        const float* bx = a.x + ((size_t)a.slot[n] * a.HW) * a.C + cb;
-        const float* ba = a.add + ((size_t)nb * a.HW) * a.C + cb;
-        float* by = a.y + ((size_t)n * a.HW) * a.C + cb;
+        int nb = 0, nx = n;                                  // the images of add and of x
+        if constexpr (ADD) { nb = n % a.add_nmod; nx = a.slot[n]; }
+        const float* bx = a.x + ((size_t)nx * a.HW) * a.C + cb;
+        const float* ba = nullptr;
+        float* by = nullptr;
+        if constexpr (ADD) { ba = a.add + ((size_t)nb * a.HW) * a.C + cb; by = a.y + ((size_t)n * a.HW) * a.C + cb; }
         for (int r = r0 + rg; r < r1; r += R) {
-            const float4 u = *reinterpret_cast<const float4*>(bx + (size_t)r * a.C);
-            const float4 w = *reinterpret_cast<const float4*>(ba + (size_t)r * a.C);
-            float4 v;
-            v.x = u.x + w.x; v.y = u.y + w.y; v.z = u.z + w.z; v.w = u.w + w.w;
-            *reinterpret_cast<float4*>(by + (size_t)r * a.C) = v;
+            float4 v = *reinterpret_cast<const float4*>(bx + (size_t)r * a.C);
+            if constexpr (ADD) {
+                v = add4(v, *reinterpret_cast<const float4*>(ba + (size_t)r * a.C));
+                *reinterpret_cast<float4*>(by + (size_t)r * a.C) = v;
+            }
             sm[0] += v.x; sq[0] += (double)v.x * v.x;
             sm[1] += v.y; sq[1] += (double)v.y * v.y;
             sm[2] += v.z; sq[2] += (double)v.z * v.z;
@@ -125,9 +91,14 @@ __global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) 
         for (int e = 0; e < 4; ++e) { o[e * 2] = tsm[e]; o[e * 2 + 1] = tsq[e]; }
     }
 }
+__global__ __launch_bounds__(256) void in_stats_partial_kernel(StatsArgs a) { stats_partial_body<false>(a); }
+__global__ __launch_bounds__(256) void add_stats_partial_kernel(AddStatsArgs a) { stats_partial_body<true>(a); }
 
 // stage 2: alpha = 1/sqrt(var+eps), beta = -mean*alpha  (the x*alpha+beta form ATen's CPU
 // batch-norm transform uses), one thread per (n, c).
+// (The tail -- mean, clamped variance, alpha, beta -- is not shared with in_finalize2_kernel and conv_epilogue: as in_alpha_beta(sm, sq, HW,
+// eps, ...) taking the two elements' addresses, the arrays and an index, or the sums by reference and the index as a functor, both kernels
+// kept their instruction and register counts but not their text: the zero fills of sm / sq swap, or the index is formed before the division.)
 __global__ void in_finalize_kernel(const double* __restrict__ part, float* __restrict__ alpha, float* __restrict__ beta,
                                    int NC, int C, int S, int HW, float eps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -227,19 +198,10 @@ __global__ __launch_bounds__(256) void norm_act_kernel(NormActArgs a) {
                 be = *reinterpret_cast<const float4*>(a.beta + (size_t)n * a.C + cq * 4);
                 cq += sc; if (cq >= c4n) cq -= c4n;
             }
-            v.x = __builtin_fmaf(v.x, al.x, be.x);
-            v.y = __builtin_fmaf(v.y, al.y, be.y);
-            v.z = __builtin_fmaf(v.z, al.z, be.z);
-            v.w = __builtin_fmaf(v.w, al.w, be.w);
+            v = fma4(v, al, be);
         }
-        if (a.relu) {
-            v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-            v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        }
-        if (a.resid) {
-            const float4 r = reinterpret_cast<const float4*>(a.resid)[i];
-            v.x = r.x + v.x; v.y = r.y + v.y; v.z = r.z + v.z; v.w = r.w + v.w;
-        }
+        if (a.relu) v = relu4(v);
+        if (a.resid) v = add4(reinterpret_cast<const float4*>(a.resid)[i], v);
         reinterpret_cast<float4*>(a.y)[i] = v;
     }
 }
@@ -278,14 +240,9 @@ __global__ __launch_bounds__(256) void fuse_resid_mean_kernel(FuseTailArgs a) {
             const float4 y = *reinterpret_cast<const float4*>(a.y2 + ((size_t)n * a.P + p) * C + c);
             const float4 al = *reinterpret_cast<const float4*>(a.alpha + (size_t)n * C + c);
             const float4 be = *reinterpret_cast<const float4*>(a.beta + (size_t)n * C + c);
-            acc.x += xr.x + __builtin_fmaf(y.x, al.x, be.x);
-            acc.y += xr.y + __builtin_fmaf(y.y, al.y, be.y);
-            acc.z += xr.z + __builtin_fmaf(y.z, al.z, be.z);
-            acc.w += xr.w + __builtin_fmaf(y.w, al.w, be.w);
+            acc = add4(acc, add4(xr, fma4(y, al, be)));
         }
-        const float kf = (float)a.K;
-        acc.x /= kf; acc.y /= kf; acc.z /= kf; acc.w /= kf;
-        *reinterpret_cast<float4*>(a.zbar + ((size_t)b * a.P + p) * C + c) = acc;
+        *reinterpret_cast<float4*>(a.zbar + ((size_t)b * a.P + p) * C + c) = div4(acc, (float)a.K);
     }
 }
 

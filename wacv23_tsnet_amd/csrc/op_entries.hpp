@@ -8,6 +8,18 @@
 #endif
 #include "launch.hpp"
 
+namespace {
+// the operand kinds tsnet_op_conv2d and tsnet_op_conv2d_epi take
+void op_check_nprod(int nprod) {
+    if (nprod != 1 && nprod != 3 && nprod != 4 && nprod != TSNET_NPROD_F16) throw ArgError("conv2d op: nprod must be 1 (bf16 operands), 16 (fp16 operands: one fp16 plane), 3 or 4 products");
+}
+// the fields every convolution operator fills from its arguments
+ConvCall op_conv_call(const float* x, const float* alpha, const float* beta, int relu, float bound, int N, int H, int W, float* y, int nprod) {
+    ConvCall c; c.x = x; c.alpha = alpha; c.beta = beta; c.relu = relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
+    return c;
+}
+}  // namespace
+
 extern "C" {
 
 const char* tsnet_op_last_error(void) { return g_op_error.c_str(); }
@@ -52,14 +64,12 @@ int tsnet_op_conv2d(const float* x, int N, int H, int W, int Cin, const float* w
                     float bound, int nprod, int kernel, int tile, float* y, void* stream) {
     OP_BEGIN
     if (!x || !w_oihw || !y) throw ArgError("null tensor");
-    if (nprod != 1 && nprod != 3 && nprod != 4 && nprod != TSNET_NPROD_F16) throw ArgError("conv2d op: nprod must be 1 (bf16 operands), 16 (fp16 operands: one fp16 plane), 3 or 4 products");
+    op_check_nprod(nprod);
     hipStream_t s = (hipStream_t)stream;
     Ctx ctx(s, current_device_cus());
-    ConvRequest req;
-    try { req = decode_tile_code(kernel, tile); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    const ConvRequest req = arg_checked([&] { return decode_tile_code(kernel, tile); });
     OpLayer op(w_oihw, bias, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, kernel == 3 ? 1 : 0);     // kernel 3: Winograd-along-x form (conv_w1.hpp)
-    ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
-    run_conv(ctx, op.L, c, req);
+    run_conv(ctx, op.L, op_conv_call(x, in_alpha, in_beta, in_relu, bound, N, H, W, y, nprod), req);
     HIP_TRY(hipStreamSynchronize(s));
     OP_END
 }
@@ -71,7 +81,7 @@ int tsnet_op_conv2d_epi(const float* x, int N, int H, int W, int Cin, const floa
                         float bound, int nprod, int kernel, int tile, float* y, const tsnet_conv_epi* epi, void* stream) {
     OP_BEGIN
     if (!x || !w_oihw || !y || !epi) throw ArgError("null tensor");
-    if (nprod != 1 && nprod != 3 && nprod != 4 && nprod != TSNET_NPROD_F16) throw ArgError("conv2d op: nprod must be 1 (bf16 operands), 16 (fp16 operands: one fp16 plane), 3 or 4 products");
+    op_check_nprod(nprod);
     const tsnet_conv_epi& e = *epi;
     if (e.stats < 0 || e.stats > 2) throw ArgError("conv2d_epi op: stats must be 0 (none), 1 (partials + finalize launch) or 2 (arrival counters offered)");
     if (e.repeat < 1) throw ArgError("conv2d_epi op: repeat must be at least 1");
@@ -81,24 +91,23 @@ int tsnet_op_conv2d_epi(const float* x, int N, int H, int W, int Cin, const floa
     if ((e.x_bf16 || e.y_bf16) && nprod != 1) throw ArgError("conv: bf16 storage goes with bf16 operands");
     hipStream_t s = (hipStream_t)stream;
     Ctx ctx(s, current_device_cus());
-    ConvRequest req;
-    try { req = decode_tile_code(kernel, tile); } catch (const std::invalid_argument& ex) { throw ArgError(ex.what()); }
+    const ConvRequest req = arg_checked([&] { return decode_tile_code(kernel, tile); });
     OpLayer op(w_oihw, bias, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, kernel == 3 ? 1 : 0);
-    ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_relu; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
+    ConvCall c = op_conv_call(x, in_alpha, in_beta, in_relu, bound, N, H, W, y, nprod);
     c.addend = e.addend; c.add_nmod = e.addend ? e.add_nmod : 1;
     c.amax_out = e.amax_out; c.in_amax = e.in_amax; c.bound_add = e.bound_add; c.x_bf16 = e.x_bf16; c.y_bf16 = e.y_bf16;
     if (e.stats) {                                      // tsnet_engine::conv_stats' request; stats = 1 withholds the counters
         c.stat_part = e.part; c.fin_alpha = e.alpha; c.fin_beta = e.beta; c.fin_counter = e.stats == 2 ? e.counters : nullptr;
     }
     if (in_alpha && !in_beta) throw ArgError("conv: alpha without beta");
-    ConvPlan p;
-    try { p = plan_conv(conv_shape(op.L, c), req, ctx.cus); } catch (const std::invalid_argument& ex) { throw ArgError(ex.what()); }
+    const ConvShape sh = conv_shape(op.L, c);
+    const ConvPlan p = arg_checked([&] { return plan_conv(sh, req, ctx.cus); });
     const size_t part_n = stat_part_doubles((size_t)N, (size_t)p.tpi, (size_t)Cout);
     if (e.stats && (e.part_capacity < 0 || part_n > (size_t)e.part_capacity))
         throw ArgError("conv2d_epi op: part holds " + std::to_string(e.part_capacity) + " doubles, the plan writes N * tpi * Cout * 2 = " + std::to_string(part_n));
     if (e.stats == 2 && (size_t)N * ((op.L.npad + 31) / 32) > kFinCounterInts)
         throw ArgError("conv2d_epi op: more (image, 32-channel group) pairs than arrival counters");
-    const int hw = conv_shape(op.L, c).ho() * conv_shape(op.L, c).wo();
+    const int hw = sh.ho() * sh.wo();
     for (int it = 0; it < e.repeat; ++it) {
         // every partial a NaN before each launch: an entry folded before its store is visible, or never written, shows in alpha / beta
         if (e.stats) HIP_TRY(hipMemsetAsync(e.part, 0xFF, part_n * sizeof(double), s));
@@ -137,13 +146,12 @@ int tsnet_op_upconv2d(const float* x, int N, int H, int W, int Cin, const float*
     if (N < 1 || H < 1 || W < 1 || (double)N * H * W * 4 * Cin >= 536870912.0) throw ArgError("upconv2d op: empty or too large a tensor");
     hipStream_t s = (hipStream_t)stream;
     Ctx ctx(s, current_device_cus());
-    ConvRequest req;
-    try { req = decode_tile_code(0, tile); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    const ConvRequest req = arg_checked([&] { return decode_tile_code(0, tile); });
     OpLayer op(w_oihw, bias, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s);
     // both routes answer to the fused form's plan: what it refuses is refused before anything is launched
-    ConvCall c; c.x = x; c.alpha = in_alpha; c.beta = in_beta; c.relu = in_alpha ? in_relu : 0; c.bound = bound; c.N = N; c.H = 2 * H; c.W = 2 * W; c.y = y; c.nprod = nprod;
+    ConvCall c = op_conv_call(x, in_alpha, in_beta, in_alpha ? in_relu : 0, bound, N, 2 * H, 2 * W, y, nprod);
     c.up2 = true;
-    try { (void)plan_conv(conv_shape(op.L, c), req, ctx.cus); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    arg_checked([&] { (void)plan_conv(conv_shape(op.L, c), req, ctx.cus); });
     DevBufs mem;
     if (kernel == 1) {
         float* up = mem.alloc<float>((size_t)N * 2 * H * 2 * W * Cin * sizeof(float));
@@ -162,7 +170,8 @@ int tsnet_op_conv2d_cat(const float* x, const float* x2, int N, int H, int W, in
     hipStream_t s = (hipStream_t)stream;
     Ctx ctx(s, current_device_cus());
     OpLayer op(w_oihw, bias, C1 + C2, Cout, ksize, stride, pad, pad_mode, nprod, s);
-    ConvCall c; c.x = x; c.x2 = x2; c.csplit = C1; c.x2_nmod = x2_nmod; c.bound = bound; c.N = N; c.H = H; c.W = W; c.y = y; c.nprod = nprod;
+    ConvCall c = op_conv_call(x, nullptr, nullptr, 0, bound, N, H, W, y, nprod);
+    c.x2 = x2; c.csplit = C1; c.x2_nmod = x2_nmod;
     run_conv(ctx, op.L, c);
     HIP_TRY(hipStreamSynchronize(s));
     OP_END
@@ -174,8 +183,7 @@ int tsnet_op_head(const float* x, int N, int H, int W, int C, const float* in_al
     if (!x || !w_oihw || !bias || !y) throw ArgError("null tensor");
     if (C < 4 || (C & 3)) throw ArgError("head op: C must be a multiple of 4");
     if (in_alpha && !in_beta) throw ArgError("head op: alpha without beta");
-    HeadRequest hr;
-    try { hr = decode_head_code(composite); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    const HeadRequest hr = arg_checked([&] { return decode_head_code(composite); });
     hipStream_t s = (hipStream_t)stream;
     const size_t wn = (size_t)3 * C * 49;
     DevBufs mem;
@@ -213,7 +221,7 @@ int tsnet_op_instnorm_stats(const float* x, int N, int HW, int C, float* alpha, 
     if (!x || !alpha || !beta) throw ArgError("null tensor");
     Ctx ctx((hipStream_t)stream, current_device_cus());
     DevBufs mem;
-    double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
+    double* part = mem.alloc<double>(stat_scratch_doubles(N, C) * sizeof(double));
     run_stats(ctx, x, N, HW, C, part, alpha, beta);
     HIP_TRY(hipStreamSynchronize(ctx.stream));
     OP_END
@@ -228,11 +236,28 @@ int tsnet_op_norm_act(const float* x, const float* alpha, const float* beta, int
     OP_END
 }
 
+// tsnet_op_upsample2x (fp32 tensors; returns with the launch enqueued) and tsnet_op_upsample2x_st (either storage; returns after the stream has drained)
+static void op_upsample_any(const float* x, const float* alpha, const float* beta, int relu, int N, int H, int W, int C, int x_bf16, int y_bf16,
+                            float* y, void* stream, bool drain) {
+    if (!x || !y) throw ArgError("upsample op: null tensor");
+    if (alpha && !beta) throw ArgError("upsample op: alpha without beta");
+    if (C < 4 || (C & 3)) throw ArgError("upsample op: C must be a multiple of 4");
+    if (N < 1 || H < 1 || W < 1) throw ArgError("upsample op: bad shape (N, H, W >= 1)");
+    Ctx ctx((hipStream_t)stream, current_device_cus());
+    run_upsample(ctx, x, alpha, beta, relu, N, H, W, C, y, x_bf16 != 0, y_bf16 != 0);
+    if (drain) HIP_TRY(hipStreamSynchronize(ctx.stream));
+}
+
 int tsnet_op_upsample2x(const float* x, const float* alpha, const float* beta, int relu, int N, int H, int W, int C, float* y, void* stream) {
     OP_BEGIN
-    if (!x || !y) throw ArgError("null tensor");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    run_upsample(ctx, x, alpha, beta, relu, N, H, W, C, y);
+    op_upsample_any(x, alpha, beta, relu, N, H, W, C, 0, 0, y, stream, false);
+    OP_END
+}
+
+int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta, int relu, int N, int H, int W, int C, int x_bf16, int y_bf16,
+                           float* y, void* stream) {
+    OP_BEGIN
+    op_upsample_any(x, alpha, beta, relu, N, H, W, C, x_bf16, y_bf16, y, stream, true);
     OP_END
 }
 
@@ -291,13 +316,10 @@ static void op_flow_impl(const float* tar_fea, const float* src_fea, const float
     fa.tq = that; fa.sq = shat; fa.tar_bbox = tar_bbox; fa.gx = gx; fa.gy = gy; fa.flow = flow;
     fa.src_bbox = src_bbox;
     fa.B = B; fa.P = P; fa.C = C; fa.h = h; fa.w = w; fa.H = H; fa.W = W; fa.sy = H / h; fa.sx = W / w;
-    std::unique_ptr<EventPair> ev(ms_out ? new EventPair : nullptr);
     run_flow(ctx, fa, NB, dslot, variant);
-    if (ev) HIP_TRY(hipEventRecord(ev->a, ctx.stream));
-    for (int r = 1; r < repeat; ++r) run_flow(ctx, fa, NB, dslot, variant);
-    if (ev) HIP_TRY(hipEventRecord(ev->b, ctx.stream));
+    const float ms = timed_repeats(ctx.stream, repeat - 1, [&](int) { run_flow(ctx, fa, NB, dslot, variant); });
     HIP_TRY(hipStreamSynchronize(ctx.stream));
-    if (ms_out) *ms_out = repeat > 1 ? ev->ms() / (float)(repeat - 1) : 0.f;
+    if (ms_out) *ms_out = ms;
 }
 
 int tsnet_op_flow(const float* tar_fea, const float* src_fea, const float* tar_bbox, const float* src_bbox,
@@ -325,49 +347,35 @@ int tsnet_op_flow_k_slots(const float* tar_fea, const float* src_fea, const floa
 
 int tsnet_flow_plan(int B, int h, int w, int C) { return (B < 1 || h < 1 || w < 1 || C < 8 || (C & 7)) ? -1 : flowp_plan(B, h, w, C); }
 
-int tsnet_op_warp(const float* src_fea, const float* flow, int B, int h, int w, int C, float* out, void* stream) {
-    OP_BEGIN
-    if (!src_fea || !flow || !out) throw ArgError("null tensor");
-    if (C & 3) throw ArgError("warp op: C must be a multiple of 4");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    DevBufs mem;
-    run_warp(ctx, src_fea, op_table_ext(mem, B, 1, B), flow, out, B, 1, h, w, C);
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    OP_END
-}
-
-int tsnet_op_warp_k(const float* src_fea, const float* flow, int B, int K, int h, int w, int C, float* out, int repeat, float* ms_out, void* stream) {
-    OP_BEGIN
-    if (!src_fea || !flow || !out) throw ArgError("null tensor");
-    if (C & 3) throw ArgError("warp op: C must be a multiple of 4");
-    if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    if (ms_out) *ms_out = 0.f;
-    DevBufs mem;
-    const int* d = op_table_ext(mem, B, K, B);        // uploaded once, outside the events
-    run_warp(ctx, src_fea, d, flow, out, B, K, h, w, C);
-    if (repeat > 1) {                    // launches 2 .. repeat between two events: the kernel ALONE (tools/warp_bench.py)
-        EventPair ev;
-        HIP_TRY(hipEventRecord(ev.a, ctx.stream));
-        for (int i = 1; i < repeat; ++i) run_warp(ctx, src_fea, d, flow, out, B, K, h, w, C);
-        HIP_TRY(hipEventRecord(ev.b, ctx.stream));
-        const float t = ev.ms();
-        if (ms_out) *ms_out = t / (float)(repeat - 1);
-    }
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    OP_END
-}
-
-// tsnet_op_warp_k_shared (ext = its SB) and tsnet_op_warp_k_slots (ext < 0: the caller's table)
-static void op_warp_any(const float* src_fea, const float* flow, int B, int K, int ext, const int* slots, int n_src, int h, int w, int C, float* out, void* stream) {
+// every spelling of the warp: tsnet_op_warp (K = 1) and tsnet_op_warp_k (ext = B: the identity), tsnet_op_warp_k_shared (ext = its SB) and
+// tsnet_op_warp_k_slots (ext < 0: the caller's table).  repeat > 1 re-launches the kernel ALONE between two events, the table uploaded once
+// and the first launch outside them (tools/warp_bench.py); *ms_out = the mean of those launches, 0 without them.
+static void op_warp_any(const float* src_fea, const float* flow, int B, int K, int ext, const int* slots, int n_src, int h, int w, int C, float* out,
+                        void* stream, int repeat = 1, float* ms_out = nullptr) {
     if (!src_fea || !flow || !out) throw ArgError("warp op: null tensor");
     if (C < 4 || (C & 3)) throw ArgError("warp op: C must be a multiple of 4");
     if (B < 1 || K < 1 || K > TSNET_MAX_SOURCES || h < 1 || w < 1) throw ArgError("warp op: bad shape (1 <= K <= 8 sources, B, h, w >= 1)");
     if (ext >= 0 && (ext < 1 || B % ext)) throw ArgError("warp op: the source-batch extent must divide the batch");
     Ctx ctx((hipStream_t)stream, current_device_cus());
+    if (ms_out) *ms_out = 0.f;
     DevBufs mem;
-    run_warp(ctx, src_fea, ext >= 0 ? op_table_ext(mem, B, K, ext) : op_slot_table(mem, "warp op", slots, K * B, n_src), flow, out, B, K, h, w, C);
+    const int* d = ext >= 0 ? op_table_ext(mem, B, K, ext) : op_slot_table(mem, "warp op", slots, K * B, n_src);
+    run_warp(ctx, src_fea, d, flow, out, B, K, h, w, C);
+    const float ms = timed_repeats(ctx.stream, repeat - 1, [&](int) { run_warp(ctx, src_fea, d, flow, out, B, K, h, w, C); });
+    if (ms_out) *ms_out = ms;
     HIP_TRY(hipStreamSynchronize(ctx.stream));
+}
+
+int tsnet_op_warp(const float* src_fea, const float* flow, int B, int h, int w, int C, float* out, void* stream) {
+    OP_BEGIN
+    op_warp_any(src_fea, flow, B, 1, B, nullptr, 0, h, w, C, out, stream);
+    OP_END
+}
+
+int tsnet_op_warp_k(const float* src_fea, const float* flow, int B, int K, int h, int w, int C, float* out, int repeat, float* ms_out, void* stream) {
+    OP_BEGIN
+    op_warp_any(src_fea, flow, B, K, B, nullptr, 0, h, w, C, out, stream, repeat, ms_out);
+    OP_END
 }
 
 int tsnet_op_warp_k_shared(const float* src_fea, const float* flow, int B, int K, int SB, int h, int w, int C, float* out, void* stream) {
@@ -393,7 +401,7 @@ static void op_add_stats_any(const float* x, const float* add, int add_nmod, int
     Ctx ctx((hipStream_t)stream, current_device_cus());
     DevBufs mem;
     const int* d = ext >= 0 ? op_table_ext(mem, add_nmod, N / add_nmod, ext) : op_slot_table(mem, "add_stats op", slots, N, n_src);
-    double* part = mem.alloc<double>((size_t)N * 64 * C * 2 * sizeof(double));
+    double* part = mem.alloc<double>(stat_scratch_doubles(N, C) * sizeof(double));
     run_add_stats(ctx, x, d, add, add_nmod, y, N, HW, C, part, alpha, beta);
     HIP_TRY(hipStreamSynchronize(ctx.stream));
 }
@@ -551,19 +559,6 @@ int tsnet_op_pack_input_u8(const uint8_t* const* img, const uint8_t* const* lbl,
     OP_END
 }
 
-int tsnet_op_upsample2x_st(const float* x, const float* alpha, const float* beta, int relu, int N, int H, int W, int C, int x_bf16, int y_bf16,
-                           float* y, void* stream) {
-    OP_BEGIN
-    if (!x || !y) throw ArgError("upsample op: null tensor");
-    if (alpha && !beta) throw ArgError("upsample op: alpha without beta");
-    if (C < 4 || (C & 3)) throw ArgError("upsample op: C must be a multiple of 4");
-    if (N < 1 || H < 1 || W < 1) throw ArgError("upsample op: bad shape (N, H, W >= 1)");
-    Ctx ctx((hipStream_t)stream, current_device_cus());
-    run_upsample(ctx, x, alpha, beta, relu, N, H, W, C, y, x_bf16 != 0, y_bf16 != 0);
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    OP_END
-}
-
 int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int pad_mode, int norm,
                      int variant, int iters, float* ms_out, void* stream) {
     OP_BEGIN
@@ -571,8 +566,7 @@ int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stri
     hipStream_t s = (hipStream_t)stream;
     Ctx ctx(s, current_device_cus());
     // variant (-1 = the layer's own kernel and tile): conv_plan.hpp decode_bench_variant
-    BenchVariant bv;
-    try { bv = decode_bench_variant(variant); } catch (const std::invalid_argument& e) { throw ArgError(e.what()); }
+    const BenchVariant bv = arg_checked([&] { return decode_bench_variant(variant); });
     const int nprod = bv.nprod;
     const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
     const size_t xn = (size_t)N * H * W * Cin, yn = (size_t)N * Ho * Wo * Cout, wn = (size_t)Cout * Cin * ksize * ksize;
@@ -595,8 +589,8 @@ int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stri
         // big layers), as consecutive layers of a forward do; the default re-launches one layer, whose planes stay cache-resident
         std::vector<std::unique_ptr<OpLayer>> cold;
         if (bv.cold) for (int i = 0; i < 24; ++i) cold.emplace_back(new OpLayer(hbuf.data(), nullptr, Cin, Cout, ksize, stride, pad, pad_mode, nprod, s, form));
-        ConvCall c; c.x = x; c.N = N; c.H = H; c.W = W; c.y = y; c.bound = (norm & 1) ? 64.f : 1.f; c.nprod = nprod;
-        if (norm & 1) { c.alpha = al; c.beta = be; c.relu = 1; }
+        ConvCall c = op_conv_call(x, nullptr, nullptr, 0, 1.f, N, H, W, y, nprod);
+        if (norm & 1) { c.alpha = al; c.beta = be; c.relu = 1; c.bound = 64.f; }
         if (norm & 2) {                                              // with the InstanceNorm statistics of the output, as the forward's layers run
             const size_t tpi = ((size_t)Ho * Wo + 63) / 64;
             c.stat_part = mem.alloc<double>(stat_part_doubles(N, tpi, Cout) * sizeof(double));
@@ -605,11 +599,7 @@ int tsnet_bench_conv(int N, int H, int W, int Cin, int Cout, int ksize, int stri
             HIP_TRY(hipMemset(c.fin_counter, 0, kFinCounterInts * sizeof(int)));
         }
         for (int i = 0; i < 2; ++i) run_conv(ctx, op.L, c, bv.req);
-        EventPair ev;
-        HIP_TRY(hipEventRecord(ev.a, s));
-        for (int i = 0; i < iters; ++i) run_conv(ctx, cold.empty() ? op.L : cold[(size_t)i % cold.size()]->L, c, bv.req);
-        HIP_TRY(hipEventRecord(ev.b, s));
-        *ms_out = ev.ms() / iters;
+        *ms_out = timed_repeats(s, iters, [&](int i) { run_conv(ctx, cold.empty() ? op.L : cold[(size_t)i % cold.size()]->L, c, bv.req); });
     }
     OP_END
 }

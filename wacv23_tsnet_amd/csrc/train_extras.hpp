@@ -15,6 +15,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "flow_warp.hpp"      // grid_sample_taps
+
 namespace tsnet {
 
 struct PatchWarpArgs {
@@ -38,24 +40,17 @@ __global__ __launch_bounds__(256) void patch_warp_kernel(PatchWarpArgs a) {
         const int p = ty * a.w + tx;
         const float gx = a.flow[((size_t)n * P + p) * 2 + 0];
         const float gy = a.flow[((size_t)n * P + p) * 2 + 1];
-        const float ix = ((gx + 1.f) * a.w - 1.f) / 2.f;    // grid_sampler_unnormalize, align_corners=False
-        const float iy = ((gy + 1.f) * a.h - 1.f) / 2.f;
-        const float fx = floorf(ix), fy = floorf(iy);
-        const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-        const float wnw = (x1 - ix) * (y1 - iy), wne = (ix - x0) * (y1 - iy);
-        const float wsw = (x1 - ix) * (iy - y0), wse = (ix - x0) * (iy - y0);
-        const bool xin0 = x0 >= 0 && x0 < a.w, xin1 = x1 >= 0 && x1 < a.w;
-        const bool yin0 = y0 >= 0 && y0 < a.h, yin1 = y1 >= 0 && y1 < a.h;
+        const GridTaps t = grid_sample_taps(gx, gy, a.w, a.h);
         const float* img = a.src[s] + (size_t)b * 3 * HW;
         const float dv = a.div[s];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* pl = img + (size_t)c * HW;
             float v = 0.f;
-            if (yin0 && xin0) v = (pl[(size_t)(y0 * a.down + dy) * a.W + x0 * a.down + dx] / dv) * wnw;
-            if (yin0 && xin1) v = __builtin_fmaf(pl[(size_t)(y0 * a.down + dy) * a.W + x1 * a.down + dx] / dv, wne, v);
-            if (yin1 && xin0) v = __builtin_fmaf(pl[(size_t)(y1 * a.down + dy) * a.W + x0 * a.down + dx] / dv, wsw, v);
-            if (yin1 && xin1) v = __builtin_fmaf(pl[(size_t)(y1 * a.down + dy) * a.W + x1 * a.down + dx] / dv, wse, v);
+            if (t.yin0 && t.xin0) v = (pl[(size_t)(t.y0 * a.down + dy) * a.W + t.x0 * a.down + dx] / dv) * t.wnw;
+            if (t.yin0 && t.xin1) v = __builtin_fmaf(pl[(size_t)(t.y0 * a.down + dy) * a.W + t.x1 * a.down + dx] / dv, t.wne, v);
+            if (t.yin1 && t.xin0) v = __builtin_fmaf(pl[(size_t)(t.y1 * a.down + dy) * a.W + t.x0 * a.down + dx] / dv, t.wsw, v);
+            if (t.yin1 && t.xin1) v = __builtin_fmaf(pl[(size_t)(t.y1 * a.down + dy) * a.W + t.x1 * a.down + dx] / dv, t.wse, v);
             a.out[((size_t)n * 3 + c) * HW + pix] = v;
         }
     }
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(256) void cosine_partial_kernel(const float* __rest
             n1 += u.x * u.x + u.y * u.y + u.z * u.z + u.w * u.w;
             n2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
         }
-#pragma unroll
+#pragma unroll      // (not shared: three wave_sum calls in a row order the twelve shuffles sum by sum, 262 -> 259 instructions, 44 -> 42 VGPRs)
         for (int off = 32; off > 0; off >>= 1) { dot += __shfl_xor(dot, off); n1 += __shfl_xor(n1, off); n2 += __shfl_xor(n2, off); }
         float a1 = sqrtf(n1), a2 = sqrtf(n2);                // F.cosine_similarity: each norm clamped at eps = 1e-8
         a1 = a1 < 1e-8f ? 1e-8f : a1; a2 = a2 < 1e-8f ? 1e-8f : a2;
