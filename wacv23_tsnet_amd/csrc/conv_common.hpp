@@ -7,8 +7,8 @@
 //   transform_octet                       IN + ReLU (branch-free), the operand scale, zero padding kept after the affine transform
 //   store_operand_octet / _quad           one plane, or the hi / lo split (two pairs per statement), then the planes' stores
 //   bf16x8_widen / bf16x4_widen           bf16 storage -> fp32, exactly
-//   patch_tile, patch_out_index           the PR x 32 rectangle of a patch tile; its epilogue row map
-//   row_tile, row_out_index               the row tile of the implicit GEMMs; its epilogue row map
+//   patch_tile, patch_rows                the PR x 32 rectangle of a patch tile; its epilogue row map
+//   row_tile, row_tile_rows               the row tile of the implicit GEMMs; its epilogue row map
 // conv_w1 resolves an item's row once and its columns per pixel, so it uses reflect_index alone, not the pair.
 // A kernel's code must not move when a step is shared (tools/isa_diff.py against the parent commit): where a helper changed the code of a tile
 // function, that function keeps its own copy under a "not shared" comment.  Deliberately NOT shared, for the same reason: the weight-plane
@@ -437,8 +437,11 @@ __device__ __forceinline__ PatchTile patch_tile(const ConvArgs& a, int tile_m) {
     t.oy0 = (t.tin / tcols) * PR; t.ox0 = (t.tin % tcols) * kPatchCols;
     return t;
 }
-// ... and the output position of its local row l (32 per output row) for the epilogue; m_img = the image's first position
-__device__ __forceinline__ int patch_out_index(const ConvArgs& a, int m_img, int oy0, int ox0, int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); }
+// The epilogue's row map, 32 local rows at a time: local row l0 + d (l0 a multiple of 32, d < 32) lies at output position m0 + d, and the
+// first nv of the 32 exist
+struct EpiRows { int m0, nv; };
+// ... of a patch tile: 32 local rows = one output row of the rectangle, all of them there; m_img = the image's first position
+__device__ __forceinline__ EpiRows patch_rows(const ConvArgs& a, int m_img, int oy0, int ox0, int l0) { return EpiRows{m_img + (oy0 + (l0 >> 5)) * a.Wo + ox0, 32}; }
 
 // A ROW tile of the implicit GEMMs: block -> BM consecutive output positions from r0 of ONE image (a ragged last tile) x BN channels from n0.
 struct RowTile { int tile_m, n0, hw, img, r0; };
@@ -453,8 +456,8 @@ __device__ __forceinline__ RowTile row_tile(const ConvArgs& a, int block) {
     t.r0 = (t.tile_m - t.img * a.tpi) * BM;
     return t;
 }
-// ... and the output position of its local row l for the epilogue: -1 for a row past the end of the image
-__device__ __forceinline__ int row_out_index(const RowTile& t, int m_img, int l) { return t.r0 + l < t.hw ? m_img + t.r0 + l : -1; }
+// ... and its epilogue row map: consecutive positions, as many as the image has left (<= 0: the block lies past its end)
+__device__ __forceinline__ EpiRows row_tile_rows(const RowTile& t, int m_img, int l0) { return EpiRows{m_img + t.r0 + l0, t.hw - t.r0 - l0}; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Bilinear x2 upsample (nn.Upsample, align_corners = False) in ONE spelling: upsample2x_kernel (norm_elementwise.hpp) and the fused patch
@@ -498,16 +501,22 @@ __device__ __forceinline__ float4 fma4(const float4& a, float s, const float4& c
 
 // ---------------------------------------------------------------------------------------------------------------
 // Shared epilogue: bias, optional per-pixel addend, fp64 InstanceNorm partial sums of the tile (fixed order: deterministic), fp32 store (last).
-// m_of(l) maps the local row l of the tile to the output position m (or -1: a row past the end of the image).
+// rows_of(l0) gives the row map (EpiRows above) for the wave's row block l0; img = the tile's image (a tile lies inside one image); RAGGED: nv may be below 32.
+// A lane's 16 values of an MFMA block are rows d = c(r) + 4 lh, c(r) = (r & 3) + 8 (r >> 2), of ONE channel: every index below is a
+// per-lane part formed once (4 lh Cout + li), a wave-uniform part per block (m0 Cout + the block's first channel) and c(r) Cout -- no
+// index map, no division and no 64-bit multiply per value.  The per-lane part is a 32-bit byte offset: at most 16 Cout + 124 (validate_conv:
+// Kpad Npad < 2^30 with Kpad >= 16, so Cout < 2^26); block base and c(r) Cout are 64-bit and wave-uniform.
 // STAT_WAVE: the wave that reduces the tile's statistics partials and hands them off (BN <= 64: one wave does it alone).  conv_w1 names a
 // producer wave -- idle in the epilogue -- so that no MFMA wave waits for the store drain and the arrival counter's round trip.
-template <int BN, int WARPS_M, int WARPS_N, int MT, int NTL, int STAT_WAVE = 0, typename MOf>
+template <int BN, int WARPS_M, int WARPS_N, int MT, int NTL, int STAT_WAVE = 0, bool RAGGED = false, typename RowsOf>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&tot)[MT][NTL], unsigned char* smem_raw, int tid, int wave, int n0,
-                                              size_t stat_tile, MOf m_of, const bool active = true) {
+                                              size_t stat_tile, int img, RowsOf rows_of, const bool active = true) {
     constexpr int WM = MT * 32, WN = NTL * 32;
     const int lane = tid & 63, li = lane & 31, lh = lane >> 5;
     const int wm0 = (wave / WARPS_N) * WM, wn0 = (wave % WARPS_N) * WN;
     const int hw = a.Ho * a.Wo;
+    const unsigned lane_el = (unsigned)(4 * lh * a.Cout + li);       // the lane's own part of every element offset
+    auto row_c = [](int r) __attribute__((always_inline)) { return (r & 3) + 8 * (r >> 2); };
     double csum[NTL], csq[NTL];
 #pragma unroll
     for (int j = 0; j < NTL; ++j) { csum[j] = 0.0; csq[j] = 0.0; }
@@ -515,29 +524,48 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&tot)[M
     // pass 1: the values (bias, addend) in place, their statistics and maximum.  The stores come LAST (pass 2 below): the statistics
     // hand-off drains this wave's outstanding stores before the workgroup counts itself, and with the tile's 32 - 64 KiB of output in
     // flight that drain was the longest wait of the epilogue -- exposed in full where one workgroup owns the CU (conv_w1).
+    // Per value still: v = tot + bias, then + addend, then csum / csq in (i, j, r) order -- the tests on a.bias, a.addend, a.stat_part stand
+    // around the value loops, and the addend's 16 loads of a block are issued together.
+    // the addend of image img % add_nmod at the position inside the image = the output's own offset, from a base moved by whole images
+    const float* const addend = a.addend ? a.addend + (ptrdiff_t)(img % a.add_nmod - img) * hw * a.Cout : nullptr;
+    if (active) {
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
+        for (int i = 0; i < MT; ++i) {
+            const EpiRows rows = rows_of(wm0 + i * 32);
+            const int nvl = rows.nv - 4 * lh;                        // row c(r) + 4 lh exists: c(r) < nvl
 #pragma unroll
-        for (int j = 0; j < NTL; ++j) {
-            const int n = n0 + wn0 + j * 32 + li;
-            const bool nok = n < a.Cout;
-            const float bv = (a.bias && nok) ? a.bias[n] : 0.f;
+            for (int j = 0; j < NTL; ++j) {
+                const int nb = n0 + wn0 + j * 32, n = nb + li;
+                const bool nok = n < a.Cout;
+                const float bv = (a.bias && nok) ? a.bias[n] : 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m_of(wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh);
-                const bool mok = active && m >= 0;
-                float v = tot[i][j][r] + bv;
-                if (a.addend && nok && mok) {
-                    const int img = m / hw;
-                    v += a.addend[((size_t)(img % a.add_nmod) * hw + (m - img * hw)) * a.Cout + n];
+                for (int r = 0; r < 16; ++r) tot[i][j][r] += bv;
+                if (addend && nok) {
+                    const float* const ab = addend + ((size_t)rows.m0 * a.Cout + nb);             // wave-uniform
+                    float av[16];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        av[r] = (!RAGGED || row_c(r) < nvl) ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(ab + (size_t)row_c(r) * a.Cout) + lane_el * 4u) : 0.f;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (!RAGGED || row_c(r) < nvl) tot[i][j][r] += av[r];
                 }
-                tot[i][j][r] = v;
-                if (a.stat_part && mok) { csum[j] += (double)v; csq[j] += (double)v * (double)v; }
-                if (nok && mok) vmax = __builtin_fmaxf(vmax, __builtin_fabsf(v));
+                if (a.stat_part) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float v = tot[i][j][r];
+                        if (!RAGGED || row_c(r) < nvl) { csum[j] += (double)v; csq[j] += (double)v * (double)v; }
+                    }
+                }
+                if (nok) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (!RAGGED || row_c(r) < nvl) vmax = __builtin_fmaxf(vmax, __builtin_fabsf(tot[i][j][r]));
+                }
             }
         }
     }
-    if (a.amax_out) tsnet_publish_amax(a.amax_out + stat_tile / (size_t)a.tpi, vmax);        // a tile lies inside one image
+    if (a.amax_out) tsnet_publish_amax(a.amax_out + img, vmax);
     if (a.stat_part) {
         __syncthreads();
         double* red = reinterpret_cast<double*>(smem_raw);
@@ -570,8 +598,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&tot)[M
             // storing wave's stores drained before the workgroup counts itself.  The drain is inline asm on purpose: the compiler may drop
             // a builtin s_waitcnt it can prove redundant.  The workgroup that reads fin_S - 1 sums the partials in a fixed order
             // (four interleaved groups, then g0+g1+g2+g3): run-to-run deterministic.
-            const int S = a.fin_S;
-            const int img = (int)(stat_tile / (size_t)S);
+            const int S = a.fin_S;                                                                 // = tiles per image: the counter is the image's (img)
             const int ntn = (a.Npad + 31) / 32;                                                    // 32 = narrowest tile
             int* counter = a.fin_counter + (size_t)img * ntn + n0 / 32;
             const bool mine = stid >= 0 && stid < BN && n0 + stid < a.Cout;
@@ -645,19 +672,28 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&tot)[M
         }
     }
     // pass 2: the stores (fp32, or bf16 in the bf16-storage mode)
-    unsigned short* const y16 = reinterpret_cast<unsigned short*>(a.y);
+    if (!active) return;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
+        const EpiRows rows = rows_of(wm0 + i * 32);
+        const int nvl = rows.nv - 4 * lh;
 #pragma unroll
         for (int j = 0; j < NTL; ++j) {
-            const int n = n0 + wn0 + j * 32 + li;
-            if (n >= a.Cout) continue;
+            const int nb = n0 + wn0 + j * 32;
+            if (nb + li >= a.Cout) continue;
+            const size_t blk = (size_t)rows.m0 * a.Cout + nb;                                       // wave-uniform
+            if (a.y_bf16) {
+                unsigned short* const yb = reinterpret_cast<unsigned short*>(a.y) + blk;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m_of(wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh);
-                if (!(active && m >= 0)) continue;
-                if (a.y_bf16) y16[(size_t)m * a.Cout + n] = bf16_rne(tot[i][j][r]);
-                else a.y[(size_t)m * a.Cout + n] = tot[i][j][r];
+                for (int r = 0; r < 16; ++r)
+                    if (!RAGGED || row_c(r) < nvl)
+                        *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(yb + (size_t)row_c(r) * a.Cout) + lane_el * 2u) = bf16_rne(tot[i][j][r]);
+            } else {
+                float* const yb = a.y + blk;
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (!RAGGED || row_c(r) < nvl)
+                        *reinterpret_cast<float*>(reinterpret_cast<char*>(yb + (size_t)row_c(r) * a.Cout) + lane_el * 4u) = tot[i][j][r];
             }
         }
     }

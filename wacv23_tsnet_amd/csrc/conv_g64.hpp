@@ -201,7 +201,7 @@ void conv_g64_kernel(ConvArgs a) {
         for (int r = 0; r < 16; ++r) out[i][0][r] = tot[i][r] * unscale;
     const int m_img = img * hw;
     __syncthreads();                                                 // the stages are free: the epilogue reduces through them
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, out, smem_raw, tid, wave, n0, (size_t)rt.tile_m, [&](int l) { return row_out_index(rt, m_img, l); });
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL, 0, true>(a, out, smem_raw, tid, wave, n0, (size_t)rt.tile_m, img, [&](int l0) { return row_tile_rows(rt, m_img, l0); });
 }
 
 }  // namespace tsnet

@@ -426,8 +426,8 @@ __device__ __forceinline__ void h2_tile(const ConvArgs& a, unsigned char* smem_r
 #pragma unroll
             for (int r = 0; r < 16; ++r) tot[i][j][r] *= unscale;    // exact: power of two
     const int m_img = img * a.Ho * a.Wo;
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,      // (not patch_out_index, here and in h2s / h2d: sharing changes the code of 71 kernels)
-                                                 [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); }, kg == 0);
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin, img,
+                                                 [&](int l0) { return patch_rows(a, m_img, oy0, ox0, l0); }, kg == 0);
 }
 
 // LDS bytes of an h2 tile: two stages x two planes x two octet regions + the sink + the transform table (two-plane offsets in every mode)
@@ -514,15 +514,23 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
         const int iy = reflect_index(oy0 - 3 + pr, a.H), ix = reflect_index(ox0 - 3 + pc, a.W);
         const unsigned v = pp < PP ? (unsigned)((((img * a.H + iy) * a.W) + ix) * 32) : kOOB;
         F4 x0 = TSNET_BUF_LOAD16(rsx, v, 0u), x1 = TSNET_BUF_LOAD16(rsx, v, 16u);
+        if (ONEP) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { x0.v[e] *= in_scale; x1.v[e] *= in_scale; }
+            for (int e = 0; e < 4; ++e) { x0.v[e] *= in_scale; x1.v[e] *= in_scale; }
+        }
         if (pp < 384) {                                               // slots 380..383 hold zeros (never read, kept finite)
             F4 Hh, Ll;                                                // (not store_operand_octet: sharing changes the code of 2 kernels)
             if (ONEP) {
                 one_plane_octet<F16P>(x0, x1, Hh);
                 *reinterpret_cast<F4*>(smem_raw + pp * 16) = Hh;
             } else {
-                split_h2_octet(x0, x1, Hh, Ll);
+                // the power-of-two scale rides in the split (conv_w1's producers): x * in_scale is exact, so hi = rne16(x in_scale) and
+                // lo = rne16(x in_scale - hi) are the halves of the scaled value -- sixteen multiplies per pixel slot less
+                unsigned hw[4], lw[4];
+                TSNET_SPLIT_2PAIRS_SCALED(x0.v[0], x0.v[1], x0.v[2], x0.v[3], in_scale, hw[0], lw[0], hw[1], lw[1]);
+                TSNET_SPLIT_2PAIRS_SCALED(x1.v[0], x1.v[1], x1.v[2], x1.v[3], in_scale, hw[2], lw[2], hw[3], lw[3]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { Hh.v[e] = __builtin_bit_cast(float, hw[e]); Ll.v[e] = __builtin_bit_cast(float, lw[e]); }
                 *reinterpret_cast<F4*>(smem_raw + pp * 16) = Hh;
                 *reinterpret_cast<F4*>(smem_raw + PLANE_S + pp * 16) = Ll;
             }
@@ -535,7 +543,9 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
     const int base = (wrow * MT * PC + li) * 16;
     // (slot offset of tap 2 st, and how far its partner tap 2 st + 1 lies) per step: a table in constant memory, read with scalar loads --
     // the loop over the chains is rolled, and deriving tap row and column of a runtime step (t0 / 7, t0 % 7) cost 84 scalar instructions per
-    // iteration beside 36 MFMAs (tools/isa_mix.py): every one an issue slot the MFMAs did not get
+    // iteration beside 36 MFMAs (tools/isa_mix.py): every one an issue slot the MFMAs did not get.  (Unrolling the four chains makes every
+    // offset an immediate, but the 150 MFMAs in one block take 168 VGPRs and spill; a running weight offset leaves the loop's 25 scalar
+    // instructions at 25: both tried on the ISA, neither kept.)
     struct StepTab { int off[25], delta[25]; };
     static constexpr StepTab kStep = [] {
         StepTab t{};
@@ -597,8 +607,8 @@ __device__ __forceinline__ void h2s_tile(const ConvArgs& a, unsigned char* smem_
         for (int r = 0; r < 16; ++r) tot[i][0][r] *= unscale;                     // exact: power of two
     const int m_img = img * a.Ho * a.Wo;
     __syncthreads();                                                  // the epilogue reuses the patch region for its reduction
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,
-                                                 [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); });
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin, img,
+                                                 [&](int l0) { return patch_rows(a, m_img, oy0, ox0, l0); });
 }
 
 constexpr int kH2sLds = 2 * 384 * 16 + 2048;     // two planes of 384 slots (+ room for the epilogue's flag word at 8192)
@@ -837,8 +847,8 @@ __device__ __forceinline__ void h2d_tile(const ConvArgs& a, unsigned char* smem_
             for (int r = 0; r < 16; ++r) tot[i][j][r] *= unscale;
     const int m_img = img * a.Ho * a.Wo;
     __syncthreads();                                                 // the epilogue reuses the patch region
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,
-                                                 [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); });
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin, img,
+                                                 [&](int l0) { return patch_rows(a, m_img, oy0, ox0, l0); });
 }
 
 // two stages x two planes x two octet regions + sink (+ 2 Cin floats x 2 of the table, added by the launcher)

@@ -185,9 +185,13 @@ void conv_h2r_kernel(ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < NTL; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) tot[i][j][r] *= unscale;
+            for (int r = 0; r < 16; ++r) {
+                float v = tot[i][j][r] * unscale;
+                TSNET_OPAQUE_V(v);                                   // this unit is built with the SLP vectoriser: straight into the epilogue's bias adds it
+                tot[i][j][r] = v;                                    // pairs multiply and add into v_pk_mul_f32 / v_pk_add_f32 (none beside MFMAs)
+            }
     const int m_img = img * hw;
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)rt.tile_m, [&](int l) { return row_out_index(rt, m_img, l); });
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL, 0, true>(a, tot, smem_raw, tid, wave, n0, (size_t)rt.tile_m, img, [&](int l0) { return row_tile_rows(rt, m_img, l0); });
 }
 
 constexpr int h2r_lds_bytes(int Cin) { return 2 * 2 * 128 * 32 + 64 + 2 * Cin * 4; }

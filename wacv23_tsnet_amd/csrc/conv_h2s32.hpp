@@ -143,15 +143,15 @@ void conv_h2s32_kernel(ConvArgs a) {
     step(24, 0); step(24, 1);                                                     // tap 48 (their look-ahead reads tap 48 again and zeros past K)
     fold();
 
-    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;      // (not conv_unscale, nor patch_out_index below: either changes the code of 3 kernels)
+    const float unscale = a.w_unscale ? in_unscale * a.w_unscale[0] : in_unscale;      // (not conv_unscale: sharing changes the code of 3 kernels)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) tot[i][0][r] *= unscale;                     // exact: power of two
     const int m_img = img * a.Ho * a.Wo;
     __syncthreads();                                                              // the epilogue reuses the patch region for its reduction
-    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin,
-                                                 [&](int l) { return m_img + (oy0 + (l >> 5)) * a.Wo + ox0 + (l & 31); });
+    conv_epilogue<BN, WARPS_M, WARPS_N, MT, NTL>(a, tot, smem_raw, tid, wave, n0, (size_t)img * pt.tper + pt.tin, img,
+                                                 [&](int l0) { return patch_rows(a, m_img, oy0, ox0, l0); });
 }
 
 }  // namespace tsnet

@@ -402,8 +402,8 @@ __device__ __forceinline__ void w1_chunk(const ConvArgs& a, unsigned char* smem_
             }
         }
         const int m_img = t.img * a.Ho * a.Wo;
-        conv_epilogue<64, 4, 2, 1, 1, 8>(a, out, ebase, tid_e, consumer ? wave : nt, t.n0, (size_t)t.img * tper + t.tin,
-                                         [&](int l) { return patch_out_index(a, m_img, t.oy0, t.ox0, l); }, consumer);
+        conv_epilogue<64, 4, 2, 1, 1, 8>(a, out, ebase, tid_e, consumer ? wave : nt, t.n0, (size_t)t.img * tper + t.tin, t.img,
+                                         [&](int l0) { return patch_rows(a, m_img, t.oy0, t.ox0, l0); }, consumer);
     };
 
     if (wave >= 8) {

@@ -196,7 +196,7 @@ __device__ __forceinline__ void w1_tile_one(const ConvArgs& a, unsigned char* sm
     w1_output_transform(ex + (size_t)(mq * 16) * 64 + wn0 + li, 64 * 64, lh, out[0][0]);
     __syncthreads();                                                 // the shared epilogue reuses the region for its reductions
     const int m_img = img * a.Ho * a.Wo;
-    conv_epilogue<64, 4, 2, 1, 1>(a, out, smem_raw, tid, consumer ? wave : nt, n0, (size_t)img * pt.tper + pt.tin, [&](int l) { return patch_out_index(a, m_img, oy0, ox0, l); }, consumer);
+    conv_epilogue<64, 4, 2, 1, 1>(a, out, smem_raw, tid, consumer ? wave : nt, n0, (size_t)img * pt.tper + pt.tin, img, [&](int l0) { return patch_rows(a, m_img, oy0, ox0, l0); }, consumer);
 }
 
 template <int NPROD, bool AFFINE, int OPT = 0>
